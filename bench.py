@@ -9,7 +9,10 @@ loss -> student data-gradient backward -> adapter backward [-> ONE RCCL all-redu
 gradient when N>1, on the communicator's own HIP stream, joined before AdamW] -> fused AdamW.  Weak scaling: ranks
 share nothing but the adapter-gradient all-reduce.  Per-GPU batch: 4 at N=1 (BASELINE configs[1]), 8 at N>1
 (configs[2]: global 64 = 8 x 8); `--batch` overrides.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set up, W warm-up steps, K timed
+steps, `--dump-outputs DIR` (what the last timed step computed, as .npy) if given, the line.  `--full` adds everything else
+the line can carry: energy, dead-row elimination, the per-kernel roofline replay, the CPU-oracle baseline, and at N > 1 the
+single-GPU-equivalent steps.
 """
 import argparse
 import ctypes
@@ -333,7 +336,9 @@ def energy_fields(sampler, ms_mean, images_per_step, tflop_per_step):
     """The chip is power-bound under this workload (the clock follows the load), so energy per step is the currency an A/B
     should be judged in: J/step = mean board power over the timed region x mean step time (the region is K back-to-back
     steps; power1_average is the SMU's own running average, sampled every 50 ms)."""
-    pw = sampler.mean_power_w() if sampler is not None else None
+    if sampler is None:
+        return {"energy_j_per_step": None, "energy_note": "board power is sampled under --full only"}
+    pw = sampler.mean_power_w()
     if pw is None:
         return {"energy_j_per_step": None, "energy_note": "no hwmon power samples on this box"}
     j = pw * ms_mean * 1e-3
@@ -341,6 +346,34 @@ def energy_fields(sampler, ms_mean, images_per_step, tflop_per_step):
             "energy_j_per_tflop": round(j / tflop_per_step, 4) if tflop_per_step else None,
             "energy_note": "mean hwmon board power over the timed region x ms_per_step_mean (rank 0's card); J per algorithmic TFLOP "
                            "of the step (20.31 TFLOP per image)"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array (torch tensor or numpy) as out_dir/<name>.npy, float64 kept, every other dtype as float32.
+    When the set is larger than `limit` bytes, each array over an equal share of it is replaced by a fixed sample of its
+    flattened elements (positions drawn once from numpy's default_rng(0) and sorted: the same positions for the same shape in
+    every run, so two builds compare element for element)."""
+    import numpy as np
+    outs = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().to(torch.float64 if a.dtype == torch.float64 else torch.float32).cpu().numpy()
+        a = np.asarray(a)
+        outs[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    if sum(a.nbytes for a in outs.values()) > limit:
+        share = limit // len(outs)
+        for name, a in outs.items():
+            if a.nbytes > share:
+                k = share // a.itemsize
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+                outs[name] = a.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in outs.items()}
 
 
 def run_protocol(args, rank, world, step, barrier, allreduce_max, sampler=None):
@@ -364,13 +397,13 @@ def run_protocol(args, rank, world, step, barrier, allreduce_max, sampler=None):
 
 def after_timing(args, rank, world, step, instrument, barrier):
     """What follows the timed region on EVERY rank, in the same order on every rank (a step contains the gradient
-    all-reduce, so a rank that skipped the instrumented replay would leave the others waiting in it): the per-kernel
-    replay, then -- rank 0, one GPU only -- the CPU baseline, then the closing barrier."""
+    all-reduce, so a rank that skipped the instrumented replay would leave the others waiting in it): under --full the
+    per-kernel replay, then -- rank 0, one GPU only -- the CPU baseline; then the closing barrier."""
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roof = instrument(step)                  # all ranks replay; only rank 0 keeps the report
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.model, args.cpu_budget, args.cpu_reference_faithful)
     barrier()
     return (roof if rank == 0 else None), cpu
@@ -461,15 +494,19 @@ def dry_run_collective(args, rank, world, json_fd):
 
     args.no_cpu_baseline = True
     tmax, _ = run_protocol(args, rank, world, step, barrier, pdist.control_max)
-    # the single-GPU-equivalent block of the GPU run: the same steps with the collective switched off, symmetric on all ranks
-    barrier()
-    local_only[0] = True
-    t0 = time.perf_counter()
-    for _ in range(3):
-        step(None)
-    solo_s = (time.perf_counter() - t0) / 3
-    local_only[0] = False
-    barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"allreduced_grad": last[0]})
+    solo_s = None
+    if args.full:
+        # the single-GPU-equivalent block of the GPU run: the same steps with the collective switched off, symmetric on all ranks
+        barrier()
+        local_only[0] = True
+        t0 = time.perf_counter()
+        for _ in range(3):
+            step(None)
+        solo_s = (time.perf_counter() - t0) / 3
+        local_only[0] = False
+        barrier()
     roof, _ = after_timing(args, rank, world, step, instrument, barrier)
     want = glob.view(world, B, 16).sum(1).mean(0).repeat(64)
     err = float((last[0] - want).abs().max())
@@ -484,7 +521,8 @@ def dry_run_collective(args, rank, world, json_fd):
                "rccl_ranks": 0, "collective": "gloo all_reduce on CPU tensors (dry run: no RCCL communicator exists here)",
                "control_plane": "gloo", "allreduce_ms": round(ar_s[0] * 1e3, 4), "allreduce_exposed_ms": None,
                "allreduce_bytes": int(flat.numel() * 4),
-               "single_gpu_equivalent": {"ms_per_step": round(solo_s * 1e3, 4), "what": "dry run: the step with the collective off"}}
+               "single_gpu_equivalent": ({"ms_per_step": round(solo_s * 1e3, 4), "what": "dry run: the step with the collective off"}
+                                         if solo_s is not None else None)}
         assert all(k in out for k in NRANK_KEYS)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
 
@@ -615,7 +653,21 @@ def main():
     ap.add_argument("--launch-timeout", type=float, default=0.0,
                     help="seconds the self-launched ranks (--gpus N without torch.distributed.run) may take in all; "
                          "default 900 + 2 s per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: board power / clock over the timed region (energy "
+                         "fields), the dead-row-elimination line, the instrumented per-kernel replay (roofline, MFMA probe, "
+                         "--breakdown, --dump-prof), the CPU-oracle baseline and, at N > 1 or --force-collective, the "
+                         "single-GPU-equivalent steps.  Without it a run sets up, warms up, times --steps steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy in "
+                         "float32, at most 64 MB in all: the step's four logged losses, the student's and the teacher's noise "
+                         "predictions, the adapter gradient and the adapter parameters after AdamW")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not (args.full or args.cpu_baseline_worker) and (args.breakdown or args.dump_prof or args.cpu_reference_faithful):
+        ap.error("--breakdown, --dump-prof and --cpu-reference-faithful report on the --full run: add --full")
     if args.cpu_baseline_worker:
         cpu_baseline_worker(args.model, args.cpu_budget, args.cpu_reference_faithful)
         return
@@ -841,14 +893,23 @@ def main():
 
     if args.single_stream:
         lib().pea_trainer_set_option(trainer._h, b"two_stream", 0)
-    pci = None
-    try:
-        pr = torch.cuda.get_device_properties(dev)
-        pci = f"{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
-    except Exception:
-        pass
-    sampler = GpuSampler(local_rank, pci) if rank == 0 else None
+    sampler = None
+    if args.full and rank == 0:
+        pci = None
+        try:
+            pr = torch.cuda.get_device_properties(dev)
+            pci = f"{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
+        except Exception:
+            pass
+        sampler = GpuSampler(local_rank, pci)
     dt, marks = run_protocol(args, rank, world, step, barrier, allreduce_max, sampler)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step holds after the last timed step: training_step's logged losses, the noise predictions,
+        # the (all-reduced) adapter gradient and the parameters optimizer_step left -- before any --full block steps again
+        dump_outputs(args.dump_outputs, dict(
+            {k: trainer.losses[i] for i, k in enumerate(trainer.LOG_KEYS)},
+            eps_student=trainer.export("eps_student"), eps_teacher=trainer.export("eps_teacher"),
+            adapter_grad=adapter.flat_grad, adapter_param=adapter.flat_param))
     ms_mean = dt / args.steps * 1e3
     ips = world * B * args.steps / dt
     # per-step device times: distance between the events recorded behind each step's AdamW on the compute stream
@@ -865,7 +926,7 @@ def main():
     # measured in this run -- the single-GPU number the N-rank value is weak scaling against (the driver's N = 1 line runs
     # BASELINE configs[1], batch 4: a different per-GPU workload)
     solo_ms = None
-    if world > 1 or args.force_collective:                  # (--force-collective: the same code path with one rank)
+    if args.full and (world > 1 or args.force_collective):  # (--force-collective: the same code path with one rank)
         barrier()
         # the local-only steps update each replica from its own shard: parameters AND both AdamW moments (and the step counter)
         # are put back afterwards, so every rank leaves this block in the replicated state it entered with
@@ -891,7 +952,7 @@ def main():
     # zero are not computed (PEATrainer.skip_dead_teacher_rows; identical losses and gradients, tests/test_dead_rows_gpu.py).
     # The headline above computes every teacher row, as the reference does.
     dre = None
-    if world == 1 and not args.no_dead_row_line and lib().pea_trainer_get_option(trainer._h, b"merge_state") == 1:
+    if args.full and world == 1 and not args.no_dead_row_line and lib().pea_trainer_get_option(trainer._h, b"merge_state") == 1:
         zh_host = batch["zh_or_not"].cpu()
         batch_dre = dict(batch, zh_or_not=zh_host)               # the dataloader's mask is a host tensor: no synchronising copy
         trainer.skip_dead_teacher_rows = True

@@ -11,7 +11,8 @@ N=${1:-3}
 B="--steps 16 --warmup 3 --no-cpu-baseline --no-roofline --no-dead-row-line"
 for i in $(seq $N); do
   for t in r05 r06; do
-    if [ $t = r05 ]; then d=.ab_r05; else d=.; fi
-    python $d/bench.py $B 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); g=d['gpu']; pw=g.get('power_w_mean') or g['power_w_median']; print('$t', d['ms_per_step'], 'ms', g['sclk_mhz_median'], 'MHz', pw, 'W', round(pw*d['ms_per_step_mean']*1e-3,2), 'J/step', d['value'], 'images/s')"
+    # this tree measures clock and power under --full only; the round-5 bench.py always did and has no such option
+    if [ $t = r05 ]; then d=.ab_r05; X=; else d=.; X=--full; fi
+    python $d/bench.py $B $X 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); g=d['gpu']; pw=g.get('power_w_mean') or g['power_w_median']; print('$t', d['ms_per_step'], 'ms', g['sclk_mhz_median'], 'MHz', pw, 'W', round(pw*d['ms_per_step_mean']*1e-3,2), 'J/step', d['value'], 'images/s')"
   done
 done

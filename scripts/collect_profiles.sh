@@ -1,14 +1,14 @@
 #!/bin/bash
-# Round profile collection on the GPU box (run through gpurun from the repo root): bench line with CPU baseline and
+# Round profile collection on an MI355X: bench line with CPU baseline and
 # per-family breakdown, rocprofv3 kernel stats of the same command, two PMC passes (FETCH_SIZE / WRITE_SIZE), the MFMA
-# utilisation pass, the per-launch profile and the GEMM / attention variant tables.  Everything lands in gpurun_out/ with the
-# round tag ($1, default r03); copy what should be judged into profiles/.
+# utilisation pass, the per-launch profile and the GEMM / attention variant tables.  Everything lands in the output folder
+# ($2, default profile_out/ in the repository) with the round tag ($1, default r06); copy what should be judged into profiles/.
 T=${1:-r06}
-R=${GRAFT_REPO_ROOT:-/root/repo}
-O=$R/gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd)
+O=${2:-$R/profile_out}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --breakdown --dump-prof $O/${T}_per_launch_profile.csv > $O/${T}_bench_line.json 2> $O/${T}_bench_breakdown.txt
+python3 $R/bench.py --full --breakdown --dump-prof $O/${T}_per_launch_profile.csv > $O/${T}_bench_line.json 2> $O/${T}_bench_breakdown.txt
 rocprofv3 --kernel-trace --stats -d /tmp/prof_stats -o r --output-format csv -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-roofline --no-dead-row-line > $O/${T}_rocprofv3_bench_line.json 2> /dev/null
 find /tmp/prof_stats -name "*kernel_stats.csv" -exec cp {} $O/${T}_rocprofv3_kernel_stats.csv \;
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/prof_fetch -o r --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-dead-row-line > /dev/null 2>&1

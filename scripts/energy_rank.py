@@ -20,7 +20,7 @@ SWITCHES = [  # (label, env that turns the NON-default state on)
 ]
 def run(env):
     e = dict(os.environ, **env)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-roofline", "--steps", "16", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-roofline", "--steps", "16", "--warmup", "3",
                         "--no-dead-row-line"], capture_output=True, text=True, env=e)
     d = json.loads(r.stdout.strip().splitlines()[-1])
     return d["ms_per_step"], d["gpu"]["power_w_mean"], d["energy_j_per_step"], d["gpu"]["sclk_mhz_median"]

@@ -136,7 +136,7 @@ def test_trainer_step_with_rccl_world1_matches_plain_step(gpu):
 def test_bench_subprocess_with_collective_and_side_stream_vae(gpu):
     """`bench.py --gpus 1 --force-collective --with-vae --model tiny` as a subprocess: the N > 1 code path on one GPU --
     RCCL communicator inside libpea_hip.so, all-reduce launched by training_step, a later batch's VAE encode enqueued
-    on the side stream between training_step and optimizer_step, the instrumented replay, one JSON line."""
+    on the side stream between training_step and optimizer_step, under --full the instrumented replay, one JSON line."""
     import json
     import subprocess
     import sys
@@ -144,7 +144,7 @@ def test_bench_subprocess_with_collective_and_side_stream_vae(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["MASTER_PORT"] = str(_free_port())
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-collective", "--with-vae",
-                        "--model", "tiny", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+                        "--model", "tiny", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -167,3 +167,40 @@ def test_bench_subprocess_with_collective_and_side_stream_vae(gpu):
     sp = out["roofline"]["sustained_peak"]
     assert sp["tflops"] > 500 and 800 < sp["in_kernel_clock_mhz"] <= 2500 and out["roofline"]["frac_of_sustained"] > 0
     assert isinstance(out["roofline"]["adapter_golden_rel_l2"]["measured_in_this_run"], list)
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(gpu, tmp_path):
+    """a plain `bench.py` run (no --full) times exactly --steps steps, carries the headline keys and nothing of --full, and
+    --dump-outputs writes the last timed step's results; two runs with the same arguments dump identical arrays (seeded
+    inputs and weights, no atomics on the path)"""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    names = ["adapter_grad", "adapter_param", "eps_student", "eps_teacher", "loss", "train_loss", "train_loss_features",
+             "train_loss_logits"]
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--model", "tiny", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["unit"] == "images/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+        assert out["roofline"] is None and out["cpu_baseline"] is None and out["dead_row_elimination"] is None
+        assert out["gpu"] is None and out["energy_j_per_step"] is None
+        assert sorted(f[:-4] for f in os.listdir(d)) == names
+        arr = {n: np.load(d / (n + ".npy")) for n in names}
+        assert all(a.dtype == np.float32 for a in arr.values())
+        assert abs(float(arr["loss"]) - out["config"]["loss"]) <= 1e-6 * max(1.0, abs(out["config"]["loss"]))
+        assert np.isfinite(arr["adapter_grad"]).all() and np.abs(arr["adapter_grad"]).max() > 0
+        assert arr["eps_student"].shape == arr["eps_teacher"].shape and arr["eps_student"].shape[0] == 4
+        dumps.append(arr)
+    for n in names:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

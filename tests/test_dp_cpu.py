@@ -130,8 +130,8 @@ def test_bench_launcher_spawns_two_ranks_over_gloo():
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--dry-run-collective"],
-                       capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--dry-run-collective",
+                        "--full"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -142,7 +142,7 @@ def test_bench_launcher_spawns_two_ranks_over_gloo():
     # and every rank was pinned to its own slice of the host's cores
     assert 100.0 < out["hbm_plan_gb_per_rank"] < 0.92 * out["hbm_capacity_gb"] and out["per_gpu_batch"] == 8
     assert out["cores_per_rank"] >= 1
-    # the whole control flow ran on BOTH ranks: warm-up + K timed steps + the instrumented replay (each step holds a
+    # the whole --full control flow ran on BOTH ranks: warm-up + K timed steps + the instrumented replay (each step holds a
     # collective, so a replay on rank 0 only would have left this subprocess hanging) + the closing barrier
     # (+ 3 local-only steps: the single-GPU-equivalent block between two barriers, as in the GPU run)
     assert out["steps_run_per_rank"] == 3 + 2 + 3 + 2 and out["replay"] == {"replayed_steps": 2}
@@ -155,6 +155,57 @@ def test_bench_launcher_spawns_two_ranks_over_gloo():
     assert out["control_plane"] == "gloo" and out["rccl_ranks"] == 0 and "gloo" in out["collective"]
     assert out["allreduce_ms"] > 0 and out["allreduce_bytes"] == 16 * 64 * 4
     assert out["single_gpu_equivalent"]["ms_per_step"] >= 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """without --full a run is set-up, W warm-up steps, EXACTLY K timed steps and the line: no replay, no single-GPU-equivalent
+    steps; --dump-outputs writes what the last timed step computed (here: the all-reduced buffer) on rank 0"""
+    import json
+    import subprocess
+
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                        "--dry-run-collective", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps_run_per_rank"] == 1 + 3 and out["replay"] is None and out["single_gpu_equivalent"] is None
+    assert sorted(os.listdir(d)) == ["allreduced_grad.npy"]
+    got = np.load(d / "allreduced_grad.npy")
+    g = torch.Generator().manual_seed(1234)
+    want = torch.randn(2 * 8, 16, generator=g).view(2, 8, 16).sum(1).mean(0).repeat(64).numpy()
+    assert got.dtype == np.float32 and got.shape == (1024,) and np.allclose(got, want, atol=1e-5)
+
+
+@pytest.mark.parametrize("opt", [["--breakdown"], ["--dump-prof", "x.csv"], ["--cpu-reference-faithful"]])
+def test_bench_full_only_options_need_full(opt):
+    """options that report on the --full run's replay or CPU baseline are a usage error without --full, not a silent no-op"""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run-collective"] + opt,
+                       capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 2 and "add --full" in r.stderr and not r.stdout.strip(), (r.returncode, r.stderr[-500:])
+
+
+def test_bench_dump_outputs_float32_and_capped_by_a_fixed_sample(tmp_path):
+    """dump_outputs(): float64 stays float64, other dtypes become float32; over the size limit every array above an equal
+    share is cut to the same seeded, sorted sample of its elements in every run"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {"big": torch.arange(1000, dtype=torch.float32), "f64": np.ones(10), "half": torch.ones(5, dtype=torch.bfloat16)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=1200)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, limit=1200)
+    assert shapes == {"big": [100], "f64": [10], "half": [5]}
+    big = np.load(tmp_path / "a" / "big.npy")
+    assert big.dtype == np.float32 and np.all(np.diff(big) > 0) and np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))
+    assert np.load(tmp_path / "a" / "f64.npy").dtype == np.float64 and np.load(tmp_path / "a" / "half.npy").dtype == np.float32
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= 1200   # 128-byte .npy headers
+    bench.dump_outputs(str(tmp_path / "c"), arrays)                 # under the default 64 MB limit nothing is sampled
+    assert np.array_equal(np.load(tmp_path / "c" / "big.npy"), np.arange(1000, dtype=np.float32))
 
 
 @pytest.mark.parametrize("kind,code", [("error", 4), ("timeout", 5)])
@@ -199,7 +250,7 @@ def test_bench_under_torch_distributed_run_as_the_driver_launches_it():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--dry-run-collective"], capture_output=True, text=True, timeout=600, env=env)
+                        "--dry-run-collective", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -210,16 +261,17 @@ def test_bench_under_torch_distributed_run_as_the_driver_launches_it():
 
 def test_bench_launcher_kills_hung_ranks_at_the_deadline(tmp_path):
     """a rank that never exits (stuck in a collective) must not block the parent forever: launch_ranks() stops its own
-    children at the deadline, names the ranks that were still alive and returns non-zero"""
+    children at the deadline, names the ranks that were still alive and returns non-zero.  Only the parent imports bench
+    (and with it torch): rank 0 must be done well before the deadline however slowly torch loads on the host."""
     import subprocess
     script = tmp_path / "hang.py"
     script.write_text(
-        "import sys, time\n"
-        f"sys.path.insert(0, {ROOT!r})\n"
-        "import bench, os\n"
+        "import os, sys, time\n"
         "if os.environ.get('RANK') is None:\n"
+        f"    sys.path.insert(0, {ROOT!r})\n"
+        "    import bench\n"
         "    bench.__file__ = __file__\n"
-        "    sys.exit(bench.launch_ranks(2, [], 3.0))\n"
+        "    sys.exit(bench.launch_ranks(2, [], 10.0))\n"
         "if os.environ['RANK'] == '1':\n"
         "    time.sleep(600)\n"
         "print('{}')\n")
