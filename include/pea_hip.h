@@ -109,6 +109,14 @@ int pea_op_upconv_subpixel_dgrad(const void* dy, const void* wt, void* dx, int B
                                  const void* res, void* stream);
 int pea_op_conv_in(const float* x_nchw, const float* w, const float* bias, void* y_nhwc, int B, int Cin, int H,
                    int W, int Cout, void* stream);
+/* conv_in of an inpainting UNet (in_channels = 2 C + 1) without the per-step torch.cat of tests/test_sdxl_zh_inpaint.py
+ * (`cat([cat([latents] * 2), mask, masked_image_latents], dim=1)`): input channel ci of image b is latents[b % latent_batch][ci]
+ * (ci < C), mask[b % cond_batch][0] (ci == C), masked_latents[b % cond_batch][ci - C - 1] (ci > C); all fp32 NCHW, 16-byte
+ * aligned, W % 4 == 0 (else PEA_E_SHAPE).  y: bf16 NHWC [B][H][W][Cout], equal bit for bit to pea_op_conv_in on the
+ * concatenated [B][2C+1][H][W] tensor. */
+int pea_op_conv_in_gather(const float* latents, const float* mask, const float* masked_latents, const float* w,
+                          const float* bias, void* y_nhwc, int B, int C, int latent_batch, int cond_batch, int H, int W,
+                          int Cout, void* stream);
 int pea_op_conv_out(const void* x_nhwc, const float* w_packed, const float* bias, float* y_nchw, int B, int Cin,
                     int H, int W, int Cout, void* stream);
 int pea_op_conv_out_dgrad(const float* dy_nchw, const float* w_packed, void* dx_nhwc, int B, int Cin, int H, int W,
@@ -175,6 +183,12 @@ int pea_op_cast_bf16_f32(const void* x, float* y, long long n, void* stream);
  *   guidance_rescale > 0 `rescale_noise_cfg` (:44-56, unbiased per-sample std); workspace from *_workspace_bytes(B).
  * dpm_update: one DPMSolverMultistepScheduler.step (:406; diffusers 0.23 [ext], dpmsolver++ midpoint) with host-side
  *   coefficients: x0 = (sample - sigma_s*eps)/alpha_s; sample <- c_s*sample + c_0*x0 + c_1*x0_prev; x0_prev <- x0. */
+/* inpainting inputs (tests/test_sdxl_zh_inpaint.py: VaeImageProcessor.preprocess, the masking of __call__, the nearest resize
+ * of prepare_mask_latents): image fp32 [N][3][H][W] and mask [N][1][H][W] in [0, 1], H and W (pixels) multiples of 8 ->
+ * init_image = 2 image - 1, masked_image = init_image * (mask < 0.5) (both [N][3][H][W]),
+ * latent_mask = (mask >= 0.5)[:, :, ::8, ::8] ([N][1][H/8][W/8]).  Exact in fp32. */
+int pea_op_inpaint_prepare(const float* image, const float* mask, int N, int H, int W, float* init_image, float* masked_image,
+                           float* latent_mask, void* stream);
 long long pea_op_cfg_combine_workspace_bytes(int B);
 int pea_op_cfg_combine(const float* eps2, float* out, int B, long long per, float guidance_scale, float guidance_rescale,
                        void* workspace, void* stream);
@@ -236,9 +250,12 @@ typedef struct pea_unet_config {
  * (train_sdxl_zh.py:138,151).  needs_grad=1 adds the reverse data-gradient tape (student);
  * own_weights=0 creates a context that must borrow weights via pea_unet_share_weights (the
  * reference loads teacher and student from the same checkpoint, train_sdxl_zh.py:138 vs :151).    */
-/* flags: PEA_UNET_GRAD (backward support) | PEA_UNET_RESIDUAL_INPUTS (ControlNet residual inputs, inference only) */
+/* flags: PEA_UNET_GRAD (backward support) | PEA_UNET_RESIDUAL_INPUTS (ControlNet residual inputs, inference only)
+ * | PEA_UNET_INPAINT_INPUTS (inpainting UNet, inference only: refused with PEA_UNET_GRAD and unless
+ * in_channels == 2 * out_channels + 1; enables pea_unet_set_inpaint_cond) */
 #define PEA_UNET_GRAD 1
 #define PEA_UNET_RESIDUAL_INPUTS 2
+#define PEA_UNET_INPAINT_INPUTS 4
 int pea_unet_create(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int own_weights,
                     void** out);
 /* Host-only planning pass of pea_unet_create (no device needed, nothing allocated): builds the op tape for the same
@@ -267,6 +284,15 @@ int pea_graph_plan_attention(int graph, const pea_unet_config* cfg, int B, int H
 int pea_unet_num_residuals(void* unet);
 int pea_unet_residual_info(void* unet, int i, int* C, int* H, int* W);
 int pea_unet_set_residuals(void* unet, int n, const void* const* ptrs, int dtype, float scale, void* stream);
+/* Inpainting condition (tests/test_sdxl_zh_inpaint.py: the per-step `cat([cat([latents] * 2), mask, masked_image_latents], dim=1)`):
+ * mask fp32 [cond_batch][1][H][W], masked_latents fp32 [cond_batch][out_channels][H][W], copied into the context once per
+ * generation.  From then on the `x` of pea_unet_forward is the latents alone, [latent_batch][out_channels][H][W], and conv_in
+ * reads channel groups of image b from latents[b % latent_batch], mask / masked_latents[b % cond_batch] (CFG: both B / 2).
+ * cond_batch and latent_batch must each divide B.  Needs PEA_UNET_INPAINT_INPUTS.  pea_unet_clear_inpaint_cond: `x` is the
+ * plain [B][in_channels][H][W] again. */
+int pea_unet_set_inpaint_cond(void* unet, const float* mask, const float* masked_latents, int cond_batch, int latent_batch,
+                              void* stream);
+int pea_unet_clear_inpaint_cond(void* unet);
 int pea_unet_destroy(void* unet);
 
 /* ControlNet (`self.controlnet(control_model_input, t, encoder_hidden_states=..., controlnet_cond=image,

@@ -53,6 +53,13 @@ def ssd1b_config() -> UNetConfig:
                       mid_block_type=None, name="ssd1b")
 
 
+def sdxl_inpaint_config() -> UNetConfig:
+    """diffusers/stable-diffusion-xl-1.0-inpainting-0.1 `unet/config.json` (the UNet of tests/test_sdxl_zh_inpaint.py) [ext,
+    recalled -- no network in the build image]: SDXL base with a 9-channel conv_in ([320, 9, 3, 3]: latents, mask, masked-image
+    latents).  `unet_config_from_diffusers()` reads the real file."""
+    return UNetConfig(in_channels=9, name="sdxl_inpaint")
+
+
 def ssd1b_uniform_config() -> UNetConfig:
     """round-1 stand-in (uniform depths 1/2/4 with a mid block); kept as an asymmetric shape case"""
     return UNetConfig(transformer_layers_per_block=(1, 2, 4), name="ssd1b_uniform")

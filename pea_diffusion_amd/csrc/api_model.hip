@@ -39,6 +39,13 @@ static int require_device(const char* what) {
   return PEA_OK;
 }
 
+// PEA_UNET_GRAD | PEA_UNET_RESIDUAL_INPUTS | PEA_UNET_INPAINT_INPUTS (Tape::build refuses the combinations it cannot serve)
+static void set_flags(Tape& u, int flags) {
+  u.needs_grad = (flags & PEA_UNET_GRAD) != 0;
+  u.residual_inputs = (flags & PEA_UNET_RESIDUAL_INPUTS) != 0;
+  u.inpaint_inputs = (flags & PEA_UNET_INPAINT_INPUTS) != 0;
+}
+
 extern "C" {
 
 int pea_unet_create(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int own_weights,
@@ -48,7 +55,7 @@ int pea_unet_create(const pea_unet_config* cfg, int B, int H, int W, int L, int 
   RCX(require_device("pea_unet_create"));
   Tape* u = new Tape();
   memcpy(&u->cfg, cfg, sizeof(PeaUnetCfg));
-  u->B = B; u->H = H; u->W = W; u->L = L; u->needs_grad = (flags & 1) != 0; u->residual_inputs = (flags & 2) != 0;
+  u->B = B; u->H = H; u->W = W; u->L = L; set_flags(*u, flags);
   u->owns_weights = own_weights != 0;
   return finish_create(u, out);
 }
@@ -57,7 +64,7 @@ int pea_unet_plan(const pea_unet_config* cfg, int B, int H, int W, int L, int fl
   NOTNULL(cfg, "pea_unet_plan");
   Tape u;
   memcpy(&u.cfg, cfg, sizeof(PeaUnetCfg));
-  u.B = B; u.H = H; u.W = W; u.L = L; u.needs_grad = (flags & 1) != 0; u.residual_inputs = (flags & 2) != 0;
+  u.B = B; u.H = H; u.W = W; u.L = L; set_flags(u, flags);
   u.plan_only = true;
   int rc = u.build();
   if (rc == PEA_OK) rc = u.alloc();
@@ -79,7 +86,7 @@ int pea_unet_plan_scratch(const pea_unet_config* cfg, int B, int H, int W, int L
   NOTNULL(scratch_bytes, "pea_unet_plan_scratch");
   Tape u;
   memcpy(&u.cfg, cfg, sizeof(PeaUnetCfg));
-  u.B = B; u.H = H; u.W = W; u.L = L; u.needs_grad = (flags & 1) != 0; u.residual_inputs = (flags & 2) != 0;
+  u.B = B; u.H = H; u.W = W; u.L = L; set_flags(u, flags);
   u.bwd_batch = bwd_batch;
   u.plan_only = true;
   int rc = u.build();
@@ -105,7 +112,7 @@ int pea_unet_plan_attention(const pea_unet_config* cfg, int B, int H, int W, int
   NOTNULL(cfg, "pea_unet_plan_attention");
   Tape u;
   memcpy(&u.cfg, cfg, sizeof(PeaUnetCfg));
-  u.B = B; u.H = H; u.W = W; u.L = L; u.needs_grad = (flags & 1) != 0; u.residual_inputs = (flags & 2) != 0;
+  u.B = B; u.H = H; u.W = W; u.L = L; set_flags(u, flags);
   u.plan_only = true;
   int rc = u.build();
   if (rc == PEA_OK) rc = u.alloc();
@@ -375,6 +382,18 @@ int pea_unet_set_residuals(void* h, int n, const void* const* ptrs, int dtype, f
     int rc = launch_residual_import(ptrs[i], dtype, t.d, u->B, t.cols, (long long)t.H * t.W, scale, (hipStream_t)stream);
     if (rc != PEA_OK) return rc;
   }
+  return PEA_OK;
+}
+int pea_unet_set_inpaint_cond(void* h, const float* mask, const float* masked_latents, int cond_batch, int latent_batch,
+                              void* stream) {
+  NOTNULL(h, "pea_unet_set_inpaint_cond");
+  return ((Tape*)h)->set_inpaint_cond(mask, masked_latents, cond_batch, latent_batch, (hipStream_t)stream);
+}
+int pea_unet_clear_inpaint_cond(void* h) {
+  NOTNULL(h, "pea_unet_clear_inpaint_cond");
+  Tape* u = (Tape*)h;
+  u->inp_set = false;
+  u->inp_cond_b = u->inp_lat_b = 0;
   return PEA_OK;
 }
 int pea_unet_num_weights(void* h) { return h ? (int)((Tape*)h)->slots.size() : 0; }

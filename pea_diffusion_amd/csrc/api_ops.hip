@@ -198,6 +198,13 @@ int pea_op_conv_in(const float* x, const float* w, const float* bias, void* y, i
                    int Cout, void* stream) {
   return launch_conv_in(x, w, bias, (bf16*)y, B, Cin, H, W, Cout, (hipStream_t)stream);
 }
+int pea_op_conv_in_gather(const float* latents, const float* mask, const float* masked_latents, const float* w,
+                          const float* bias, void* y, int B, int C, int latent_batch, int cond_batch, int H, int W, int Cout,
+                          void* stream) {
+  if (!w || !bias || !y) { pea_set_error("pea_op_conv_in_gather: null pointer"); return PEA_E_INVALID; }
+  return launch_conv_in_gather(latents, mask, masked_latents, w, bias, (bf16*)y, B, C, latent_batch, cond_batch, H, W, Cout,
+                               (hipStream_t)stream);
+}
 int pea_op_conv_out(const void* x, const float* w, const float* bias, float* y, int B, int Cin, int H, int W,
                     int Cout, void* stream) {
   return launch_conv_out((const bf16*)x, w, bias, y, B, Cin, H, W, Cout, (hipStream_t)stream);
@@ -340,6 +347,14 @@ int pea_op_dpm_update(float* sample, const float* eps, float* x0_prev, long long
                       float c_s, float c_0, float c_1, void* stream) {
   if (!sample || !eps || !x0_prev) { pea_set_error("pea_op_dpm_update: null pointer"); return PEA_E_INVALID; }
   return launch_dpm_update(sample, eps, x0_prev, n, alpha_s, sigma_s, c_s, c_0, c_1, (hipStream_t)stream);
+}
+int pea_op_inpaint_prepare(const float* image, const float* mask, int N, int H, int W, float* init_image, float* masked_image,
+                           float* latent_mask, void* stream) {
+  if (!image || !mask || !init_image || !masked_image || !latent_mask) {
+    pea_set_error("pea_op_inpaint_prepare: null pointer");
+    return PEA_E_INVALID;
+  }
+  return launch_inpaint_prepare(image, mask, N, H, W, init_image, masked_image, latent_mask, (hipStream_t)stream);
 }
 
 }  // extern "C"

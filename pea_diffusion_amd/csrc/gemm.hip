@@ -2076,11 +2076,19 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ 
 // FMA instead of 4).  It serves both 4-channel ends that produce a wide NHWC tensor from a narrow fp32 NCHW one:
 //   FLIP = false: conv_in                x [B][Cs][H][W], w [N][Cs][3][3]  ->  y [pix][N] (+ bias, optional SiLU)
 //   FLIP = true : dgrad of conv_out     dy [B][Cs][H][W], w [Cs][3][3][N] ->  dx [pix][N]   (taps mirrored)
-template <bool FLIP>
+// GATHER (with FLIP = false): the inpainting UNet's conv_in reads its Cs = 2 C + 1 input channels from three tensors instead of
+// their torch.cat (tests/test_sdxl_zh_inpaint.py: cat([cat([latents] * 2), mask, masked_image_latents], dim=1)); channel ci of
+// image b is latents[b % lat_b][ci] (ci < C), mask[b % cond_b][0] (ci == C), masked[b % cond_b][ci - C - 1] (ci > C).  Same
+// loop, same summation order: the result equals the plain kernel on the concatenated tensor bit for bit.
+struct ConvGatherSrc {
+  const float* lat; const float* mask; const float* masked;
+  int C, lat_b, cond_b;
+};
+template <bool FLIP, bool GATHER = false>
 __global__ __launch_bounds__(256) void conv_few4_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ bias, bf16* __restrict__ y, int B,
                                                         int Cs, int H, int W, int N, int groups_per_block, int ldy,
-                                                        int silu) {
+                                                        int silu, ConvGatherSrc gs) {
   extern __shared__ __attribute__((aligned(16))) char cfsm[];
   float* wl = (float*)cfsm;                       // [Cs*9][N]
   const int K = Cs * 9;
@@ -2112,12 +2120,22 @@ __global__ __launch_bounds__(256) void conv_few4_kernel(const float* __restrict_
     for (int p = 0; p < 4; ++p)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[p][j] = bs[j];
+    const long long HW = (long long)H * W;
+    const int bl = GATHER ? b % gs.lat_b : 0, bc = GATHER ? b % gs.cond_b : 0;
     for (int ci = 0; ci < Cs; ++ci)
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) {
         const int iy = FLIP ? yh + 1 - ky : yh + ky - 1;
         if ((unsigned)iy >= (unsigned)H) continue;
-        const float* row = x + (((long long)b * Cs + ci) * H + iy) * W;
+        const float* row;
+        if constexpr (GATHER) {
+          const float* plane = ci < gs.C    ? gs.lat + ((long long)bl * gs.C + ci) * HW
+                               : ci == gs.C ? gs.mask + (long long)bc * HW
+                                            : gs.masked + ((long long)bc * (Cs - gs.C - 1) + (ci - gs.C - 1)) * HW;
+          row = plane + (long long)iy * W;
+        } else {
+          row = x + (((long long)b * Cs + ci) * H + iy) * W;
+        }
         float v[6];                               // inputs x0-1 .. x0+4 (x0 % 4 == 0: the middle four are one aligned 16-byte load)
         const f32x4 mid = *(const f32x4*)(row + x0);
         v[0] = x0 > 0 ? row[x0 - 1] : 0.f;
@@ -2149,18 +2167,20 @@ __global__ __launch_bounds__(256) void conv_few4_kernel(const float* __restrict_
   }
 }
 
-// shared launcher of the two uses; returns false when the shape needs the one-pixel-per-thread kernels
-template <bool FLIP>
+// shared launcher of the uses; returns false when the shape needs the one-pixel-per-thread kernels (the gather form has none:
+// its caller refuses those shapes first)
+template <bool FLIP, bool GATHER = false>
 static bool launch_conv_few4(const float* x, const float* w, const float* bias, bf16* y, int B, int Cs, int H, int W, int N,
-                             int ldy, int silu, hipStream_t s, int* rc) {
+                             int ldy, int silu, hipStream_t s, int* rc, const ConvGatherSrc& gs = ConvGatherSrc{}) {
   static const bool off = getenv("PEA_CONV_ENDS_1PX") != nullptr;               // A/B switch
   const size_t lds = (size_t)Cs * 9 * N * 4;
-  if (off || W % 4 != 0 || N % 8 != 0 || N / 8 > 256 || lds > 160 * 1024 || (((unsigned long long)x) & 15) != 0) return false;
+  if (!GATHER && (off || W % 4 != 0 || N % 8 != 0 || N / 8 > 256 || lds > 160 * 1024 || (((unsigned long long)x) & 15) != 0))
+    return false;
   *rc = PEA_OK;
   if (lds > 64 * 1024) {
     static bool attr_set = false;
     if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)conv_few4_kernel<FLIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+      if (hipFuncSetAttribute((const void*)conv_few4_kernel<FLIP, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
         *rc = PEA_E_HIP;
         return true;
       }
@@ -2172,8 +2192,8 @@ static bool launch_conv_few4(const float* x, const float* w, const float* bias, 
   // two to three workgroups per CU each walk their share of the pixel groups (the weights are staged once per workgroup)
   long long per = cdivl(ngroups, 768);
   per = cdivl(per, ppb) * ppb;
-  hipLaunchKernelGGL(conv_few4_kernel<FLIP>, dim3((unsigned)cdivl(ngroups, per)), dim3(256), lds, s, x, w, bias, y, B, Cs, H, W, N,
-                     (int)per, ldy, silu);
+  hipLaunchKernelGGL((conv_few4_kernel<FLIP, GATHER>), dim3((unsigned)cdivl(ngroups, per)), dim3(256), lds, s, x, w, bias, y, B, Cs,
+                     H, W, N, (int)per, ldy, silu, gs);
   if (hipGetLastError() != hipSuccess) *rc = PEA_E_HIP;
   return true;
 }
@@ -2201,6 +2221,23 @@ int launch_conv_in(const float* x, const float* w, const float* bias, bf16* y, i
                      bias, y, B, Cin, H, W, Cout, per, ldy, silu);
   HIPCHK(hipGetLastError());
   return PEA_OK;
+}
+
+int launch_conv_in_gather(const float* lat, const float* mask, const float* masked, const float* w, const float* bias, bf16* y,
+                          int B, int C, int lat_b, int cond_b, int H, int W, int Cout, hipStream_t s, int ldy) {
+  if (ldy <= 0) ldy = Cout;
+  const int Cs = 2 * C + 1;
+  auto al16 = [](const float* p) { return p != nullptr && (((unsigned long long)p) & 15) == 0; };
+  SHAPECHK(C > 0 && lat_b > 0 && cond_b > 0 && B % lat_b == 0 && B % cond_b == 0,
+           "conv_in_gather: B=%d must be a multiple of latent_batch=%d and cond_batch=%d", B, lat_b, cond_b);
+  SHAPECHK(W % 4 == 0 && Cout % 8 == 0 && Cout / 8 <= 256 && (size_t)Cs * 9 * Cout * 4 <= 160 * 1024,
+           "conv_in_gather: W=%d must be a multiple of 4, Cout=%d of 8 (%d input channels)", W, Cout, Cs);
+  SHAPECHK(al16(lat) && al16(mask) && al16(masked), "conv_in_gather: latents / mask / masked latents must be 16-byte aligned");
+  int rc = PEA_OK;
+  launch_conv_few4<false, true>(nullptr, w, bias, y, B, Cs, H, W, Cout, ldy, 0, s, &rc,
+                                ConvGatherSrc{lat, mask, masked, C, lat_b, cond_b});
+  if (rc != PEA_OK) pea_set_error("conv_in_gather: launch failed");
+  return rc;
 }
 
 // conv_out: one wave per output pixel; lanes split the (tap, ci) reduction, 16-byte loads.

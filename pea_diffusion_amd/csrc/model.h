@@ -148,6 +148,14 @@ struct Tape {
   float* vae_h = nullptr;            // VAE: encoder output before quant_conv, fp32 [B][C2][h][w]
   bool residual_inputs = false;      // ControlNet: down_block_additional_residuals / mid_block_additional_residual
   std::vector<int> ext_res;          // their tensors, diffusers order (conv_in, down blocks..., then mid last)
+  // Inpainting (PEA_UNET_INPAINT_INPUTS, inference only): while a condition is set, conv_in gathers its 2 C + 1 input channels
+  // from x_in ([inp_lat_b][C][H][W]) and the mask / masked latents copied into inp_buf ([B][1][H][W] then [B][C][H][W], the
+  // first inp_cond_b samples of each in use) instead of reading a concatenated [B][2C+1][H][W] x_in
+  bool inpaint_inputs = false;
+  float* inp_buf = nullptr;
+  bool inp_set = false;
+  int inp_cond_b = 0, inp_lat_b = 0;
+  int set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s);
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

@@ -559,6 +559,12 @@ int Tape::build() {
                "unet: level %d has %d heads over %d channels; head_dim must be a multiple of 8 and <= 192", i,
                c.heads[i], c.block_out[i]);
   }
+  if (inpaint_inputs) {
+    SHAPECHK(graph == 0 && !needs_grad, "unet: PEA_UNET_INPAINT_INPUTS is an inference flag (not with PEA_UNET_GRAD)");
+    SHAPECHK(c.in_channels == 2 * c.out_channels + 1, "unet: PEA_UNET_INPAINT_INPUTS needs in_channels == 2 * out_channels + 1 "
+             "(latents, mask, masked latents), got in_channels=%d out_channels=%d", c.in_channels, c.out_channels);
+    SHAPECHK(W % 4 == 0, "unet: PEA_UNET_INPAINT_INPUTS needs a latent width that is a multiple of 4, got %d", W);
+  }
   SHAPECHK(c.cross_dim % 64 == 0, "unet: cross_attention_dim %% 64");
   SHAPECHK((H % (1 << (c.n_levels - 1))) == 0 && (W % (1 << (c.n_levels - 1))) == 0, "unet: latent %dx%d", H, W);
   Builder bd(*this);
@@ -1035,6 +1041,29 @@ Tape::~Tape() {
   if (rel_bias) (void)hipFree(rel_bias);
   if (rel_bucket) (void)hipFree(rel_bucket);
   if (cross_kvlen) (void)hipFree(cross_kvlen);
+  if (inp_buf) (void)hipFree(inp_buf);
+}
+
+int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s) {
+  if (!inpaint_inputs) {
+    pea_set_error("pea_unet_set_inpaint_cond: context created without PEA_UNET_INPAINT_INPUTS");
+    return PEA_E_STATE;
+  }
+  SHAPECHK(cond_b > 0 && lat_b > 0 && B % cond_b == 0 && B % lat_b == 0,
+           "pea_unet_set_inpaint_cond: cond_batch=%d and latent_batch=%d must each divide the UNet batch %d", cond_b, lat_b, B);
+  if (!mask || !masked) {
+    pea_set_error("pea_unet_set_inpaint_cond: null mask / masked latents");
+    return PEA_E_INVALID;
+  }
+  const int C = cfg.out_channels;
+  const size_t plane = (size_t)H * W;
+  if (!inp_buf) HIPCHK(hipMalloc((void**)&inp_buf, sizeof(float) * (size_t)B * (1 + C) * plane));
+  HIPCHK(hipMemcpyAsync(inp_buf, mask, sizeof(float) * cond_b * plane, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(inp_buf + (size_t)B * plane, masked, sizeof(float) * cond_b * C * plane, hipMemcpyDeviceToDevice, s));
+  inp_set = true;
+  inp_cond_b = cond_b;
+  inp_lat_b = lat_b;
+  return PEA_OK;
 }
 
 int Tape::load_weight(const char* name, const float* src, long long numel, hipStream_t s) {
@@ -1307,6 +1336,11 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
           SHAPECHK(cond_in != nullptr, "controlnet: no conditioning image set");
           RC(launch_conv_in(cond_in, slots[o.w].f32, slots[o.bias].f32, tn[o.out].d, B, 3, tn[o.out].H, tn[o.out].W,
                             o.p0, s, tn[o.out].cols, o.p3 == 2));
+          break;
+        }
+        if (inp_set) {                 // inpainting: latents from x_in, mask / masked latents from the context
+          RC(launch_conv_in_gather(x_in, inp_buf, inp_buf + (size_t)B * H * W, slots[o.w].f32, slots[o.bias].f32, tn[o.out].d,
+                                   B, cfg.out_channels, inp_lat_b, inp_cond_b, H, W, tn[o.out].cols, s));
           break;
         }
         RC(launch_conv_in(x_in, slots[o.w].f32, slots[o.bias].f32, tn[o.out].d, B, cfg.in_channels, H, W,
@@ -1782,6 +1816,11 @@ int Trainer::prepare() {
   Tape& Tt = *teacher;
   SHAPECHK(S.needs_grad, "trainer: student context needs gradient support");
   SHAPECHK(S.B == Tt.B && S.H == Tt.H && S.W == Tt.W, "trainer: student/teacher shapes differ");
+  // the noise, eps and KD-loss buffers below are sized by in_channels: a UNet whose input is wider than its output (the 9-channel
+  // inpainting UNet) has no KD step here
+  SHAPECHK(S.cfg.in_channels == S.cfg.out_channels && Tt.cfg.in_channels == Tt.cfg.out_channels,
+           "trainer: in_channels must equal out_channels (student %d -> %d, teacher %d -> %d); an inpainting UNet is not trained",
+           S.cfg.in_channels, S.cfg.out_channels, Tt.cfg.in_channels, Tt.cfg.out_channels);
   // feature taps are paired by hook name (d0.., m, u0..: cast_hook, train_sdxl_zh.py:79-84).  A student without a mid
   // block (SSD-1B-style, mid_block_type null) has no 'm' tap: that term leaves the feature loss (the reference's
   // cast_hook would fail on `unet.mid_block is None`; every other tap must exist on both sides).

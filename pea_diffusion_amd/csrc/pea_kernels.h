@@ -67,6 +67,11 @@ int launch_gemm(const GemmP& p, hipStream_t stream);
 // conv_in:  x NCHW fp32 [B][Cin][H][W] -> y NHWC bf16 [B][H][W][Cout];  w [Cout][Cin][3][3] fp32
 int launch_conv_in(const float* x, const float* w, const float* bias, bf16* y, int B, int Cin, int H, int W,
                    int Cout, hipStream_t s, int ldy = 0, int silu = 0);   // ldy: output row stride (0 = Cout)
+// the inpainting UNet's conv_in (Cin = 2 C + 1) reading its input channels from latents [lat_b][C][H][W], mask [cond_b][1][H][W]
+// and masked latents [cond_b][C][H][W] (image b uses sample b % lat_b / b % cond_b): the plain kernel on their torch.cat, bit for
+// bit.  W % 4 == 0 and 16-byte aligned sources, else PEA_E_SHAPE (there is no other form).
+int launch_conv_in_gather(const float* lat, const float* mask, const float* masked, const float* w, const float* bias, bf16* y,
+                          int B, int C, int lat_b, int cond_b, int H, int W, int Cout, hipStream_t s, int ldy = 0);
 // conv_out: x NHWC bf16 [B][H][W][Cin] -> y NCHW fp32 [B][Cout][H][W];  w [Cout][3][3][Cin] fp32
 int launch_conv_out(const bf16* x, const float* w, const float* bias, float* y, int B, int Cin, int H, int W,
                     int Cout, hipStream_t s);
@@ -238,6 +243,9 @@ int launch_cfg_combine(const float* eps2, float* out, int B, long long per, floa
 int launch_dpm_update(float* sample, const float* eps, float* x0_prev, long long n, float alpha_s, float sigma_s,
                       float c_s, float c_0, float c_1, hipStream_t s);
 int launch_residual_import(const void* src, int dtype, bf16* dst, int B, int C, long long HW, float scale, hipStream_t s);
+// inpainting: init image, masked image and the latent-resolution mask from image [N][3][H][W] / mask [N][1][H][W] (H, W % 8 == 0)
+int launch_inpaint_prepare(const float* image, const float* mask, int N, int H, int W, float* init, float* masked,
+                           float* lmask, hipStream_t s);
 int launch_softmax_rows(bf16* s, long long rows, int cols, int ld, float scale, hipStream_t st);   // in place
 int launch_vae_posterior(const float* h, const float* wq, const float* bq, const float* noise, float* moments,
                          float* latents, int B, int C2, long long HW, float scaling, hipStream_t s);

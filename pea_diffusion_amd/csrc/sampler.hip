@@ -100,6 +100,39 @@ int launch_dpm_update(float* sample, const float* eps, float* x0_prev, long long
   return PEA_OK;
 }
 
+// Inpainting inputs (tests/test_sdxl_zh_inpaint.py: VaeImageProcessor.preprocess of image and mask, the masking of __call__ and
+// the nearest-mode resize of prepare_mask_latents): per pixel of image [N][3][H][W] and mask [N][1][H][W], both in [0, 1],
+//   init = 2 image - 1,  masked = init * (mask < 0.5),  latent_mask[n][0][y/8][x/8] = (mask >= 0.5) at y % 8 == x % 8 == 0.
+// The multiply by the 0 / 1 keep factor is literal (a negative init gives -0, as in torch); every result is exact in fp32.
+__global__ void inpaint_prepare_kernel(const float* __restrict__ image, const float* __restrict__ mask,
+                                       float* __restrict__ init, float* __restrict__ masked, float* __restrict__ lmask,
+                                       int H, int W, long long n) {
+  const long long HW = (long long)H * W;
+  SM_LOOP(i, n) {                                 // i = pixel of the mask, n = N * H * W
+    const long long b = i / HW, p = i - b * HW;
+    const float m = mask[i];
+    const float keep = m >= 0.5f ? 0.f : 1.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const long long j = (b * 3 + c) * HW + p;
+      const float v = 2.f * image[j] - 1.f;
+      init[j] = v;
+      masked[j] = v * keep;
+    }
+    const int y = (int)(p / W), x = (int)(p - (long long)y * W);
+    if (((y | x) & 7) == 0) lmask[(b * (H / 8) + y / 8) * (W / 8) + x / 8] = 1.f - keep;
+  }
+}
+int launch_inpaint_prepare(const float* image, const float* mask, int N, int H, int W, float* init, float* masked,
+                           float* lmask, hipStream_t s) {
+  SHAPECHK(N > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "inpaint_prepare: N=%d, image %dx%d must be multiples of 8", N,
+           H, W);
+  const long long n = (long long)N * H * W;
+  hipLaunchKernelGGL(inpaint_prepare_kernel, dim3(sm_grid(n)), dim3(256), 0, s, image, mask, init, masked, lmask, H, W, n);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
 // ControlNet residual hand-over: [B][C][HW] (fp32 or bf16) -> [B][HW][C] bf16, scaled
 template <typename T>
 __global__ void nchw_to_nhwc_scaled_kernel(const T* __restrict__ x, bf16* __restrict__ y, int C, long long HW,

@@ -157,6 +157,29 @@ def conv_in(x_nchw, w, bias):
     return y
 
 
+def conv_in_gather(latents, mask, masked_latents, w, bias, B):
+    """conv_in of an inpainting UNet over `cat([latents[b % lb], mask[b % cb], masked_latents[b % cb]], dim=1)` for b < B,
+    without materialising the concatenation (bf16 NHWC out)."""
+    lb, C, H, W = latents.shape
+    cb = mask.shape[0]
+    Cout = w.shape[0]
+    y = torch.empty(B, H, W, Cout, device=latents.device, dtype=BF)
+    check(lib().pea_op_conv_in_gather(ptr(latents), ptr(mask), ptr(masked_latents), ptr(w.contiguous()), ptr(bias), ptr(y), B,
+                                      C, lb, cb, H, W, Cout, stream_ptr()))
+    return y
+
+
+def inpaint_prepare(image, mask):
+    """image [N,3,H,W], mask [N,1,H,W] fp32 in [0, 1] -> (init_image = 2 image - 1, masked_image = init_image * (mask < 0.5),
+    latent_mask = (mask >= 0.5)[:, :, ::8, ::8])"""
+    N, _, H, W = image.shape
+    init = torch.empty_like(image)
+    masked = torch.empty_like(image)
+    lmask = torch.empty(N, 1, H // 8, W // 8, device=image.device, dtype=torch.float32)
+    check(lib().pea_op_inpaint_prepare(ptr(image), ptr(mask), N, H, W, ptr(init), ptr(masked), ptr(lmask), stream_ptr()))
+    return init, masked, lmask
+
+
 def pack_conv_out(w):
     Co, Ci = w.shape[:2]
     out = torch.empty(Co, 3, 3, Ci, device=w.device, dtype=torch.float32)

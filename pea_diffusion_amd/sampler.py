@@ -54,6 +54,19 @@ class DPMSolverMultistep:
         self._x0_prev = None
         return self.timesteps
 
+    def set_begin_index(self, begin_index: int = 0):
+        """Start the solver at position `begin_index` of the schedule (img2img / inpainting with strength < 1 run
+        `timesteps[t_start:]`): as diffusers 0.23 derives the step index from the timestep's position in the FULL schedule, the
+        coefficients are those of that position, the first step is first order (no earlier data prediction exists) and the
+        lower_order_final test keeps using the full length."""
+        if self.timesteps is None:
+            raise ValueError("set_begin_index: call set_timesteps first")
+        if not 0 <= begin_index < len(self.timesteps):
+            raise ValueError(f"set_begin_index: {begin_index} outside the {len(self.timesteps)}-step schedule")
+        self._i = int(begin_index)
+        self._lower = 0
+        self._x0_prev = None
+
     def scale_model_input(self, sample, timestep=None):
         return sample
 
@@ -79,20 +92,27 @@ class DPMSolverMultistep:
     def step(self, model_output, timestep, sample, return_dict: bool = False, **kwargs):
         """`latents = scheduler.step(noise_pred, t, latents, return_dict=False)[0]` (:406).  fp32 CUDA tensors;
         `sample` is updated IN PLACE and returned."""
-        i, n = self._i, len(self.timesteps)
-        final = (i == n - 1) and self.lower_order_final and n < 15
-        order = 1 if (self.solver_order == 1 or self._lower < 1 or final) else 2
-        a_s, s_s, c_s, c0, c1 = self._coefficients(i, order)
+        order, (a_s, s_s, c_s, c0, c1) = self.next_step_plan()
         if sample.dtype != torch.float32 or not sample.is_contiguous():
             sample = sample.float().contiguous()
         eps = model_output.float().contiguous()
         if self._x0_prev is None:
             self._x0_prev = torch.zeros_like(sample)
         ops.dpm_update_(sample, eps, self._x0_prev, a_s, s_s, c_s, c0, c1)
+        self._advance()
+        return (sample,)
+
+    def next_step_plan(self):
+        """host side of the next `step`: (order, (alpha_s, sigma_s, c_s, c_0, c_1))"""
+        i, n = self._i, len(self.timesteps)
+        final = (i == n - 1) and self.lower_order_final and n < 15
+        order = 1 if (self.solver_order == 1 or self._lower < 1 or final) else 2
+        return order, self._coefficients(i, order)
+
+    def _advance(self):
         if self._lower < self.solver_order:
             self._lower += 1
         self._i += 1
-        return (sample,)
 
 
 def denoise(unet, scheduler, latents, prompt_embeds, added_cond_kwargs, num_inference_steps: int = 30,

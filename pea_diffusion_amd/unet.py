@@ -44,7 +44,7 @@ class _Config:
 class HipUNet:
     def __init__(self, cfg, batch: int, height: Optional[int] = None, width: Optional[int] = None, ctx_len: int = 77,
                  needs_grad: bool = False, share_weights_from: Optional["HipUNet"] = None,
-                 residual_inputs: bool = False):
+                 residual_inputs: bool = False, inpaint_inputs: bool = False):
         if not torch.cuda.is_available():
             raise PeaError("HipUNet needs a MI355X (no CPU fallback)")
         self.cfg = cfg
@@ -57,7 +57,9 @@ class HipUNet:
         self._h = ctypes.c_void_p()
         c = _cfg.to_c(cfg)
         self.residual_inputs = residual_inputs
-        flags = (1 if needs_grad else 0) | (2 if residual_inputs else 0)   # PEA_UNET_GRAD | PEA_UNET_RESIDUAL_INPUTS
+        self.inpaint_inputs = inpaint_inputs
+        # PEA_UNET_GRAD | PEA_UNET_RESIDUAL_INPUTS | PEA_UNET_INPAINT_INPUTS
+        flags = (1 if needs_grad else 0) | (2 if residual_inputs else 0) | (4 if inpaint_inputs else 0)
         check(lib().pea_unet_create(ctypes.byref(c), self.B, self.H, self.W, self.L, flags,
                                     int(share_weights_from is None), ctypes.byref(self._h)))
         if share_weights_from is not None:
@@ -142,9 +144,8 @@ class HipUNet:
             self.set_additional_residuals(down_block_additional_residuals, mid_block_additional_residual)
         elif self.residual_inputs and self._residuals_set:
             self.set_additional_residuals(None, None)        # a call without the kwargs is a plain UNet call
-        B = sample.shape[0]
-        if tuple(sample.shape) != (self.B, self.in_channels, self.H, self.W):
-            raise PeaError(f"HipUNet built for {(self.B, self.in_channels, self.H, self.W)}, got {tuple(sample.shape)}")
+        B = self.B
+        self._route_inpaint(sample)
         x = sample.detach().to(self.device, torch.float32).contiguous()
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])
         t = t.to(self.device, torch.float32).reshape(-1).expand(B).contiguous()
@@ -172,6 +173,54 @@ class HipUNet:
                     fn(blk, (), out)
         out = eps.to(sample.dtype) if sample.dtype in (torch.float16, torch.bfloat16) else eps
         return (out,)
+
+    # ---------------------------------------------------------------- inpainting condition
+    _inp = None            # (mask, masked_latents) fp32 on the device, as last handed to the context
+    _inp_lat_b = 0
+    _inp_live = False      # the context currently gathers (a plain 9-channel call clears it until the next latents-only call)
+
+    def set_inpaint_cond(self, mask, masked_latents, latent_batch: Optional[int] = None):
+        """The per-generation inputs of the inpainting UNet (tests/test_sdxl_zh_inpaint.py: `mask`, `masked_image_latents` of
+        the per-step `torch.cat([latent_model_input, mask, masked_image_latents], dim=1)`), copied into the context once.
+        mask [cb,1,H,W], masked_latents [cb,C,H,W] (C = out_channels), cb dividing the UNet batch (with CFG: the images
+        WITHOUT the CFG doubling, cb = B/2).  Afterwards `__call__` also takes the latents alone, [lb,C,H,W] with lb dividing B
+        (default latent_batch: cb); image b reads latents[b % lb] and mask / masked_latents[b % cb]."""
+        if not self.inpaint_inputs:
+            raise PeaError("HipUNet was created without inpaint_inputs=True")
+        C = self.cfg.out_channels
+        cb = mask.shape[0]
+        if tuple(mask.shape) != (cb, 1, self.H, self.W) or tuple(masked_latents.shape) != (cb, C, self.H, self.W):
+            raise PeaError(f"set_inpaint_cond: mask {tuple(mask.shape)} / masked_latents {tuple(masked_latents.shape)}, expected "
+                           f"[cb,1,{self.H},{self.W}] / [cb,{C},{self.H},{self.W}]")
+        m = mask.detach().to(self.device, torch.float32).contiguous()
+        ml = masked_latents.detach().to(self.device, torch.float32).contiguous()
+        lb = cb if latent_batch is None else int(latent_batch)
+        check(lib().pea_unet_set_inpaint_cond(self._h, ptr(m), ptr(ml), cb, lb, stream_ptr()))
+        self._inp, self._inp_lat_b, self._inp_live = (m, ml), lb, True
+
+    def clear_inpaint_cond(self):
+        """back to the plain call: `sample` is the full [B, in_channels, H, W] input again"""
+        check(lib().pea_unet_clear_inpaint_cond(self._h))
+        self._inp, self._inp_lat_b, self._inp_live = None, 0, False
+
+    def _route_inpaint(self, sample):
+        shp = tuple(sample.shape)
+        if shp == (self.B, self.in_channels, self.H, self.W):
+            if self._inp_live:              # the reference's own concatenated input: the plain conv_in reads it
+                check(lib().pea_unet_clear_inpaint_cond(self._h))
+                self._inp_live = False
+            return
+        C = self.cfg.out_channels
+        if self._inp is not None and len(shp) == 4 and shp[1:] == (C, self.H, self.W) and shp[0] > 0 and self.B % shp[0] == 0:
+            if not self._inp_live or shp[0] != self._inp_lat_b:
+                check(lib().pea_unet_set_inpaint_cond(self._h, ptr(self._inp[0]), ptr(self._inp[1]), self._inp[0].shape[0],
+                                                      shp[0], stream_ptr()))
+                self._inp_lat_b, self._inp_live = shp[0], True
+            return
+        want = f"{(self.B, self.in_channels, self.H, self.W)}"
+        if self._inp is not None:
+            want += f" or latents [lb, {C}, {self.H}, {self.W}] with lb dividing {self.B}"
+        raise PeaError(f"HipUNet built for {want}, got {shp}")
 
     # ---------------------------------------------------------------- ControlNet residual inputs
     _residuals_set = False
