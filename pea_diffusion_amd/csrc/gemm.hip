@@ -1965,7 +1965,11 @@ int launch_gemm(const GemmP& p_in, hipStream_t stream) {
   }
   int v = pick_variant(p);                                  // (reads p.epi_fast)
   if (p.qscale_cols && (v == 34 || v == 35)) v = 28;        // the staged / deferred forms carry no column scale
+  if (p.geglu_y && (v == 34 || v == 35)) v = 28;            // ... and no GEGLU epilogue (34 drops the stash, 35 the output)
   if ((p.gbwd_pre || p.ln_stats) && (v == 39 || v == 40)) v = 28;     // (those epilogues have no 192-row instantiation)
+  // the batched-load epilogue reads one row-vector entry per wave tile: a 48-row wave tile of the 192-row forms would straddle
+  // two samples (the shape rule never picks them with a row vector; a pinned variant must not either)
+  if (p.rowvec && p.epi_fast && (v == 39 || v == 40)) v = 28;
   if (p.ksplit > 1) {
     SHAPECHK(p.out_f32 && !p.accum_f32 && !p.bias && !p.res && !p.rowvec && !p.preact && p.act == 0 && p.mode == 0,
              "gemm: split-K writes plain fp32 partials");

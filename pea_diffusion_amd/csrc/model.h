@@ -186,6 +186,7 @@ struct Tape {
   float* eps_out = nullptr; const float* deps_in = nullptr;
 
   int build();
+  int check_attn_bwd_tokens() const;     // a training context: every attention's query count a multiple of 4
   int build_vae_encoder();
   int build_vae_decoder();
   int release_acts();

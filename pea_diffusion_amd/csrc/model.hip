@@ -542,6 +542,17 @@ int Tape::build_text_t5() {
   return PEA_OK;
 }
 
+// the attention backward takes query counts in multiples of 4 (attention.hip, launch_attention_bwd): a training context whose
+// token grid breaks that (an SD1.5 mid block at a 56 x 104 latent: 7 x 13 = 91 tokens) is refused when it is created, not in its
+// first backward pass
+int Tape::check_attn_bwd_tokens() const {
+  if (needs_grad)
+    for (const Op& o : ops)
+      SHAPECHK(o.kind != OP_ATTN || o.p1 % 4 == 0, "unet: latent %dx%d gives an attention over %d tokens; a training context "
+               "(PEA_UNET_GRAD) needs multiples of 4", H, W, o.p1);
+  return PEA_OK;
+}
+
 int Tape::build() {
   if (graph == 4) return build_text();
   if (graph == 1) return build_vae_encoder();
@@ -695,7 +706,7 @@ int Tape::build() {
       cn_out.push_back(bd.linear(skips[k], "controlnet_down_blocks." + std::to_string(k), tn[skips[k]].cols, true));
     cn_out.push_back(bd.linear(x, "controlnet_mid_block", tn[x].cols, true));
     SHAPECHK(bd.kv_off == kvall_total, "controlnet: stacked K|V projection layout mismatch (%d vs %d)", bd.kv_off, kvall_total);
-    return PEA_OK;
+    return check_attn_bwd_tokens();
   }
   for (int i = 0; i < n; ++i) {
     const std::string p = "up_blocks." + std::to_string(i);
@@ -732,7 +743,7 @@ int Tape::build() {
       else slots[o.w].need_wt = true;
     }
   }
-  return PEA_OK;
+  return check_attn_bwd_tokens();
 }
 
 // Every flash-attention op takes its Q from the projection right in front of it (fused Q|K|V: columns [0, C); to_q: the

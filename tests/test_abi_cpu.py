@@ -132,3 +132,16 @@ def test_clean_build_from_sources_only(tmp_path):
     nm = subprocess.run(["nm", "-D", "--defined-only", str(so)], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in nm.splitlines() if " T pea_" in ln}
     assert exported == set(protos), (sorted(exported - set(protos)), sorted(set(protos) - exported))
+
+
+def test_training_plan_refuses_attention_token_counts_the_backward_cannot_take():
+    """an SD1.5 UNet at a 56 x 104 latent has a 7 x 13 = 91-token mid block: the attention backward needs query counts in
+    multiples of 4, so a training plan (PEA_UNET_GRAD) is refused when it is built; the inference plan is not"""
+    import ctypes as C
+    from pea_diffusion_amd import config as pc
+    L = _lib.lib()
+    c = pc.to_c(pc.sd15_config())
+    assert L.pea_unet_plan(C.byref(c), 1, 56, 104, 77, 1, None, None, None, None, None, None) != 0
+    assert b"91 tokens" in L.pea_last_error()
+    assert L.pea_unet_plan(C.byref(c), 1, 56, 104, 77, 0, None, None, None, None, None, None) == 0
+    assert L.pea_unet_plan(C.byref(c), 1, 64, 104, 77, 1, None, None, None, None, None, None) == 0      # 8 x 13 = 104 tokens
