@@ -200,15 +200,12 @@ __device__ __forceinline__ bf16x8 read_row_frag(const char* tile, int row, int s
 // XCD-aware workgroup order.  Workgroups are handed to the 8 XCDs round-robin in dispatch order (x fastest), so the
 // query blocks of one head -- which all stream that head's K and V (or Q and dO) -- would land on 8 different L2s and
 // every XCD would see every head: a working set of all heads per 4-MB L2.  Remapped, XCD x runs a contiguous range of
-// (batch, head, block) triples, i.e. whole heads, and a head's operands are read into one L2 once.  `env
-// PEA_ATTN_NO_XCD=1` restores the dispatch order (A/B).
-__device__ __forceinline__ void attn_block_coords(int remap, int& bx, int& by, int& bz) {
+// (batch, head, block) triples, i.e. whole heads, and a head's operands are read into one L2 once.
+__device__ __forceinline__ void attn_block_coords(int& bx, int& by, int& bz) {
   const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z;
   unsigned lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  if (remap) {
-    const unsigned total = gx * gy * gz, q = total >> 3, r = total & 7, xcd = lin & 7, j = lin >> 3;
-    lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const unsigned total = gx * gy * gz, q = total >> 3, r = total & 7, xcd = lin & 7, j = lin >> 3;
+  lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
   bx = (int)(lin % gx);
   const unsigned t = lin / gx;
   by = (int)(t % gy);
@@ -596,7 +593,7 @@ template <int MODE, bool USE_TR, int ND, bool TXT = false>
 __global__ __launch_bounds__(256, (ND == 1 ? (MODE == 0 ? 3 : 2) : 1)) void attn_q_kernel(const AttnP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int blk_x, head, b;
-  attn_block_coords(p.xcd_remap, blk_x, head, b);
+  attn_block_coords(blk_x, head, b);
   attn_q_body<MODE, USE_TR, ND, TXT, true>(p, smem, blk_x, head, b);
 }
 
@@ -885,7 +882,7 @@ template <bool USE_TR, int ND>
 __global__ __launch_bounds__(256, (ND == 1 ? 2 : 1)) void attn_dkv_kernel(const AttnP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int blk_x, head, b;
-  attn_block_coords(p.xcd_remap, blk_x, head, b);
+  attn_block_coords(blk_x, head, b);
   attn_dkv_body<USE_TR, ND>(p, smem, blk_x, head, b);
 }
 
@@ -897,32 +894,11 @@ __global__ __launch_bounds__(256, (ND == 1 ? 2 : 1)) void attn_dkv_kernel(const 
 // then dK/dV blocks -- and XCD x owns a contiguous range of heads, so a head's Q / K / V / dO are read into one L2 once
 // for both roles.  delta comes from attn_delta_kernel (the roles run concurrently, so the dQ role cannot hand it over).
 template <bool USE_TR, int ND>
-__global__ __launch_bounds__(256, (ND == 1 ? 2 : 1)) void attn_bwd_fused_kernel(const AttnP p, int n_dq, int n_dkv, int heavy_first) {
+__global__ __launch_bounds__(256, (ND == 1 ? 2 : 1)) void attn_bwd_fused_kernel(const AttnP p, int n_dq, int n_dkv) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const unsigned total = gridDim.x;
-  unsigned lin = blockIdx.x;
+  const unsigned total = gridDim.x, q = total >> 3, r = total & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+  const unsigned lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
   const int per_head = n_dq + n_dkv;
-  if (p.xcd_remap) {
-    const unsigned q = total >> 3, r = total & 7, xcd = lin & 7, j = lin >> 3;
-    const unsigned start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, cnt = q + (xcd < r ? 1u : 0u);
-    if (heavy_first && r == 0 && cnt % per_head == 0) {
-      // Dispatch order inside an XCD's range of heads: ALL dK/dV workgroups (4 products per tile) of those heads first, then
-      // all dQ workgroups (3 products).  The grid is 2.5 rounds of the chip's slots (1024 tokens, B * H = 80); the hardware
-      // hands a free slot the next workgroup in order, so what is left for the last, partly filled round should be the
-      // lighter role, and the heavy ones must not start last.  A head's operands then meet one L2 twice instead of once:
-      // the loops do not care (profiles/EXPERIMENTS.md: cache-resident operands are worth 2 % to self-attention).
-      const unsigned nh = cnt / per_head, first_bh = start / per_head;
-      unsigned bh_l, rem;
-      if (j < nh * (unsigned)n_dkv) { bh_l = j / n_dkv; rem = j - bh_l * n_dkv; }
-      else { const unsigned j2 = j - nh * n_dkv; bh_l = j2 / n_dq; rem = n_dkv + (j2 - bh_l * n_dq); }
-      const int bh = (int)(first_bh + bh_l);
-      const int b = bh / p.H, head = bh - b * p.H;
-      if ((int)rem < n_dkv) attn_dkv_body<USE_TR, ND>(p, smem, (int)rem, head, b);
-      else attn_q_body<1, USE_TR, ND, false, false>(p, smem, (int)rem - n_dkv, head, b);
-      return;
-    }
-    lin = start + j;
-  }
   const int bh = (int)(lin / per_head), rem = (int)(lin - (unsigned)bh * per_head);
   const int b = bh / p.H, head = bh - b * p.H;
   if (rem < n_dkv) attn_dkv_body<USE_TR, ND>(p, smem, rem, head, b);          // heavier role (4 products) first
@@ -952,7 +928,7 @@ __global__ __launch_bounds__(256, 3) void xattn_fwd_kernel(const AttnP p, int up
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
   int split, head, b;
-  attn_block_coords(p.xcd_remap, split, head, b);
+  attn_block_coords(split, head, b);
   const int nu = (p.Sq + 127) >> 7;
   const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
   const float c = p.q_prescaled ? 1.f : p.scale * LOG2E;         // prescaled Q: the scores are in the log2 domain already
@@ -1109,7 +1085,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd_kernel(const AttnP p, int up
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
   int split, head, b;
-  attn_block_coords(p.xcd_remap, split, head, b);
+  attn_block_coords(split, head, b);
   const int nu = (p.Sq + 127) >> 7;
   const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
   const float c = p.q_prescaled ? 1.f : p.scale * LOG2E;         // prescaled Q: the scores are in the log2 domain already
@@ -1388,30 +1364,6 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd_kernel(const AttnP p, int up
     }
 }
 
-// one 16-byte element of the split reduce (head_dim 64): out[b][key][h*64+d] (+)= sum_split part[split][b][h][key][{dK,dV}][d],
-// splits added in order.  Shared by attn_dkv_reduce_kernel's nd == 1 case in spirit; used by xattn_bwd2_kernel's prologue.
-__device__ __forceinline__ void dkv_reduce_elem64(const float* __restrict__ part, bf16* dK, bf16* dV, int lddk, int lddv, int ns,
-                                                  int B, int H, int Skv, int accum, long long idx) {
-  const int d4 = (int)(idx & 15) * 4;
-  long long r = idx >> 4;
-  const int which = (int)(r & 1); r >>= 1;
-  const int key = (int)(r % Skv); r /= Skv;
-  const int head = (int)(r % H);
-  const int b = (int)(r / H);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int s = 0; s < ns; ++s) {
-    const f32x4 v = *(const f32x4*)(part + ((((long long)s * B + b) * H + head) * Skv + key) * 128 + which * 64 + d4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] += v[j];
-  }
-  bf16* dst = which ? dV + ((long long)b * Skv + key) * lddv + head * 64 + d4 : dK + ((long long)b * Skv + key) * lddk + head * 64 + d4;
-  bf16x4 o;
-  if (accum) o = *(const bf16x4*)dst;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = (bf16)(acc[j] + (accum ? (float)o[j] : 0.f));
-  *(bf16x4*)dst = o;
-}
-
 // ============================================================================= cross-attention backward, v2 (round 6)
 // The one-pass kernel above runs BOTH orientations on every wave, one after the other, off a single-buffered 128-query
 // stage: per unit a wave walks LDS read -> MFMA -> exp -> MFMA chains of 100 MFMAs with nothing beside it on its SIMD but
@@ -1440,7 +1392,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd2_kernel(const AttnP p, int u
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
   int split, head, b;
-  attn_block_coords(p.xcd_remap, split, head, b);
+  attn_block_coords(split, head, b);
   const int nu = (p.Sq + 63) >> 6;
   const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
   const float c = PRE ? 1.f : p.scale * LOG2E;
@@ -1485,16 +1437,6 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd2_kernel(const AttnP p, int u
   if (u_begin < u_end) {
     stage_unit(u_begin, 0);
     fetch_o(u_begin);
-  }
-  // Deferred split reduce of ANOTHER launch (the previous cross-attention layer of the backward pass: AttnP::red_*): every
-  // workgroup adds up its share of those partials while its own K / V / first unit are in flight -- 70 launches of a 5.8 us
-  // kernel per step otherwise.  Nothing here depends on this workgroup's own data.
-  if (p.red_part) {
-    const long long total = (long long)p.red_B * p.red_H * p.red_Skv * 32;
-    const long long nthr = (long long)gridDim.x * gridDim.y * gridDim.z * 256;
-    const long long first = ((long long)blockIdx.x + gridDim.x * (blockIdx.y + (long long)gridDim.y * blockIdx.z)) * 256 + tid;
-    for (long long idx = first; idx < total; idx += nthr)
-      dkv_reduce_elem64(p.red_part, p.red_dK, p.red_dV, p.red_lddk, p.red_lddv, p.red_nsplit, p.red_B, p.red_H, p.red_Skv, p.red_accum, idx);
   }
   const bool key_wave = wave >= 2;
   // the shared head of a unit, executed by every wave: wait for the unit's tiles, start the next unit's, form delta.
@@ -1824,7 +1766,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd3_kernel(const AttnP p, int u
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
   int split, head, b;
-  attn_block_coords(p.xcd_remap, split, head, b);
+  attn_block_coords(split, head, b);
   const int nu = (p.Sq + 63) >> 6;
   const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
   const float c = PRE ? 1.f : p.scale * LOG2E;
@@ -1868,13 +1810,6 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd3_kernel(const AttnP p, int u
   if (u_begin < u_end) {
     stage_unit(u_begin, 0);
     fetch_o(u_begin);
-  }
-  if (p.red_part) {                                               // deferred split reduce of another launch (see xattn_bwd2_kernel)
-    const long long total = (long long)p.red_B * p.red_H * p.red_Skv * 32;
-    const long long nthr = (long long)gridDim.x * gridDim.y * gridDim.z * 256;
-    const long long first = ((long long)blockIdx.x + gridDim.x * (blockIdx.y + (long long)gridDim.y * blockIdx.z)) * 256 + tid;
-    for (long long idx = first; idx < total; idx += nthr)
-      dkv_reduce_elem64(p.red_part, p.red_dK, p.red_dV, p.red_lddk, p.red_lddv, p.red_nsplit, p.red_B, p.red_H, p.red_Skv, p.red_accum, idx);
   }
   // wave roles
   const bool key_wave = wave >= 1 && wave <= KB;
@@ -2222,10 +2157,10 @@ __global__ void attn_dkv_reduce_kernel(const AttnP p) {
 // v2 of the one-pass cross-attention backward (xattn_bwd2_kernel: 64-query units, specialised waves): 33 .. 96 keys
 // which one-pass kernel: 0 = round 3 (xattn_bwd_kernel) for every key count; 2 = xattn_bwd2_kernel where it applies (33..96
 // keys); 1 / 3 (default) = the newest that applies: xattn_bwd3_kernel for 33..80 keys, xattn_bwd2_kernel for 81..96.
-// PEA_XATTN_BWD_V1=1 / PEA_XATTN_BWD_VER=n in the environment, pea_debug_set_xattn_bwd_v2(n) at run time (A/B, parity tests).
-static int g_xattn_v2 = getenv("PEA_XATTN_BWD_V1") ? 0 : (getenv("PEA_XATTN_BWD_VER") ? atoi(getenv("PEA_XATTN_BWD_VER")) : 3);
+// PEA_XATTN_BWD_VER=n in the environment, pea_debug_set_xattn_bwd_v2(n) at run time (A/B, parity tests).
+static int g_xattn_v2 = getenv("PEA_XATTN_BWD_VER") ? atoi(getenv("PEA_XATTN_BWD_VER")) : 3;
 extern "C" void pea_debug_set_xattn_bwd_v2(int v) { g_xattn_v2 = v; }
-static bool xattn_v2_keys(int Skv) { return g_xattn_v2 && Skv > 32 && Skv <= 96; }     // v2 OR v3: 64-query units, deferrable reduce
+static bool xattn_v2_keys(int Skv) { return g_xattn_v2 && Skv > 32 && Skv <= 96; }     // v2 OR v3: 64-query units
 static bool xattn_v3_keys(int Skv) { return g_xattn_v2 != 0 && g_xattn_v2 != 2 && Skv > 32 && Skv <= 80; }
 int attention_bwd_nsplit(int B, int H, int Sq, int Skv) {
   if (Skv > 128 || Sq < 512) return 1;
@@ -2255,7 +2190,6 @@ size_t attention_bwd_scratch_bytes(int B, int H, int Sq, int Skv, int nd) {
 static int g_attn_use_tr = 1;
 static int g_attn_xattn = getenv("PEA_XATTN_OFF") ? 0 : 1;               // PEA_XATTN_OFF=1: cross-attention on the general kernels (A/B)
 extern "C" void pea_debug_set_attn_xattn(int v) { g_attn_xattn = v; }
-static int g_attn_xcd = getenv("PEA_ATTN_NO_XCD") ? 0 : 1;
 extern "C" void pea_debug_set_attn_tr(int v) { g_attn_use_tr = v; }
 
 static int attn_check(const AttnP& p) {
@@ -2329,32 +2263,6 @@ static bool attn_use_xattn(const AttnP& p) {
   return g_attn_xattn && g_attn_use_tr && p.nd == 1 && p.Skv <= 128 && p.dQ && p.dK && p.dV && (p.nsplit <= 1 || p.dkv_part);
 }
 extern "C" void pea_debug_set_attn_fused_bwd(int v) { g_attn_fused_bwd = v; }
-// PEA_XATTN_DEFER=1: a cross-attention layer's split reduce rides in the next such launch's prologue instead of its own 5.8 us
-// launch.  Built for VERDICT r05 item 1a ("a single batched launch per step instead of 70"), parity-green (per-layer K / V
-// gradient checks of the full model), and worth NOTHING in the step: 99.86 / 99.76 ms with it, 99.78 / 99.87 without, alternating
-// processes on one box (profiles/r06_ab_defer_reduce.log) -- the prologue's extra loads cost what the launches did.  Off.
-static int g_xattn_defer = getenv("PEA_XATTN_DEFER") ? atoi(getenv("PEA_XATTN_DEFER")) : 0;
-int attention_bwd_defers(const AttnP& p0) {
-  AttnP p = p0;
-  if (p.nd == 0) p.nd = 1;
-  p.nsplit = p.dkv_part ? attention_bwd_nsplit(p.B, p.H, p.Sq, p.Skv) : 1;
-  return (g_xattn_defer && attn_use_xattn(p) && xattn_v2_keys(p.Skv) && p.nsplit > 1) ? 1 : 0;
-}
-void attention_set_deferred(AttnP& cur, const AttnP& pend) {
-  cur.red_part = pend.dkv_part; cur.red_dK = pend.dK; cur.red_dV = pend.dV; cur.red_lddk = pend.lddk; cur.red_lddv = pend.lddv;
-  cur.red_nsplit = attention_bwd_nsplit(pend.B, pend.H, pend.Sq, pend.Skv);
-  cur.red_B = pend.B; cur.red_H = pend.H; cur.red_Skv = pend.Skv; cur.red_accum = pend.accum_dkv;
-}
-int launch_attention_dkv_reduce(const AttnP& pend, hipStream_t s) {
-  AttnP p = pend;
-  if (p.nd == 0) p.nd = 1;
-  p.nsplit = attention_bwd_nsplit(p.B, p.H, p.Sq, p.Skv);
-  SHAPECHK(p.dkv_part && p.nsplit > 1 && p.dK && p.dV, "attention: nothing to reduce");
-  const long long total = (long long)p.B * p.H * p.Skv * 2 * 16 * p.nd;
-  hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, p);
-  HIPCHK(hipGetLastError());
-  return PEA_OK;
-}
 template <int ND>
 static int attn_bwd_nd(const AttnP& p, hipStream_t s) {
   int rc = attn_set_lds_attr<ND>();
@@ -2415,7 +2323,7 @@ static int attn_bwd_nd(const AttnP& p, hipStream_t s) {
       else if (kb == 3) hipLaunchKernelGGL(xattn_bwd_kernel<3>, grid, dim3(256), lds, s, p, upw);
       else hipLaunchKernelGGL(xattn_bwd_kernel<4>, grid, dim3(256), lds, s, p, upw);
       }
-      if (p.nsplit > 1 && !(p.defer_reduce && xattn_v2_keys(p.Skv))) {
+      if (p.nsplit > 1) {
         const long long total = (long long)p.B * p.H * p.Skv * 2 * 16;
         hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, p);
       }
@@ -2432,9 +2340,8 @@ static int attn_bwd_nd(const AttnP& p, hipStream_t s) {
     }
     const int n_dq = cdiv(p.Sq, 128) * ND, n_dkv = cdiv(p.Skv, 128) * (p.nsplit > 1 ? p.nsplit : 1) * ND;
     const dim3 grid((unsigned)((n_dq + n_dkv) * p.H * p.B));
-    static const int heavy_first = getenv("PEA_ATTN_BWD_HEAVY_FIRST") ? atoi(getenv("PEA_ATTN_BWD_HEAVY_FIRST")) : 0;
-    if (g_attn_use_tr) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, ND>), grid, dim3(256), lds, s, p, n_dq, n_dkv, heavy_first);
-    else hipLaunchKernelGGL((attn_bwd_fused_kernel<false, ND>), grid, dim3(256), lds, s, p, n_dq, n_dkv, heavy_first);
+    if (g_attn_use_tr) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, ND>), grid, dim3(256), lds, s, p, n_dq, n_dkv);
+    else hipLaunchKernelGGL((attn_bwd_fused_kernel<false, ND>), grid, dim3(256), lds, s, p, n_dq, n_dkv);
     if (p.nsplit > 1) {
       const long long total = (long long)p.B * p.H * p.Skv * 2 * 16 * ND;
       hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, p);
@@ -2458,7 +2365,6 @@ static int attn_bwd_nd(const AttnP& p, hipStream_t s) {
 
 int launch_attention_fwd(const AttnP& p0, hipStream_t s) {
   AttnP p = p0;
-  p.xcd_remap = g_attn_xcd;
   if (p.nd == 0) p.nd = 1;
   int rc = attn_check(p);
   if (rc) return rc;
@@ -2474,7 +2380,6 @@ int launch_attention_fwd(const AttnP& p0, hipStream_t s) {
 
 int launch_attention_bwd(const AttnP& p0, hipStream_t s) {
   AttnP p = p0;
-  p.xcd_remap = g_attn_xcd;
   if (p.nd == 0) p.nd = 1;
   p.nsplit = p.dkv_part ? attention_bwd_nsplit(p.B, p.H, p.Sq, p.Skv) : 1;
   int rc = attn_check(p);

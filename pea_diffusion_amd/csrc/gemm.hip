@@ -1893,8 +1893,7 @@ static int pick_variant(const GemmP& p) {
   static const int ksw_mink = getenv("PEA_GEMM_KSW_MINK") ? atoi(getenv("PEA_GEMM_KSW_MINK")) : 0;
   if (t128 <= cus && ksw_mink > 0 && p.K >= ksw_mink && (p.K / BK) % 2 == 0 && p.epi_fast && p.ksplit <= 1 && p.mode == 0 && t128 > cus * 5 / 8) return 41;
   if (t128 <= cus) return lean ? 35 : 25;            // at most one 128x160 tile per CU
-  static const bool one_round_persistent = getenv("PEA_GEMM_ONE_ROUND_PERSISTENT") != nullptr;   // experiment: 27 instead of 24
-  if (t256 <= cus) return t256 > cus * 3 / 4 ? (one_round_persistent ? 27 : 24) : (lean ? 35 : 28);
+  if (t256 <= cus) return t256 > cus * 3 / 4 ? 24 : (lean ? 35 : 28);
   // more than one 256x160 tile per CU: the large tile wins (less L2 -> LDS traffic per flop) unless its tile count
   // leaves the last round of CUs mostly idle (e.g. 384 tiles = 1.5 rounds), then the 128x160 form balances better
   const int rounds = cdiv(t256, cus);
@@ -2176,9 +2175,8 @@ __global__ __launch_bounds__(256) void conv_few4_kernel(const float* __restrict_
 template <bool FLIP, bool GATHER = false>
 static bool launch_conv_few4(const float* x, const float* w, const float* bias, bf16* y, int B, int Cs, int H, int W, int N,
                              int ldy, int silu, hipStream_t s, int* rc, const ConvGatherSrc& gs = ConvGatherSrc{}) {
-  static const bool off = getenv("PEA_CONV_ENDS_1PX") != nullptr;               // A/B switch
   const size_t lds = (size_t)Cs * 9 * N * 4;
-  if (!GATHER && (off || W % 4 != 0 || N % 8 != 0 || N / 8 > 256 || lds > 160 * 1024 || (((unsigned long long)x) & 15) != 0))
+  if (!GATHER && (W % 4 != 0 || N % 8 != 0 || N / 8 > 256 || lds > 160 * 1024 || (((unsigned long long)x) & 15) != 0))
     return false;
   *rc = PEA_OK;
   if (lds > 64 * 1024) {
@@ -2381,9 +2379,8 @@ int launch_conv_out(const bf16* x, const float* w, const float* bias, float* y, 
                     int Cout, hipStream_t s) {
   SHAPECHK(Cout <= 8 && Cin % 8 == 0, "conv_out: Cout<=8, Cin%%8");
   const long long pix = (long long)B * H * W;
-  static const bool direct = getenv("PEA_CONV_OUT_DIRECT") != nullptr;        // A/B switch: the one-wave-per-pixel form
   const size_t lds = (size_t)9 * (Cin / 32) * 4 * 8 * ((Cout + 3) / 4) * 16;       // [9 Cin / 32][4][8 or 16 rows][16 bytes]
-  if (!direct && Cin % 32 == 0 && lds <= 160 * 1024) {
+  if (Cin % 32 == 0 && lds <= 160 * 1024) {
     if (lds > 64 * 1024) {
       static bool attr_set = false;
       if (!attr_set) {

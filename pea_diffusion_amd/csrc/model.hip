@@ -752,11 +752,9 @@ int Tape::build() {
 // per-score multiply (AttnP::q_prescaled).  The attention backward returns the gradient w.r.t. the unscaled q, so the
 // projection's data-gradient GEMM is unchanged.
 void Tape::tag_q_prescale() {
-  static const bool off = getenv("PEA_ATTN_NO_PRESCALE") != nullptr;          // A/B switch
   n_attn = n_attn_pre = 0;
   for (const Op& a : ops)
     if (a.kind == OP_ATTN) { ++n_attn; n_attn_pre += a.pre ? 1 : 0; }
-  if (off) return;
   // An attention op that fails a condition below keeps a plain Q: the kernels then round Q * scale * log2(e) to bf16 themselves
   // (attention.hip: scale_frag), one more rounding than the tagged path.  Nothing on the product's graphs may take that path
   // silently: the census (pea_tape_attention_census) is asserted by the tests for every graph, and a miss is logged once here.
@@ -907,8 +905,7 @@ void Tape::scratch_needs(size_t need[8]) {
   need[2] = delta_elems * 4 * 2;               // two row constants per (b, h, q): -delta, -lse*log2e
   need[3] = ups_elems * 2;
   need[4] = geglu_elems * 2;
-  need[5] = 2 * part_bytes;                    // two halves: a launch writes one while the previous layer's half is being reduced
-  part_half_elems = part_bytes / sizeof(float);
+  need[5] = part_bytes;
   if (t_ehs >= 0 && kvall_total > 0) {
     const int ksteps = kvall_total / 64;
     kv_nsplit = std::max(1, std::min(32, ksteps / 128));
@@ -1194,12 +1191,10 @@ int Tape::all_loaded(std::string* missing) const {
 // ============================================================================ forward
 static void fill_gemm(GemmP& p) { memset(&p, 0, sizeof(p)); p.alpha = 1.f; p.rows_per_batch = 1; }
 // What a fused-GEGLU projection (op.p3 == 3 with a stash tensor op.c) leaves in its stash: 1 = (gelu(gate), h * gelu'(gate)),
-// the two factors of the backward (GemmP::stash_grad); 0 = the raw (h, gate) pre-activation -- the tanh form (no backward
-// exists for it) and the PEA_GEGLU_UNFUSED experiment, whose separate GEGLU kernel reads the pre-activation.
-static bool g_geglu_unfused = getenv("PEA_GEGLU_UNFUSED") != nullptr;
-static bool g_geglu_stash_raw = getenv("PEA_GEGLU_STASH_RAW") != nullptr;      // A/B switch: stash (h, gate) as in round 2
+// the two factors of the backward (GemmP::stash_grad); 0 = the raw (h, gate) pre-activation.  Form 0 is left to the tanh
+// form (the T5 encoder's gated-gelu), which keeps no stash and has no backward: every stash a backward pass reads is form 1.
 static int geglu_stash_form(const Op& o) {
-  return (o.p3 == 3 && o.c >= 0 && o.p1 == 0 && !g_geglu_stash_raw && !(g_geglu_unfused && o.fold < 0)) ? 1 : 0;
+  return (o.p3 == 3 && o.c >= 0 && o.p1 == 0) ? 1 : 0;
 }
 
 int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype, const void* text, int text_dtype,
@@ -1247,13 +1242,12 @@ int Tape::gemm(GemmP& p, hipStream_t s) {
       const size_t i = q->pos++;
       if (i >= q->w.size() || q->w[i].first != (const void*)p.W) { q->ready = false; q->w.clear(); wseq_cur = nullptr; }
       else {
-        static const int dist = getenv("PEA_GEMM_PF_DIST") ? atoi(getenv("PEA_GEMM_PF_DIST")) : 1;     // experiment: launches ahead
-        if (i + dist < q->w.size()) {
+        if (i + 1 < q->w.size()) {
           // armed only for a target inside the weights owner's arena: a recorded pointer that no longer is (a weights owner
           // re-created behind a borrower's back) would send the DMA waves' touch loads to unmapped memory -- a GPU page fault
           const Tape* ow = weights_owner ? weights_owner : this;
-          const char* t = (const char*)q->w[i + dist].first;
-          const long long nb = q->w[i + dist].second;
+          const char* t = (const char*)q->w[i + 1].first;
+          const long long nb = q->w[i + 1].second;
           if (ow->warena && t >= ow->warena && t + nb <= ow->warena + ow->wbytes) { p.pf_ptr = t; p.pf_bytes = nb; }
           else { q->ready = false; q->w.clear(); wseq_cur = nullptr; }
         }
@@ -1295,12 +1289,6 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
           const LnFold& f = folds[o.fold];
           p.A = tn[ops[f.ln_op].a].d; p.W = f.wf; p.ldw = f.K; p.bias = f.t;
           p.ln_stats = ops[f.ln_op].aux; p.ln_s = f.s;
-        }
-        if (o.p3 == 3 && g_geglu_unfused && o.c >= 0 && o.fold < 0) {      // A/B switch for experiments
-          p.geglu_y = nullptr; p.stash_rows = 0;
-          RC(gemm(p, s));
-          RC(launch_geglu_fwd_il(tn[o.c].d, out.d, out.rows, out.cols, s));
-          break;
         }
         RC(gemm(p, s));
         break;
@@ -1436,7 +1424,6 @@ static int g_geglu_bwd_fused = getenv("PEA_GEGLU_BWD_UNFUSED") ? 0 : 1;
 extern "C" void pea_debug_set_geglu_bwd_fused(int v) { g_geglu_bwd_fused = v; }
 void Tape::begin_backward() {
   for (Tn& t : tn) { t.gw = false; t.gpend = nullptr; }
-  pend_red_valid = false;                      // (a pass that failed half-way leaves nothing behind)
 }
 
 int Tape::backward(const float* deps, hipStream_t s) {
@@ -1501,7 +1488,6 @@ int Tape::backward(const float* deps, hipStream_t s) {
       case OP_LINEAR: {
         Tn& a = tn[o.a];
         if (a.rg && o.p3 == 2) {          // stacked K|V projection: M = B*L rows, K = sum(2C) -> split-K + ordered reduce
-          RC(flush_pending_reduce(s));     // the last cross-attention layer's dK / dV partials -> out.g
           FusedMat& f = fused[o.fused];
           GemmP p; fill_gemm(p);
           p.A = out.g; p.lda = out.cols; p.M = (int)rb(out); p.K = out.cols; p.N = a.cols;
@@ -1515,8 +1501,8 @@ int Tape::backward(const float* deps, hipStream_t s) {
         }
         if (a.rg && o.p3 == 3) {          // fused GEGLU: d(pre-activation) into scratch, then the dgrad GEMM over K = 8C
           Tn& hg = tn[o.c];
-          SHAPECHK(o.stash_form >= 0, "unet: GEGLU op %d has no stash from a forward pass", oi);
-          if (dpre_of != o.out) RC(launch_geglu_bwd_il(hg.d, out.g, geglu_tmp, rb(out), out.cols, s, o.stash_form));
+          SHAPECHK(o.stash_form == 1, "unet: GEGLU op %d has no stash from a forward pass", oi);
+          if (dpre_of != o.out) RC(launch_geglu_bwd_il(hg.d, out.g, geglu_tmp, rb(out), out.cols, s));
           dpre_of = -1;
           WSlot& w = slots[o.w];
           GemmP p; fill_gemm(p);
@@ -1641,19 +1627,7 @@ int Tape::backward(const float* deps, hipStream_t s) {
         SHAPECHK(!q.gw && !q.gpend && !k.gpend && (!k.gw || o.b == t_kvall), "unet: attention operand gradient written twice");
         if (q.rg) { p.dQ = q.g + o.acol; p.lddq = q.cols; }
         if (k.rg) { p.dK = k.g + o.bcol; p.lddk = k.cols; p.dV = v.g + o.ccol; p.lddv = v.cols; }
-        if (o.b == t_kvall && attention_bwd_defers(p)) {
-          // cross-attention layer on the specialised-wave kernel: its split reduce rides in the NEXT such launch's prologue
-          // (d(K|V) of t_kvall is read by nothing before the stacked K|V dgrad GEMM at the end of the pass)
-          p.dkv_part = attn_part + (part_toggle ? part_half_elems : 0);
-          p.defer_reduce = 1;
-          if (pend_red_valid) attention_set_deferred(p, pend_red);
-          RC(launch_attention_bwd(p, s));
-          pend_red = p;
-          pend_red_valid = true;
-          part_toggle ^= 1;
-        } else {
-          RC(launch_attention_bwd(p, s));
-        }
+        RC(launch_attention_bwd(p, s));
         if (q.rg) q.gw = true;
         if (k.rg) { k.gw = true; v.gw = true; }
         break;
@@ -1671,17 +1645,10 @@ int Tape::backward(const float* deps, hipStream_t s) {
         break;
     }
   }
-  RC(flush_pending_reduce(s));                 // (a graph without the stacked projection op)
   for (Tn& t : tn)
     if (t.rg) RC(materialize(t));              // graph inputs that only ever received a passed-on gradient
   wscope.ok = true;
   return PEA_OK;
-}
-
-int Tape::flush_pending_reduce(hipStream_t s) {
-  if (!pend_red_valid) return PEA_OK;
-  pend_red_valid = false;
-  return launch_attention_dkv_reduce(pend_red, s);
 }
 
 // ============================================================================ adapter

@@ -1,5 +1,4 @@
-"""Timing of the 4-channel ends of the UNet (conv_in, conv_out, conv_out dgrad) at the bench shape [8][128][128][320].
-PEA_CONV_OUT_DIRECT=1 in the environment selects the one-wave-per-pixel conv_out for an A/B."""
+"""Timing of the 4-channel ends of the UNet (conv_in, conv_out, conv_out dgrad) at the bench shape [8][128][128][320]."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

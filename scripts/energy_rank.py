@@ -9,12 +9,9 @@ SWITCHES = [  # (label, env that turns the NON-default state on)
     ("next-op weight prefetch OFF", {"PEA_GEMM_PF": "0"}),
     ("upsampler convs folded (not sub-pixel)", {"PEA_UPCONV_SUBPIXEL": "0"}),
     ("intra-workgroup K split, K >= 1280 (variant 41)", {"PEA_GEMM_KSW_MINK": "1280"}),
-    ("one-round launches on the persistent kernel", {"PEA_GEMM_ONE_ROUND_PERSISTENT": "1"}),
     ("LayerNorm folded into the consuming GEMM", {"PEA_LN_FOLD": "1"}),
     ("cross-attention backward: round-3 kernel", {"PEA_XATTN_BWD_VER": "0"}),
     ("cross-attention backward: v2 (7 products)", {"PEA_XATTN_BWD_VER": "2"}),
-    ("cross-attention split reduce deferred", {"PEA_XATTN_DEFER": "1"}),
-    ("attention backward: heavy role first", {"PEA_ATTN_BWD_HEAVY_FIRST": "1"}),
     ("GroupNorm three-kernel path everywhere", {"PEA_GN_UNFUSED": "1"}),
     ("kernel arguments in host memory", {"HIP_FORCE_DEV_KERNARG": "0"}),
 ]
