@@ -194,6 +194,20 @@ int pea_op_cfg_combine(const float* eps2, float* out, int B, long long per, floa
                        void* workspace, void* stream);
 int pea_op_dpm_update(float* sample, const float* eps, float* x0_prev, long long n, float alpha_s, float sigma_s,
                       float c_s, float c_0, float c_1, void* stream);
+/* lcm_update: one LCMScheduler.step (tests/test_sdxl_zh_lcm.py:178; diffusers 0.23 [ext]: epsilon prediction, boundary scalings
+ *   c_skip / c_out) with host-side coefficients folded to four scalars, fp32 [n], in place:
+ *     denoised = kx * sample + ke * eps          kx = c_out / sqrt(a_t) + c_skip,  ke = -c_out * sqrt(1 - a_t) / sqrt(a_t)
+ *     sample  <- c_prev * denoised + c_noise * noise        c_prev = sqrt(a_prev), c_noise = sqrt(1 - a_prev)
+ *   noise NULL (the last step, c_prev = 1): the noise term is dropped.  denoised (diffusers' second output) may be NULL. */
+int pea_op_lcm_update(float* sample, const float* eps, const float* noise, float* denoised, long long n, float kx, float ke,
+                      float c_prev, float c_noise, void* stream);
+
+/* LoRA weight composition (`pipe.load_lora_weights(...)`, `pipe.fuse_lora()`, tests/test_sdxl_zh_lcm.py:181-182):
+ *   out[m][k] = acc[m][k] + scale * sum_r up[m][r] * down[r][k]      all fp32 device, torch layouts, 1 <= rank <= 256
+ * M = output features (Cout), Kf = numel / M (Cin, or Cin * 9 for a [Co][Ci][3][3] weight with `down [r][Ci][3][3]`).
+ * acc may be out (several adapters accumulate into one matrix).  fp32 products in a fixed order: bit-reproducible. */
+int pea_op_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank, float scale,
+                        void* stream);
 
 /* Fused KD loss of train_sdxl_zh.py:399-441 (SD1.5: train_sd_zh.py:217-276, nan_guard=1).
  * taps_s/taps_t/dtaps: HOST arrays of ntaps device pointers (bf16, elementwise-paired layouts);
@@ -367,6 +381,15 @@ int pea_unet_num_weights(void* unet);
 int pea_unet_weight_info(void* unet, int i, char* name, int name_len, long long* numel, int* kind, int* d0, int* d1);
 /* src: DEVICE fp32, torch layout, `numel` elements; converted to the internal bf16 layouts      */
 int pea_unet_load_weight(void* unet, const char* name, const float* src, long long numel, void* stream);
+/* pea_unet_load_weight of `base + sum_i scales[i] * ups[i] . downs[i]` (LoRA fusion): composed in fp32 (pea_op_lora_compose)
+ * BEFORE the conversion to the internal bf16 layouts, so the fused weight is rounded once.  base: DEVICE fp32 [numel], torch
+ * layout; downs / ups / ranks / scales: HOST arrays of n_adapters entries; downs[i]: DEVICE fp32 [ranks[i]][numel / d0],
+ * ups[i]: DEVICE fp32 [d0][ranks[i]] (d0 of pea_unet_weight_info), scales[i] = lora_scale * alpha / rank.  Argument errors
+ * (n_adapters < 1, a rank outside 1..256, null pointers), a vector weight, a numel that is not the weight's and a context
+ * that borrows its weights are refused before any device work.                                       */
+int pea_unet_load_weight_lora(void* unet, const char* name, const float* base, long long numel, int n_adapters,
+                              const float* const* downs, const float* const* ups, const int* ranks, const float* scales,
+                              void* stream);
 /* random weights of this architecture (no checkpoints exist in the image)                        */
 int pea_unet_init_random(void* unet, unsigned long long seed, void* stream);
 int pea_unet_share_weights(void* dst, void* src);

@@ -424,6 +424,27 @@ int pea_unet_load_weight(void* h, const char* name, const float* src, long long 
   }
   return u->load_weight(name, src, numel, (hipStream_t)stream);
 }
+int pea_unet_load_weight_lora(void* h, const char* name, const float* base, long long numel, int n_adapters,
+                              const float* const* downs, const float* const* ups, const int* ranks, const float* scales,
+                              void* stream) {
+  /* argument errors first: they need neither a context nor a device */
+  if (n_adapters < 1 || !downs || !ups || !ranks || !scales || !name || !base) {
+    pea_set_error("pea_unet_load_weight_lora: n_adapters=%d, null name / base / factor arrays", n_adapters);
+    return PEA_E_INVALID;
+  }
+  for (int i = 0; i < n_adapters; ++i) {
+    if (ranks[i] < 1 || ranks[i] > 256) {
+      pea_set_error("pea_unet_load_weight_lora: adapter %d has rank=%d (1..256)", i, ranks[i]);
+      return PEA_E_SHAPE;
+    }
+    if (!downs[i] || !ups[i]) {
+      pea_set_error("pea_unet_load_weight_lora: adapter %d has a null factor", i);
+      return PEA_E_INVALID;
+    }
+  }
+  NOTNULL(h, "pea_unet_load_weight_lora");
+  return ((Tape*)h)->load_weight_lora(name, base, numel, n_adapters, downs, ups, ranks, scales, (hipStream_t)stream);
+}
 int pea_unet_init_random(void* h, unsigned long long seed, void* stream) {
   NOTNULL(h, "pea_unet_init_random");
   return ((Tape*)h)->init_random(seed, (hipStream_t)stream);

@@ -348,6 +348,15 @@ int pea_op_dpm_update(float* sample, const float* eps, float* x0_prev, long long
   if (!sample || !eps || !x0_prev) { pea_set_error("pea_op_dpm_update: null pointer"); return PEA_E_INVALID; }
   return launch_dpm_update(sample, eps, x0_prev, n, alpha_s, sigma_s, c_s, c_0, c_1, (hipStream_t)stream);
 }
+int pea_op_lcm_update(float* sample, const float* eps, const float* noise, float* denoised, long long n, float kx, float ke,
+                      float c_prev, float c_noise, void* stream) {
+  return launch_lcm_update(sample, eps, noise, denoised, n, kx, ke, c_prev, c_noise, (hipStream_t)stream);
+}
+// ---- LoRA weight composition (lora.hip)
+int pea_op_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank, float scale,
+                        void* stream) {
+  return launch_lora_compose(acc, down, up, out, M, Kf, rank, scale, (hipStream_t)stream);
+}
 int pea_op_inpaint_prepare(const float* image, const float* mask, int N, int H, int W, float* init_image, float* masked_image,
                            float* latent_mask, void* stream) {
   if (!image || !mask || !init_image || !masked_image || !latent_mask) {

@@ -227,6 +227,8 @@ struct Tape {
   int ensure_acts();                 // lazy allocation of the activation / gradient arenas and scratch
   int alloc();
   int load_weight(const char* name, const float* dev_ptr, long long numel, hipStream_t s);
+  int load_weight_lora(const char* name, const float* base, long long numel, int n, const float* const* downs,
+                       const float* const* ups, const int* ranks, const float* scales, hipStream_t s);
   int init_random(unsigned long long seed, hipStream_t s);
   int share_weights_from(const Tape& src);
   int forward(const float* x, const float* t, const void* ehs, int ehs_dtype, const void* text, int text_dtype,

@@ -1118,6 +1118,37 @@ int Tape::load_weight(const char* name, const float* src, long long numel, hipSt
   return PEA_OK;
 }
 
+// LoRA fusion: base + sum_i scales[i] * ups[i] . downs[i] composed in fp32 in the load-time staging buffer, then loaded like any
+// weight (every packed layout, fold_dirty and the recorded weight sequences behave as for load_weight)
+int Tape::load_weight_lora(const char* name, const float* base, long long numel, int n, const float* const* downs,
+                           const float* const* ups, const int* ranks, const float* scales, hipStream_t s) {
+  if (!owns_weights || plan_only) {
+    pea_set_error("pea_unet_load_weight_lora: context borrows its weights");
+    return PEA_E_STATE;
+  }
+  auto it = slot_by_name.find(name);
+  if (it == slot_by_name.end()) {
+    pea_set_error("unet: unknown weight '%s'", name);
+    return PEA_E_NOTFOUND;
+  }
+  const WSlot& w = slots[it->second];
+  SHAPECHK(w.kind != W_VEC, "unet: '%s' is a vector (bias / norm weight): LoRA factors apply to matrices and convolutions", name);
+  SHAPECHK(numel == w.numel, "unet: weight '%s' has %lld elements, expected %lld", name, numel, w.numel);
+  SHAPECHK(w.d0 > 0 && numel % w.d0 == 0, "unet: weight '%s': %lld elements do not split into %d rows", name, numel, w.d0);
+  if (!tmp_f32 || tmp_f32_elems < (size_t)numel) {
+    if (tmp_f32) (void)hipFree(tmp_f32);
+    tmp_f32 = nullptr;
+    tmp_f32_elems = (size_t)numel;
+    HIPCHK(hipMalloc((void**)&tmp_f32, tmp_f32_elems * 4));
+  }
+  const float* acc = base;
+  for (int i = 0; i < n; ++i) {
+    RC(launch_lora_compose(acc, downs[i], ups[i], tmp_f32, w.d0, (int)(numel / w.d0), ranks[i], scales[i], s));
+    acc = tmp_f32;
+  }
+  return load_weight(name, tmp_f32, numel, s);
+}
+
 // (re)compute W' / s / t of every folded LayerNorm from the current weights; blocks until they are in place, because
 // contexts that share these weights may read them from other streams
 int Tape::ensure_folded(hipStream_t s) {

@@ -231,7 +231,13 @@ size_t cfg_combine_workspace_bytes(int B);
 int launch_cfg_combine(const float* eps2, float* out, int B, long long per, float g, float rescale, void* ws, hipStream_t s);
 int launch_dpm_update(float* sample, const float* eps, float* x0_prev, long long n, float alpha_s, float sigma_s,
                       float c_s, float c_0, float c_1, hipStream_t s);
+// LCMScheduler.step: denoised = kx * sample + ke * eps; sample <- c_prev * denoised + c_noise * noise (noise / denoised may be null)
+int launch_lcm_update(float* sample, const float* eps, const float* noise, float* denoised, long long n, float kx, float ke,
+                      float c_prev, float c_noise, hipStream_t s);
 int launch_residual_import(const void* src, int dtype, bf16* dst, int B, int C, long long HW, float scale, hipStream_t s);
+// lora.hip: out[M][Kf] = acc + scale * up[M][rank] . down[rank][Kf], fp32 (acc may be out)
+int launch_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank,
+                        float scale, hipStream_t s);
 // inpainting: init image, masked image and the latent-resolution mask from image [N][3][H][W] / mask [N][1][H][W] (H, W % 8 == 0)
 int launch_inpaint_prepare(const float* image, const float* mask, int N, int H, int W, float* init, float* masked,
                            float* lmask, hipStream_t s);

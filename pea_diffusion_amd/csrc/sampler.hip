@@ -100,6 +100,50 @@ int launch_dpm_update(float* sample, const float* eps, float* x0_prev, long long
   return PEA_OK;
 }
 
+// LCMScheduler.step (tests/test_sdxl_zh_lcm.py:178; diffusers 0.23 [ext]) with the host's float64 scalars folded to four:
+//   denoised = c_out * (x - sqrt(1 - a_t) eps) / sqrt(a_t) + c_skip * x = kx * x + ke * eps
+//   sample  <- c_prev * denoised + c_noise * noise          (noise NULL, the last step: c_prev * denoised)
+// The vector part covers [0, 4 n4) with 16-byte accesses, the scalar part the rest (everything when n4 == 0).
+__global__ void lcm_update_kernel(float* __restrict__ sample, const float* __restrict__ eps, const float* __restrict__ noise,
+                                  float* __restrict__ denoised, long long n, long long n4, float kx, float ke, float c_prev,
+                                  float c_noise) {
+  SM_LOOP(i, n4) {
+    const f32x4 x = ((const f32x4*)sample)[i], e = ((const f32x4*)eps)[i];
+    f32x4 d, y;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { d[j] = fmaf(kx, x[j], ke * e[j]); y[j] = c_prev * d[j]; }
+    if (noise) {
+      const f32x4 z = ((const f32x4*)noise)[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[j] = fmaf(c_noise, z[j], y[j]);
+    }
+    ((f32x4*)sample)[i] = y;
+    if (denoised) ((f32x4*)denoised)[i] = d;
+  }
+  SM_LOOP(t, n - 4 * n4) {
+    const long long i = 4 * n4 + t;
+    const float d = fmaf(kx, sample[i], ke * eps[i]);       // explicit fmaf: both parts round alike whatever hipcc contracts
+    float y = c_prev * d;
+    if (noise) y = fmaf(c_noise, noise[i], y);
+    sample[i] = y;
+    if (denoised) denoised[i] = d;
+  }
+}
+int launch_lcm_update(float* sample, const float* eps, const float* noise, float* denoised, long long n, float kx, float ke,
+                      float c_prev, float c_noise, hipStream_t s) {
+  SHAPECHK(n > 0, "lcm_update: n=%lld", n);
+  if (!sample || !eps) {
+    pea_set_error("lcm_update: null pointer");
+    return PEA_E_INVALID;
+  }
+  const bool vec = (((uintptr_t)sample | (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)denoised) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  hipLaunchKernelGGL(lcm_update_kernel, dim3(sm_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, s, sample, eps, noise, denoised, n,
+                     n4, kx, ke, c_prev, c_noise);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
 // Inpainting inputs (tests/test_sdxl_zh_inpaint.py: VaeImageProcessor.preprocess of image and mask, the masking of __call__ and
 // the nearest-mode resize of prepare_mask_latents): per pixel of image [N][3][H][W] and mask [N][1][H][W], both in [0, 1],
 //   init = 2 image - 1,  masked = init * (mask < 0.5),  latent_mask[n][0][y/8][x/8] = (mask >= 0.5) at y % 8 == x % 8 == 0.

@@ -373,3 +373,27 @@ def dpm_update_(sample, eps, x0_prev, alpha_s, sigma_s, c_s, c_0, c_1):
     check(lib().pea_op_dpm_update(ptr(sample), ptr(eps), ptr(x0_prev), sample.numel(), float(alpha_s), float(sigma_s),
                                   float(c_s), float(c_0), float(c_1), stream_ptr()))
     return sample
+
+
+def lcm_update_(sample, eps, noise, kx, ke, c_prev, c_noise, denoised=None):
+    """In place, one LCMScheduler.step: d = kx*sample + ke*eps; sample <- c_prev*d + c_noise*noise (noise None: c_prev*d);
+    `denoised` (optional, same shape) receives d."""
+    for t in (sample, eps, noise, denoised):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == sample.numel())
+    check(lib().pea_op_lcm_update(ptr(sample), ptr(eps), ptr(noise), ptr(denoised), sample.numel(), float(kx), float(ke),
+                                  float(c_prev), float(c_noise), stream_ptr()))
+    return sample
+
+
+def lora_compose(acc, down, up, scale, out=None):
+    """out[M][Kf] = acc + scale * up[M][r] @ down[r][Kf], fp32 on the GPU (acc any shape with M leading; out may be acc)."""
+    M, r = up.shape[0], down.shape[0]
+    Kf = acc.numel() // M
+    for t in (acc, down, up):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert up.numel() == M * r and down.numel() == r * Kf and acc.numel() == M * Kf
+    if out is None:
+        out = torch.empty_like(acc)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == acc.numel()
+    check(lib().pea_op_lora_compose(ptr(acc), ptr(down), ptr(up), ptr(out), M, Kf, r, float(scale), stream_ptr()))
+    return out

@@ -41,6 +41,17 @@ class _Config:
         self.__dict__.update(cfg.__dict__)
 
 
+def _staged(device, k, shape, t):
+    """weight `k` of a state dict as contiguous fp32 on the device, size-checked against the table's shape (a free function:
+    HipControlNet, the VAE and the text encoders borrow `HipUNet.load_state_dict` unbound)"""
+    n = 1
+    for s in shape:
+        n *= s
+    if t.numel() != n:
+        raise PeaError(f"load_state_dict: {k} has shape {tuple(t.shape)}, expected {shape} (or 1x1 conv)")
+    return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
 class HipUNet:
     def __init__(self, cfg, batch: int, height: Optional[int] = None, width: Optional[int] = None, ctx_len: int = 77,
                  needs_grad: bool = False, share_weights_from: Optional["HipUNet"] = None,
@@ -118,16 +129,67 @@ class HipUNet:
         for k, shape in table.items():
             if k not in sd:
                 continue
-            t = sd[k]
-            n = 1
-            for s in shape:
-                n *= s
-            if t.numel() != n:
-                raise PeaError(f"load_state_dict: {k} has shape {tuple(t.shape)}, expected {shape} (or 1x1 conv)")
-            t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            t = _staged(self.device, k, shape, sd[k])
             check(lib().pea_unet_load_weight(self._h, k.encode(), ptr(t), t.numel(), stream_ptr()))
         torch.cuda.current_stream().synchronize()      # staging tensors above are freed after this call
         return missing, unexpected
+
+    # ---------------------------------------------------------------- LoRA
+    _fused: tuple = ()         # keys currently loaded as base + LoRA
+
+    def fuse_lora(self, base_state_dict: Dict[str, torch.Tensor], lora, lora_scale: float = 1.0) -> List[str]:
+        """`pipe.load_lora_weights(path); pipe.fuse_lora(lora_scale)` (tests/test_sdxl_zh_lcm.py:181-182).  `lora`: a LoRA
+        state dict, a `.safetensors` / `.bin` path (lora.load_lora_state_dict), or a list of `(lora, scale)` pairs that
+        accumulate into the same weights (LCM-LoRA plus a style LoRA).  Every touched weight is re-loaded as
+        base + sum lora_scale * scale * alpha / rank * up @ down, composed in fp32 on the device from `base_state_dict`
+        (the packed bf16 weights cannot be un-rounded) and rounded to bf16 once; weights fused by an earlier call and not
+        named now go back to the base.  Contexts sharing these weights see the result.  Returns the fused keys."""
+        from .lora import load_lora_state_dict, resolve_lora
+        if getattr(self, "_weights_owner", None) is not None:
+            raise PeaError("fuse_lora: this context borrows its weights; fuse on the context that owns them")
+        table = self.weight_table()
+        pairs = lora if isinstance(lora, (list, tuple)) else [(lora, 1.0)]
+        per_key: Dict[str, list] = {}
+        for item, scale in pairs:
+            resolved, _ = resolve_lora(load_lora_state_dict(item), table)
+            for k, (down, up, alpha) in resolved.items():
+                per_key.setdefault(k, []).append((down, up, float(lora_scale) * float(scale) * alpha / down.shape[0]))
+        absent = [k for k in list(per_key) + list(self._fused) if k not in base_state_dict]
+        if absent:
+            raise PeaError(f"fuse_lora: base_state_dict lacks {absent[:5]}")
+        for k in self._fused:
+            if k not in per_key:
+                t = _staged(self.device, k, table[k], base_state_dict[k])
+                check(lib().pea_unet_load_weight(self._h, k.encode(), ptr(t), t.numel(), stream_ptr()))
+        for k, ads in per_key.items():
+            base = _staged(self.device, k, table[k], base_state_dict[k])
+            n = len(ads)
+            keep = [(d.to(self.device), u.to(self.device)) for d, u, _ in ads]
+            downs = (ctypes.c_void_p * n)(*[d.data_ptr() for d, _ in keep])
+            ups = (ctypes.c_void_p * n)(*[u.data_ptr() for _, u in keep])
+            ranks = (ctypes.c_int * n)(*[d.shape[0] for d, _ in keep])
+            scales = (ctypes.c_float * n)(*[s for _, _, s in ads])
+            check(lib().pea_unet_load_weight_lora(self._h, k.encode(), ptr(base), base.numel(), n, downs, ups, ranks,
+                                                  scales, stream_ptr()))
+        torch.cuda.current_stream().synchronize()      # staging tensors above are freed after this call
+        self._fused = tuple(per_key)
+        return list(per_key)
+
+    def unfuse_lora(self, base_state_dict: Dict[str, torch.Tensor]) -> List[str]:
+        """`pipe.unfuse_lora()`: re-loads the fused keys from the base -- through the same load as any weight, so the UNet is
+        bit-identical to one that never fused.  Returns the keys that were restored."""
+        if getattr(self, "_weights_owner", None) is not None:
+            raise PeaError("unfuse_lora: this context borrows its weights")
+        table = self.weight_table()
+        absent = [k for k in self._fused if k not in base_state_dict]
+        if absent:
+            raise PeaError(f"unfuse_lora: base_state_dict lacks {absent[:5]}")
+        for k in self._fused:
+            t = _staged(self.device, k, table[k], base_state_dict[k])
+            check(lib().pea_unet_load_weight(self._h, k.encode(), ptr(t), t.numel(), stream_ptr()))
+        torch.cuda.current_stream().synchronize()
+        restored, self._fused = list(self._fused), ()
+        return restored
 
     def init_random(self, seed: int = 0):
         check(lib().pea_unet_init_random(self._h, seed, stream_ptr()))
