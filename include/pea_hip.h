@@ -201,6 +201,19 @@ int pea_op_dpm_update(float* sample, const float* eps, float* x0_prev, long long
  *   noise NULL (the last step, c_prev = 1): the noise term is dropped.  denoised (diffusers' second output) may be NULL. */
 int pea_op_lcm_update(float* sample, const float* eps, const float* noise, float* denoised, long long n, float kx, float ke,
                       float c_prev, float c_noise, void* stream);
+/* euler_update: one EulerDiscreteScheduler / EulerAncestralDiscreteScheduler step (diffusers 0.23 [ext]: epsilon prediction,
+ *   so the derivative (x - x0) / sigma is eps itself) fused with the NEXT step's scale_model_input and the CFG batch
+ *   doubling, host-side coefficients folded to three scalars, fp32 [n]:
+ *     x'        = sample + k_e * eps                  k_e = sigma_down - sigma   (Euler: sigma_down = sigma_next)
+ *     x'       += k_n * noise                         k_n = sigma_up; noise NULL (Euler, or the last ancestral step): dropped
+ *     sample   <- x'                                  in place
+ *     model_in[d * n + i] <- x' * k_s  for d < dup    k_s = 1 / sqrt(sigma_next^2 + 1); dup 1 or 2 (2: the CFG-doubled batch)
+ *   model_in NULL: only the sample is updated (the last step).  eps NULL is the entry form: sample is only read and
+ *   model_in = sample * k_s (the first step's scale_model_input; noise must be NULL, model_in not).  model_in ([dup * n]) must
+ *   not overlap sample.  16-byte accesses when every pointer (model_in + n included for dup 2) is 16-byte aligned, scalar
+ *   otherwise, with identical results; no atomics: bit-reproducible. */
+int pea_op_euler_update(float* sample, const float* eps, const float* noise, float* model_in, long long n, int dup, float k_e,
+                        float k_n, float k_s, void* stream);
 
 /* LoRA weight composition (`pipe.load_lora_weights(...)`, `pipe.fuse_lora()`, tests/test_sdxl_zh_lcm.py:181-182):
  *   out[m][k] = acc[m][k] + scale * sum_r up[m][r] * down[r][k]      all fp32 device, torch layouts, 1 <= rank <= 256
@@ -277,6 +290,27 @@ int pea_unet_create(const pea_unet_config* cfg, int B, int H, int W, int L, int 
  * / gradient arenas will take in HBM.  Use it to size a configuration against 288 GB before creating it.   */
 int pea_unet_plan(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int* n_ops, int* n_weights,
                   long long* n_params, long long* weight_bytes, long long* act_bytes, long long* grad_bytes);
+/* Guidance-embedded UNets (`time_cond_proj_dim` of fully distilled LCM checkpoints such as LCM-SDXL; the reference's loop
+ * computes the input at tests/test_sdxl_zh_inpaint.py:721-745).  The layout of pea_unet_config is frozen, so the width travels
+ * beside it: pea_unet_create_cond / pea_unet_plan_cond are pea_unet_create / pea_unet_plan with time_cond_proj_dim (0: none,
+ * what the two plain entry points forward; otherwise a multiple of 64, the GEMM's K tile, else PEA_E_SHAPE).  The graph gains
+ * the bias-free Linear `time_embedding.cond_proj.weight` [block_out[0]][time_cond_proj_dim], whose output is added to the
+ * sinusoidal timestep projection in front of time_embedding.linear_1 (inference and PEA_UNET_GRAD contexts alike; the input
+ * receives no gradient).  pea_unet_plan_cond also reports the attention census of pea_unet_plan_attention (either may be NULL).
+ * pea_unet_plan_weight: numel / kind / dims (as pea_unet_weight_info) of the weight `name` on the planned graph, PEA_E_NOTFOUND
+ * when the graph has none of that name.
+ * pea_unet_set_timestep_cond: cond fp32 [B][time_cond_proj_dim] on the device (`timestep_cond` of the UNet call), copied into
+ * the context and in effect for every following pea_unet_forward; NULL clears it.  Unset or cleared, the projection
+ * contributes nothing (diffusers with timestep_cond=None) and eps equals that of a plain UNet with the same weights bit for
+ * bit.  PEA_E_STATE on a context created without a time_cond_proj_dim. */
+int pea_unet_create_cond(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int time_cond_proj_dim,
+                         int own_weights, void** out);
+int pea_unet_plan_cond(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int time_cond_proj_dim, int* n_ops,
+                       int* n_weights, long long* n_params, long long* weight_bytes, long long* act_bytes,
+                       long long* grad_bytes, int* n_attn, int* n_prescaled);
+int pea_unet_plan_weight(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int time_cond_proj_dim,
+                         const char* name, long long* numel, int* kind, int* d0, int* d1);
+int pea_unet_set_timestep_cond(void* unet, const float* cond, void* stream);
 /* ... and the scratch buffers the same context allocates beside those arenas on first use (GroupNorm partials, attention
  * row constants and dK/dV split partials, the FF d(pre-activation) buffer, split-K partials of the stacked K|V projection,
  * fp32 time-embedding gradients).  bwd_batch > 0: a merged-pass context that differentiates its leading bwd_batch samples. */

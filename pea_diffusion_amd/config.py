@@ -32,6 +32,9 @@ class UNetConfig:
     addition_time_embed_dim: int = 256
     projection_class_embeddings_input_dim: int = 2816
     name: str = "sdxl"
+    # guidance embedding of fully distilled LCM UNets: width of `timestep_cond` (time_embedding.cond_proj); None = no such input.
+    # Not a pea_unet_config field (that layout is frozen): HipUNet hands it to pea_unet_create_cond.
+    time_cond_proj_dim: Optional[int] = None
 
     @property
     def pooled_dim(self) -> int:
@@ -40,6 +43,13 @@ class UNetConfig:
 
 def sdxl_config() -> UNetConfig:
     return UNetConfig()
+
+
+def lcm_sdxl_config() -> UNetConfig:
+    """latent-consistency/lcm-sdxl `unet/config.json` [ext, recalled -- no network in the build image]: SDXL base plus
+    `time_cond_proj_dim: 256`, the guidance-scale embedding the reference's loop feeds as `timestep_cond`
+    (tests/test_sdxl_zh_inpaint.py:721-745).  2 567 463 684 + 320 x 256 parameters."""
+    return UNetConfig(time_cond_proj_dim=256, name="lcm_sdxl")
 
 
 def ssd1b_config() -> UNetConfig:
@@ -120,7 +130,8 @@ def unet_config_from_diffusers(d: dict, name: str = "from_json") -> UNetConfig:
         cross_attention_dim=d.get("cross_attention_dim", 1280), use_linear_projection=bool(d.get("use_linear_projection", False)),
         norm_num_groups=d.get("norm_num_groups", 32), norm_eps=d.get("norm_eps", 1e-5),
         addition_embed_type=d.get("addition_embed_type"), addition_time_embed_dim=d.get("addition_time_embed_dim") or 0,
-        projection_class_embeddings_input_dim=d.get("projection_class_embeddings_input_dim") or 0, name=name)
+        projection_class_embeddings_input_dim=d.get("projection_class_embeddings_input_dim") or 0, name=name,
+        time_cond_proj_dim=d.get("time_cond_proj_dim") or None)
 
 
 def sd15_config() -> UNetConfig:
@@ -158,6 +169,11 @@ class CUNetConfig(ctypes.Structure):
                 ("eps", ctypes.c_float), ("text_time", ctypes.c_int), ("add_time_dim", ctypes.c_int),
                 ("proj_in_dim", ctypes.c_int), ("per_layer_depth", ctypes.c_int),
                 ("depth_down", (ctypes.c_int * 4) * 4), ("depth_up", (ctypes.c_int * 4) * 4), ("depth_mid", ctypes.c_int)]
+
+
+def time_cond_dim(cfg) -> int:
+    """`time_cond_proj_dim` as the C ABI takes it beside the config struct (0: none)"""
+    return int(getattr(cfg, "time_cond_proj_dim", None) or 0)
 
 
 def to_c(cfg) -> CUNetConfig:

@@ -48,23 +48,73 @@ static void set_flags(Tape& u, int flags) {
 
 extern "C" {
 
-int pea_unet_create(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int own_weights,
-                    void** out) {
+static int check_cond_dim(const char* what, int time_cond_proj_dim) {
+  if (time_cond_proj_dim < 0) {
+    pea_set_error("%s: time_cond_proj_dim=%d (0: none)", what, time_cond_proj_dim);
+    return PEA_E_INVALID;
+  }
+  return PEA_OK;
+}
+int pea_unet_create_cond(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int time_cond_proj_dim,
+                         int own_weights, void** out) {
   NOTNULL(cfg, "pea_unet_create");
   NOTNULL(out, "pea_unet_create");
+  RCX(check_cond_dim("pea_unet_create_cond", time_cond_proj_dim));
   RCX(require_device("pea_unet_create"));
   Tape* u = new Tape();
   memcpy(&u->cfg, cfg, sizeof(PeaUnetCfg));
   u->B = B; u->H = H; u->W = W; u->L = L; set_flags(*u, flags);
+  u->time_cond_dim = time_cond_proj_dim;
   u->owns_weights = own_weights != 0;
   return finish_create(u, out);
 }
+int pea_unet_create(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int own_weights,
+                    void** out) {
+  return pea_unet_create_cond(cfg, B, H, W, L, flags, 0, own_weights, out);
+}
+int pea_unet_set_timestep_cond(void* h, const float* cond, void* stream) {
+  NOTNULL(h, "pea_unet_set_timestep_cond");
+  return ((Tape*)h)->set_timestep_cond(cond, (hipStream_t)stream);
+}
 int pea_unet_plan(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int* n_ops, int* n_weights,
                   long long* n_params, long long* weight_bytes, long long* act_bytes, long long* grad_bytes) {
-  NOTNULL(cfg, "pea_unet_plan");
+  return pea_unet_plan_cond(cfg, B, H, W, L, flags, 0, n_ops, n_weights, n_params, weight_bytes, act_bytes, grad_bytes, nullptr,
+                            nullptr);
+}
+int pea_unet_plan_weight(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int time_cond_proj_dim,
+                         const char* name, long long* numel, int* kind, int* d0, int* d1) {
+  NOTNULL(cfg, "pea_unet_plan_weight");
+  NOTNULL(name, "pea_unet_plan_weight");
+  RCX(check_cond_dim("pea_unet_plan_weight", time_cond_proj_dim));
   Tape u;
   memcpy(&u.cfg, cfg, sizeof(PeaUnetCfg));
   u.B = B; u.H = H; u.W = W; u.L = L; set_flags(u, flags);
+  u.time_cond_dim = time_cond_proj_dim;
+  u.plan_only = true;
+  int rc = u.build();
+  if (rc == PEA_OK) rc = u.alloc();
+  if (rc != PEA_OK) return rc;
+  auto it = u.slot_by_name.find(name);
+  if (it == u.slot_by_name.end()) {
+    pea_set_error("pea_unet_plan_weight: the graph has no weight '%s'", name);
+    return PEA_E_NOTFOUND;
+  }
+  const WSlot& s = u.slots[it->second];
+  if (numel) *numel = s.numel;
+  if (kind) *kind = s.kind;
+  if (d0) *d0 = s.d0;
+  if (d1) *d1 = s.d1;
+  return PEA_OK;
+}
+int pea_unet_plan_cond(const pea_unet_config* cfg, int B, int H, int W, int L, int flags, int time_cond_proj_dim, int* n_ops,
+                       int* n_weights, long long* n_params, long long* weight_bytes, long long* act_bytes,
+                       long long* grad_bytes, int* n_attn, int* n_prescaled) {
+  NOTNULL(cfg, "pea_unet_plan");
+  RCX(check_cond_dim("pea_unet_plan_cond", time_cond_proj_dim));
+  Tape u;
+  memcpy(&u.cfg, cfg, sizeof(PeaUnetCfg));
+  u.B = B; u.H = H; u.W = W; u.L = L; set_flags(u, flags);
+  u.time_cond_dim = time_cond_proj_dim;
   u.plan_only = true;
   int rc = u.build();
   if (rc == PEA_OK) rc = u.alloc();
@@ -77,6 +127,8 @@ int pea_unet_plan(const pea_unet_config* cfg, int B, int H, int W, int L, int fl
   if (weight_bytes) *weight_bytes = (long long)u.wbytes;
   if (act_bytes) *act_bytes = (long long)u.abytes;
   if (grad_bytes) *grad_bytes = (long long)u.gbytes;
+  if (n_attn) *n_attn = u.n_attn;
+  if (n_prescaled) *n_prescaled = u.n_attn_pre;
   return PEA_OK;
 }
 /* scratch buffers the same context allocates beside its arenas on first use (host only).  bwd_batch > 0: a merged-pass context

@@ -352,6 +352,10 @@ int pea_op_lcm_update(float* sample, const float* eps, const float* noise, float
                       float c_prev, float c_noise, void* stream) {
   return launch_lcm_update(sample, eps, noise, denoised, n, kx, ke, c_prev, c_noise, (hipStream_t)stream);
 }
+int pea_op_euler_update(float* sample, const float* eps, const float* noise, float* model_in, long long n, int dup, float k_e,
+                        float k_n, float k_s, void* stream) {
+  return launch_euler_update(sample, eps, noise, model_in, n, dup, k_e, k_n, k_s, (hipStream_t)stream);
+}
 // ---- LoRA weight composition (lora.hip)
 int pea_op_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank, float scale,
                         void* stream) {

@@ -156,6 +156,14 @@ struct Tape {
   bool inp_set = false;
   int inp_cond_b = 0, inp_lat_b = 0;
   int set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s);
+  // Guidance embedding (`time_cond_proj_dim` of fully distilled LCM UNets; not a pea_unet_config field, whose layout is frozen:
+  // pea_unet_create_cond / pea_unet_plan_cond carry it): a conditioning input [B][time_cond_dim] goes through the bias-free
+  // Linear time_embedding.cond_proj and is added to the sinusoidal timestep projection in front of time_embedding.linear_1.
+  // The input tensor t_tcond is zero until pea_unet_set_timestep_cond fills it (and again after NULL): a zero row projects to
+  // zero and the epilogue's add returns the timestep projection bit for bit, diffusers' `timestep_cond=None`.
+  int time_cond_dim = 0;
+  int t_tcond = -1;
+  int set_timestep_cond(const float* cond, hipStream_t s);
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

@@ -592,6 +592,14 @@ int Tape::build() {
   // time embedding
   int te = bd.T(B, c.block_out[0], B);
   { Op& o = bd.push(OP_TEMB); o.out = te; o.src = 0; o.p0 = c.block_out[0]; }
+  if (time_cond_dim) {   // TimestepEmbedding(cond_proj_dim=...): sample + cond_proj(condition), in the GEMM's residual epilogue
+    SHAPECHK(graph == 0, "unet: time_cond_proj_dim is a UNet2DConditionModel field (graph %d)", graph);
+    SHAPECHK(time_cond_dim > 0 && time_cond_dim % 64 == 0,
+             "unet: time_cond_proj_dim=%d must be a positive multiple of 64 (the GEMM's K tile)", time_cond_dim);
+    t_tcond = bd.T(B, time_cond_dim, B);
+    tn[t_tcond].zero_init = true;
+    te = bd.linear(t_tcond, "time_embedding.cond_proj", c.block_out[0], false, te);
+  }
   int emb = bd.linear(te, "time_embedding.linear_1", temb_dim, true);
   emb = bd.silu(emb);
   emb = bd.linear(emb, "time_embedding.linear_2", temb_dim, true);
@@ -1071,6 +1079,18 @@ int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, i
   inp_set = true;
   inp_cond_b = cond_b;
   inp_lat_b = lat_b;
+  return PEA_OK;
+}
+
+int Tape::set_timestep_cond(const float* cond, hipStream_t s) {
+  if (t_tcond < 0) {
+    pea_set_error("pea_unet_set_timestep_cond: context created without a time_cond_proj_dim (pea_unet_create_cond)");
+    return PEA_E_STATE;
+  }
+  RC(ensure_acts());
+  Tn& t = tn[t_tcond];
+  if (!cond) HIPCHK(hipMemsetAsync(t.d, 0, (size_t)t.rows * t.cols * 2, s));
+  else RC(launch_cast_f32_bf16(cond, t.d, t.rows * t.cols, s));
   return PEA_OK;
 }
 
@@ -1919,6 +1939,7 @@ int Trainer::step(const float* latents, const float* noise, const long long* tim
     if (ok) {
       merged = new Tape();
       merged->cfg = S.cfg;
+      merged->time_cond_dim = S.time_cond_dim;     // (never set on the merged context: it contributes nothing)
       merged->B = 2 * B; merged->H = S.H; merged->W = S.W; merged->L = Tt.L;
       merged->needs_grad = true; merged->owns_weights = false; merged->bwd_batch = B;
       RC(merged->build());
@@ -2024,6 +2045,7 @@ int Trainer::context_for(int nt, Tape** out) {
   if (it != merged_n.end()) { *out = it->second; return PEA_OK; }
   Tape* m = new Tape();
   m->cfg = S.cfg;
+  m->time_cond_dim = S.time_cond_dim;
   m->B = B + nt; m->H = S.H; m->W = S.W; m->L = Tt.L;
   m->needs_grad = true; m->owns_weights = false; m->bwd_batch = B;
   int rc = m->build();

@@ -234,6 +234,8 @@ int launch_dpm_update(float* sample, const float* eps, float* x0_prev, long long
 // LCMScheduler.step: denoised = kx * sample + ke * eps; sample <- c_prev * denoised + c_noise * noise (noise / denoised may be null)
 int launch_lcm_update(float* sample, const float* eps, const float* noise, float* denoised, long long n, float kx, float ke,
                       float c_prev, float c_noise, hipStream_t s);
+int launch_euler_update(float* sample, const float* eps, const float* noise, float* model_in, long long n, int dup, float k_e,
+                        float k_n, float k_s, hipStream_t s);
 int launch_residual_import(const void* src, int dtype, bf16* dst, int B, int C, long long HW, float scale, hipStream_t s);
 // lora.hip: out[M][Kf] = acc + scale * up[M][rank] . down[rank][Kf], fp32 (acc may be out)
 int launch_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank,

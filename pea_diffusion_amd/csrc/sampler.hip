@@ -144,6 +144,71 @@ int launch_lcm_update(float* sample, const float* eps, const float* noise, float
   return PEA_OK;
 }
 
+// EulerDiscreteScheduler / EulerAncestralDiscreteScheduler step (diffusers 0.23 [ext]; epsilon prediction, so the derivative
+// (x - x0) / sigma IS eps) fused with the NEXT step's scale_model_input and the CFG batch doubling:
+//   x' = sample + k_e * eps (+ k_n * noise);  sample <- x';  model_in[d * n + i] <- x' * k_s  for d < dup
+// eps NULL is the entry form (sample is only read: model_in = sample * k_s).  The vector part covers [0, 4 n4) with 16-byte
+// accesses, the scalar part the rest (everything when n4 == 0); explicit fmaf so that both parts round alike.
+__global__ void euler_update_kernel(float* __restrict__ sample, const float* __restrict__ eps, const float* __restrict__ noise,
+                                    float* __restrict__ model_in, long long n, long long n4, int dup, float k_e, float k_n,
+                                    float k_s) {
+  SM_LOOP(i, n4) {
+    f32x4 x = ((const f32x4*)sample)[i];
+    if (eps) {
+      const f32x4 e = ((const f32x4*)eps)[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = fmaf(k_e, e[j], x[j]);
+      if (noise) {
+        const f32x4 z = ((const f32x4*)noise)[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j] = fmaf(k_n, z[j], x[j]);
+      }
+      ((f32x4*)sample)[i] = x;
+    }
+    if (model_in) {
+      f32x4 m;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) m[j] = x[j] * k_s;
+      ((f32x4*)model_in)[i] = m;
+      if (dup == 2) ((f32x4*)(model_in + n))[i] = m;
+    }
+  }
+  SM_LOOP(t, n - 4 * n4) {
+    const long long i = 4 * n4 + t;
+    float x = sample[i];
+    if (eps) {
+      x = fmaf(k_e, eps[i], x);
+      if (noise) x = fmaf(k_n, noise[i], x);
+      sample[i] = x;
+    }
+    if (model_in) {
+      const float m = x * k_s;
+      model_in[i] = m;
+      if (dup == 2) model_in[n + i] = m;
+    }
+  }
+}
+int launch_euler_update(float* sample, const float* eps, const float* noise, float* model_in, long long n, int dup, float k_e,
+                        float k_n, float k_s, hipStream_t s) {
+  SHAPECHK(n > 0 && (dup == 1 || dup == 2), "euler_update: n=%lld dup=%d (1 or 2)", n, dup);
+  if (!sample) {
+    pea_set_error("euler_update: null sample");
+    return PEA_E_INVALID;
+  }
+  if (!eps && (noise || !model_in)) {
+    pea_set_error("euler_update: without eps (the entry form) model_in is the only output and there is no noise term");
+    return PEA_E_INVALID;
+  }
+  // the second copy of a doubled model input starts at model_in + n: one more pointer that has to be 16-byte aligned
+  const uintptr_t second = (model_in && dup == 2) ? (uintptr_t)(model_in + n) : 0;
+  const bool vec = (((uintptr_t)sample | (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)model_in | second) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  hipLaunchKernelGGL(euler_update_kernel, dim3(sm_grid(vec ? (n + 3) / 4 : n)), dim3(256), 0, s, sample, eps, noise, model_in, n,
+                     n4, dup, k_e, k_n, k_s);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
 // Inpainting inputs (tests/test_sdxl_zh_inpaint.py: VaeImageProcessor.preprocess of image and mask, the masking of __call__ and
 // the nearest-mode resize of prepare_mask_latents): per pixel of image [N][3][H][W] and mask [N][1][H][W], both in [0, 1],
 //   init = 2 image - 1,  masked = init * (mask < 0.5),  latent_mask[n][0][y/8][x/8] = (mask >= 0.5) at y % 8 == x % 8 == 0.

@@ -53,13 +53,16 @@ def inpaint_denoise(unet, scheduler, vae_encoder, image, mask, prompt_embeds, ad
                     num_inference_steps: int = 50, strength: float = 0.9999, guidance_scale: float = 7.5,
                     guidance_rescale: float = 0.0, noise: Optional[torch.Tensor] = None,
                     vae_noise: Optional[Sequence[Optional[torch.Tensor]]] = None, generator: Optional[torch.Generator] = None,
-                    callback: Optional[Callable] = None) -> torch.Tensor:
+                    callback: Optional[Callable] = None, timestep_cond=None) -> torch.Tensor:
     """Inpainting denoise loop (:481-762) -> final latents fp32 [N,4,h,w] (the VAE decode stays outside, as in
     `sampler.denoise`).  image / mask: [N,3,8h,8w] / [N,1,8h,8w] in [0, 1]; `unet` a 9-channel HipUNet built with
     inpaint_inputs=True for batch 2N under CFG (guidance_scale > 1), N otherwise; `vae_encoder` a HipVAEEncoder for [N,3,8h,8w].
     noise: the start noise [N,4,h,w]; vae_noise: (init image, masked image) posterior-sampling noise of the two VAE encodes
     (the first is only used when strength < 1).  Anything not given is drawn from `generator` in the reference's order:
-    init-image encode, start noise, masked-image encode."""
+    init-image encode, start noise, masked-image encode.  The sigma-space schedulers (`sampler.EulerDiscrete`, ...) start a
+    strength < 1 run from `image_latents + sigma * noise` and get `generator` for their steps; `timestep_cond` as in
+    `sampler.denoise`."""
+    from .sampler import check_timestep_cond
     if unet.in_channels == unet.cfg.out_channels:
         raise ValueError(f"inpaint_denoise needs a {2 * unet.cfg.out_channels + 1}-channel inpainting UNet; a "
                          f"{unet.in_channels}-channel UNet never sees the mask (that is img2img)")
@@ -68,6 +71,9 @@ def inpaint_denoise(unet, scheduler, vae_encoder, image, mask, prompt_embeds, ad
     if not getattr(unet, "inpaint_inputs", False):
         raise ValueError("inpaint_denoise: build the UNet with HipUNet(..., inpaint_inputs=True)")
     do_cfg = guidance_scale > 1.0
+    timestep_cond = check_timestep_cond(unet, timestep_cond, do_cfg)
+    ukw = {} if timestep_cond is None else dict(timestep_cond=timestep_cond)
+    skw = dict(generator=generator) if getattr(scheduler, "fused_model_input", False) else {}
     N = image.shape[0]
     if unet.B != (2 * N if do_cfg else N):
         raise ValueError(f"The UNet is built for batch {unet.B}; {N} images {'with' if do_cfg else 'without'} CFG need "
@@ -91,17 +97,20 @@ def inpaint_denoise(unet, scheduler, vae_encoder, image, mask, prompt_embeds, ad
     else:
         t0 = timesteps[:1].to(dev, torch.int64).repeat(N).contiguous()
         ac = torch.from_numpy(scheduler.alphas_cumprod).to(dev, torch.float32)
-        latents = ops.add_noise(image_latents.contiguous(), noise, t0, ac)
+        if getattr(scheduler, "fused_model_input", False):
+            latents = scheduler.add_noise(image_latents, noise, t_start)
+        else:
+            latents = ops.add_noise(image_latents.contiguous(), noise, t0, ac)
     masked_latents = vae_encoder.encode_latents(masked_image, noise=_noise(shape, vn[1], generator, dev))
     unet.set_inpaint_cond(latent_mask, masked_latents, latent_batch=N)
     try:
         for i, t in enumerate(timesteps):
             x = scheduler.scale_model_input(latents, t)
             noise_pred = unet(x, t, encoder_hidden_states=prompt_embeds, added_cond_kwargs=added_cond_kwargs,
-                              return_dict=False)[0]
+                              return_dict=False, **ukw)[0]
             if do_cfg:
                 noise_pred = ops.cfg_combine(noise_pred.float(), guidance_scale, guidance_rescale)
-            latents = scheduler.step(noise_pred, t, latents, return_dict=False)[0]
+            latents = scheduler.step(noise_pred, t, latents, return_dict=False, **skw)[0]
             if callback is not None:
                 callback(i, t, latents)
     finally:

@@ -385,6 +385,19 @@ def lcm_update_(sample, eps, noise, kx, ke, c_prev, c_noise, denoised=None):
     return sample
 
 
+def euler_update_(sample, eps, noise, model_in, k_e, k_n, k_s, dup=1):
+    """One Euler / Euler-ancestral step fused with the next model input (pea_op_euler_update): in place
+    sample <- sample + k_e*eps (+ k_n*noise); model_in[d] <- sample * k_s for d < dup (model_in None: skipped).
+    eps None is the entry form: sample is only read, model_in = sample * k_s."""
+    n = sample.numel()
+    for t in (sample, eps, noise):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
+    assert model_in is None or (model_in.dtype == torch.float32 and model_in.is_contiguous() and model_in.numel() == dup * n)
+    check(lib().pea_op_euler_update(ptr(sample), ptr(eps), ptr(noise), ptr(model_in), n, int(dup), float(k_e), float(k_n),
+                                    float(k_s), stream_ptr()))
+    return sample
+
+
 def lora_compose(acc, down, up, scale, out=None):
     """out[M][Kf] = acc + scale * up[M][r] @ down[r][Kf], fp32 on the GPU (acc any shape with M leading; out may be acc)."""
     M, r = up.shape[0], down.shape[0]

@@ -71,8 +71,9 @@ class HipUNet:
         self.inpaint_inputs = inpaint_inputs
         # PEA_UNET_GRAD | PEA_UNET_RESIDUAL_INPUTS | PEA_UNET_INPAINT_INPUTS
         flags = (1 if needs_grad else 0) | (2 if residual_inputs else 0) | (4 if inpaint_inputs else 0)
-        check(lib().pea_unet_create(ctypes.byref(c), self.B, self.H, self.W, self.L, flags,
-                                    int(share_weights_from is None), ctypes.byref(self._h)))
+        self.time_cond_proj_dim = _cfg.time_cond_dim(cfg) or None
+        check(lib().pea_unet_create_cond(ctypes.byref(c), self.B, self.H, self.W, self.L, flags, _cfg.time_cond_dim(cfg),
+                                         int(share_weights_from is None), ctypes.byref(self._h)))
         if share_weights_from is not None:
             check(lib().pea_unet_share_weights(self._h, share_weights_from._h))
             self._weights_owner = share_weights_from      # keep alive
@@ -100,6 +101,7 @@ class HipUNet:
     def release_activations(self):
         """free the activation / gradient arenas (weights stay); the next forward allocates them again"""
         check(lib().pea_unet_release_activations(self._h))
+        self._tcond = None             # the context's conditioning input comes back zeroed
 
     # ---------------------------------------------------------------- weights
     def weight_table(self) -> Dict[str, tuple]:
@@ -201,7 +203,11 @@ class HipUNet:
 
     # ---------------------------------------------------------------- forward
     def __call__(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, cross_attention_kwargs=None,
-                 return_dict=False, down_block_additional_residuals=None, mid_block_additional_residual=None):
+                 return_dict=False, down_block_additional_residuals=None, mid_block_additional_residual=None,
+                 timestep_cond=None):
+        """`timestep_cond` [B, time_cond_proj_dim]: the guidance-scale embedding of a guidance-embedded UNet
+        (`sampler.guidance_scale_embedding`); None, as in diffusers, leaves the projection out of this call."""
+        self._route_timestep_cond(timestep_cond)
         if down_block_additional_residuals is not None or mid_block_additional_residual is not None:
             self.set_additional_residuals(down_block_additional_residuals, mid_block_additional_residual)
         elif self.residual_inputs and self._residuals_set:
@@ -235,6 +241,23 @@ class HipUNet:
                     fn(blk, (), out)
         out = eps.to(sample.dtype) if sample.dtype in (torch.float16, torch.bfloat16) else eps
         return (out,)
+
+    # ---------------------------------------------------------------- guidance embedding
+    _tcond = None          # the conditioning last handed to the context (kept alive while the cast may still be queued)
+
+    def _route_timestep_cond(self, timestep_cond):
+        if timestep_cond is None:
+            if self._tcond is not None:
+                check(lib().pea_unet_set_timestep_cond(self._h, None, stream_ptr()))
+                self._tcond = None
+            return
+        if self.time_cond_proj_dim is None:
+            raise PeaError("timestep_cond given, but this UNet's config has no time_cond_proj_dim")
+        if tuple(timestep_cond.shape) != (self.B, self.time_cond_proj_dim):
+            raise PeaError(f"timestep_cond {tuple(timestep_cond.shape)} != {(self.B, self.time_cond_proj_dim)}")
+        c = timestep_cond.detach().to(self.device, torch.float32).contiguous()
+        check(lib().pea_unet_set_timestep_cond(self._h, ptr(c), stream_ptr()))
+        self._tcond = c
 
     # ---------------------------------------------------------------- inpainting condition
     _inp = None            # (mask, masked_latents) fp32 on the device, as last handed to the context
