@@ -393,6 +393,55 @@ int pea_text_forward(void* enc, const long long* ids, int hidden_index, float* h
  * log2 domain).  Diagnostic read-back for the bucket parity test. */
 int pea_text_rel_bias(void* enc, float* bias_out, void* stream);
 
+/* CLIP vision tower (HF transformers CLIPVisionModelWithProjection) on the same op tape, inference only: the image half of
+ * the CLIP pairs whose text half pea_text_* runs, for image-text similarity (CLIPScore) of decoded samples.  Keys
+ * `vision_model.embeddings.{class_embedding, patch_embedding.weight, position_embedding.weight}`, `vision_model.pre_layrnorm.*`
+ * (spelling as HF), `vision_model.encoder.layers.N.{layer_norm1, self_attn.{q,k,v,out}_proj, layer_norm2, mlp.fc1, mlp.fc2}.*`,
+ * `vision_model.post_layernorm.*`, `visual_projection.weight`; the handle works with pea_unet_num_weights / weight_info /
+ * load_weight / init_random / memory / destroy.
+ *   rows = patchify(pixels) [B*Np][3 P P], column (c, py, px) (zero-padded to a multiple of 64, the GEMM's K tile: 588 -> 640)
+ *   x[b][0] = class_embedding + pos[0];  x[b][1+i] = rows[b][i] . patch_w^T + pos[1+i];  hidden_states[0] = pre_layrnorm(x)
+ *   `layers` pre-LN blocks, unmasked attention over Np + 1 tokens, scale head_dim^-0.5, MLP activation `act`
+ *   pooler_output = post_layernorm(h_N[:, 0]);  image_embeds = pooler_output . visual_projection^T
+ * head_dim = width / heads must be 64 (ViT-B/32, B/16, L/14) or 80 (ViT-H/14; stored zero-padded to 128 like the SD1.5 UNet's
+ * heads), else PEA_E_SHAPE; width and intermediate multiples of 64, proj_dim a multiple of 4.
+ * pea_vision_plan: host only (no device needed): parameter total, tokens per image (Np + 1), attention ops (= layers).
+ * pea_vision_forward: pixels fp32 [B,3,S,S] (already normalised: pea_op_preprocess), device.  hidden_index as pea_text_forward:
+ * -1 = the last state BEFORE post_layernorm (HF `last_hidden_state`), -2 = hidden_states[-2], k >= 0 = hidden_states[k].
+ * Outputs, each optional (NULL): hidden_out fp32 [B,Np+1,width], pooled_out fp32 [B,width] (`pooler_output`), embeds_out
+ * fp32 [B,proj_dim] (`image_embeds`). */
+typedef struct pea_vision_config {
+  int image_size, patch_size, width, heads, layers, intermediate;
+  int act;          /* 1 GELU(erf), 3 quick-GELU */
+  int proj_dim;     /* visual_projection width */
+  float eps;
+} pea_vision_config;
+int pea_vision_create(const pea_vision_config* cfg, int B, void** out);
+int pea_vision_plan(const pea_vision_config* cfg, int B, long long* n_params, int* n_tokens, int* n_attn);
+int pea_vision_forward(void* enc, const float* pixels, int hidden_index, float* hidden_out, float* pooled_out, float* embeds_out,
+                       void* stream);
+/* Image preprocessing in front of the tower: images fp32 [B,3,H,W] -> v = clamp((x - lo) / (hi - lo), 0, 1), with `quantize`
+ * round(v * 255) / 255 (what a saved 8-bit image holds) -> antialiased bicubic resample with the definition of
+ * torch.nn.functional.interpolate(mode="bicubic", antialias=True, align_corners=False) (separable Keys kernel a = -0.5, support
+ * 2 max(scale, 1), per-output weights normalised to sum 1) -> centre crop -> (v - mean[c]) / std[c] -> out fp32 [B,3,size,size].
+ * The caller supplies one tap table per axis, DEVICE buffers covering the `size` CROPPED output coordinates: coordinate i reads
+ * source coordinates first[i] .. first[i] + count[i] - 1 with weights[i * taps + k] (zero past count[i]); and the tiling: one
+ * workgroup produces tile_h x tile_w outputs (tile_w % 4 == 0) from a source window of at most win_h x win_w pixels (win_w % 4
+ * == 0, its first column rounded down to a multiple of 4) staged in LDS: 4 (win_h win_w + win_h tile_w + tile_w x_taps +
+ * tile_h y_taps) bytes <= 64 KiB, else PEA_E_SHAPE.  pea_diffusion_amd/vision.py builds both from (H, W, size) in float64. */
+int pea_op_preprocess(const float* images, int B, int H, int W, float lo, float hi, int quantize, const int* y_first,
+                      const int* y_count, const float* y_weights, int y_taps, const int* x_first, const int* x_count,
+                      const float* x_weights, int x_taps, int size, int tile_h, int tile_w, int win_h, int win_w, float mean0,
+                      float mean1, float mean2, float std0, float std1, float std2, float* out, void* stream);
+/* pixels fp32 [B,3,S,S] -> rows bf16 [B*(S/P)^2][kpad] (the patch GEMM's A operand): column (c, py, px) = the conv weight
+ * flattened, columns >= 3 P P zero; kpad >= 3 P P, a multiple of 8.  A gather and one rounding. */
+int pea_op_patchify(const float* pixels, void* rows, int B, int S, int P, int kpad, void* stream);
+/* CLIPScore (Hessel et al. 2021): out[b] = w * max(cos(image_embeds[b], text_embeds[b]), 0); clamp = 0 keeps negative cosines
+ * (w = 1: the plain cosine).  fp32 [B,D] inputs, fp32 [B] output; norms floored at 1e-8 as torch.cosine_similarity does; one
+ * wave per pair with a fixed reduction order: bit-reproducible run to run. */
+int pea_op_clip_score(const float* image_embeds, const float* text_embeds, float* out, int B, int D, float w, int clamp,
+                      void* stream);
+
 /* VAE encoder (AutoencoderKL.encode, train_sdxl_zh.py:306-309; train_sd_zh.py:188-189) on the same op tape: cfg uses
  * in_channels (3), out_channels (2 * latent channels = 8), n_levels, block_out, layers_per_block, groups, eps.
  * The handle works with pea_unet_num_weights / weight_info / load_weight / init_random / memory / destroy (diffusers

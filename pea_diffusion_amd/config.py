@@ -360,3 +360,66 @@ def text_to_c(cfg) -> CTextConfig:
     c.proj_dim, c.eps, c.eos_id = cfg.projection_dim, cfg.layer_norm_eps, cfg.eos_token_id
     c.pos_offset = getattr(cfg, "position_offset", 0)
     return c
+
+
+# ---- CLIP vision towers (HF transformers CLIPVisionModelWithProjection): the image half of the CLIP pairs, for CLIPScore
+@dataclass
+class VisionConfig:
+    image_size: int = 224
+    patch_size: int = 14
+    hidden_size: int = 1024
+    num_attention_heads: int = 16
+    num_hidden_layers: int = 24
+    intermediate_size: int = 4096
+    hidden_act: str = "quick_gelu"          # "quick_gelu" | "gelu"
+    projection_dim: int = 768
+    layer_norm_eps: float = 1e-5
+    # the preprocessing that belongs to the checkpoint (OpenAI CLIP statistics; every tower below was trained with them)
+    image_mean: Tuple[float, float, float] = (0.48145466, 0.4578275, 0.40821073)
+    image_std: Tuple[float, float, float] = (0.26862954, 0.26130258, 0.27577711)
+    name: str = "clip_vit_l14"
+
+    @property
+    def num_tokens(self) -> int:
+        return (self.image_size // self.patch_size) ** 2 + 1
+
+
+def clip_vit_b32_config() -> VisionConfig:   # openai/clip-vit-base-patch32
+    return VisionConfig(patch_size=32, hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072,
+                        projection_dim=512, name="clip_vit_b32")
+
+
+def clip_vit_l14_config() -> VisionConfig:   # openai/clip-vit-large-patch14 (the image tower beside SDXL's text_encoder)
+    return VisionConfig()
+
+
+def clip_vit_h14_config() -> VisionConfig:
+    """ViT-H/14 (head_dim 80): the image tower of Chinese-CLIP ViT-H/14 and of xlm-roberta-large-ViT-H-14 (`mul_clip`), the
+    pairs the student text towers belong to"""
+    return VisionConfig(hidden_size=1280, num_attention_heads=16, num_hidden_layers=32, intermediate_size=5120,
+                        hidden_act="gelu", projection_dim=1024, name="clip_vit_h14")
+
+
+def tiny_vit_config() -> VisionConfig:       # 17 tokens, patch K = 588 -> 640 (padded)
+    return VisionConfig(image_size=56, patch_size=14, hidden_size=128, num_attention_heads=2, num_hidden_layers=2,
+                        intermediate_size=512, projection_dim=64, name="tiny_vit")
+
+
+def tiny_vit_h80_config() -> VisionConfig:   # head_dim 80 (the ViT-H/14 head width)
+    return VisionConfig(image_size=56, patch_size=14, hidden_size=320, num_attention_heads=4, num_hidden_layers=1,
+                        intermediate_size=320, hidden_act="gelu", projection_dim=64, name="tiny_vit_h80")
+
+
+class CVisionConfig(ctypes.Structure):
+    _fields_ = [("image_size", ctypes.c_int), ("patch_size", ctypes.c_int), ("width", ctypes.c_int), ("heads", ctypes.c_int),
+                ("layers", ctypes.c_int), ("intermediate", ctypes.c_int), ("act", ctypes.c_int), ("proj_dim", ctypes.c_int),
+                ("eps", ctypes.c_float)]
+
+
+def vision_to_c(cfg) -> CVisionConfig:
+    c = CVisionConfig()
+    c.image_size, c.patch_size, c.width = cfg.image_size, cfg.patch_size, cfg.hidden_size
+    c.heads, c.layers, c.intermediate = cfg.num_attention_heads, cfg.num_hidden_layers, cfg.intermediate_size
+    c.act = {"quick_gelu": 3, "gelu": 1}[cfg.hidden_act]
+    c.proj_dim, c.eps = cfg.projection_dim, cfg.layer_norm_eps
+    return c

@@ -45,6 +45,13 @@ struct PeaTextCfg {          // mirrors `pea_text_config` of include/pea_hip.h
   int rel_max_dist;          // T5: relative_attention_max_distance
 };
 
+struct PeaVisionCfg {        // mirrors `pea_vision_config` of include/pea_hip.h
+  int image_size, patch_size, width, heads, layers, intermediate;
+  int act;                   // GEMM epilogue activation of the MLP: 1 GELU(erf), 3 quick-GELU
+  int proj_dim;              // visual_projection width
+  float eps;
+};
+
 enum WKind { W_VEC, W_LINEAR, W_CONV3, W_CONV_IN, W_CONV_OUT };
 
 struct WSlot {
@@ -65,7 +72,7 @@ struct WSlot {
   int row_off = 0;
   int row_step = 1;          // > 1: this slot's rows are interleaved with its siblings' (T5 gated FF: wi_1 even, wi_0 odd)
   // head padding (heads whose width d is not a multiple of 64 are stored dp = 64*ceil(d/64) wide, zero filled)
-  int pad_mode = 0, pad_d = 0, pad_dp = 0;   // 1: rows (to_q/k/v), 2: columns (to_out), 3: GEGLU (h_i, gate_i) row interleave
+  int pad_mode = 0, pad_d = 0, pad_dp = 0;   // 1: rows (to_q/k/v; a W_VEC: the bias of such rows), 2: columns (to_out), 3: GEGLU (h_i, gate_i) row interleave
   int st_n = 0, st_k = 0;    // stored (padded) dims of a LINEAR weight
 };
 
@@ -106,7 +113,7 @@ struct Tn {
 };
 
 enum OpKind { OP_CONV_IN, OP_CONV3, OP_LINEAR, OP_GN, OP_LN, OP_ATTN, OP_GEGLU, OP_CONCAT, OP_SILU, OP_TEMB,
-              OP_CONV_OUT, OP_ADD, OP_ATTN_MAT, OP_EMBED, OP_GATHER_EOS };
+              OP_CONV_OUT, OP_ADD, OP_ATTN_MAT, OP_EMBED, OP_GATHER_EOS, OP_VIS_EMBED, OP_CLS_ROW };
 
 struct Op {
   int kind;
@@ -136,7 +143,7 @@ struct Tape {
   int B, H, W, L;                 // batch, latent H/W, context length
   bool needs_grad;
   int bwd_batch = 0;                 // > 0: backward() differentiates only the first bwd_batch samples (merged passes)
-  int graph = 0;                     // 0: UNet2DConditionModel, 1: AutoencoderKL encoder, 2: ControlNetModel, 3: AutoencoderKL decoder, 4: text encoder (1-4: inference only)
+  int graph = 0;                     // 0: UNet2DConditionModel, 1: AutoencoderKL encoder, 2: ControlNetModel, 3: AutoencoderKL decoder, 4: text encoder, 5: CLIP vision tower (1-5: inference only)
   std::vector<int> cn_out;           // ControlNet: output tensors (down residuals in diffusers order, mid last)
   int ce_begin = -1, ce_end = -1;    // ControlNet: op range of the conditioning embedding (constant over a generation)
   bool ce_valid = false;             // ... already computed for the current conditioning image
@@ -204,6 +211,9 @@ struct Tape {
   std::vector<int> hidden;           // graph 4: hidden_states[0..layers] tensor ids; t_final = final LN output, t_pooled
   int t_final = -1, t_pooled = -1;
   const long long* ids_in = nullptr;
+  int build_vision();
+  PeaVisionCfg vcfg{};               // graph 5: CLIP vision tower; hidden / t_final (last state, before post_layernorm) / t_pooled (image_embeds) as graph 4
+  int t_vrows = -1, t_vpool = -1;    // graph 5: patch rows [B*Np][Kpad] (written by launch_patchify), post_layernorm(h_N[:, 0]) = pooler_output
   int* kvlen = nullptr;              // graph 4 (BERT): per-sample valid token count
   float* rel_bias = nullptr;         // graph 4 (T5): [heads][L][64*ceil(L/64)] relative-position bias in the log2 domain
   int* rel_bucket = nullptr;         // ... |key - query| -> sub-bucket table [L]

@@ -88,8 +88,10 @@ struct Builder {
       const int w = padded ? lin(pfx[i] + ".weight", Ns[i], K, 1, (*pad_d)[i], (*pad_dp)[i]) : lin(pfx[i] + ".weight", Ns[i], K);
       u.slots[w].fused_parent = fi; u.slots[w].row_off = off;
       if (bias) {
-        const int b = vec(pfx[i] + ".bias", Ns[i]);
+        // the bias of zero-padded heads: the torch vector is heads * d long, its stored block heads * dp (pad entries zero)
+        const int b = vec(pfx[i] + ".bias", padded ? Ns[i] / (*pad_dp)[i] * (*pad_d)[i] : Ns[i]);
         u.slots[b].fused_parent = fi; u.slots[b].row_off = off;
+        if (padded) { u.slots[b].pad_mode = 1; u.slots[b].pad_d = (*pad_d)[i]; u.slots[b].pad_dp = (*pad_dp)[i]; }
       }
       off += Ns[i];
     }
@@ -542,6 +544,66 @@ int Tape::build_text_t5() {
   return PEA_OK;
 }
 
+// CLIP vision tower (HF transformers CLIPVisionModelWithProjection; keys `vision_model.*`, `visual_projection.weight`): the image
+// half of the CLIP pairs whose text half build_text() runs.  Patch rows [B*Np][Kpad] (launch_patchify: column order (c, py, px) =
+// the conv weight flattened, zero-padded from 3 P P to the GEMM's K tile) -> patch GEMM (no bias) -> class row + position add +
+// pre_layrnorm in one pass (launch_vision_embed) = hidden_states[0] -> pre-LN blocks with unmasked attention over Np + 1 tokens
+// -> pooler_output = post_layernorm(h_N[:, 0]) -> image_embeds = pooler_output @ visual_projection^T.  Head widths 64 (ViT-B/L)
+// and 80 (ViT-H/14, stored 128 wide zero-padded like the SD1.5 UNet's heads).
+int Tape::build_vision() {
+  const PeaVisionCfg& c = vcfg;
+  SHAPECHK(!needs_grad, "vision tower: inference graph only");
+  SHAPECHK(c.patch_size > 0 && c.image_size >= c.patch_size && c.image_size % c.patch_size == 0,
+           "vision tower: image %d / patch %d", c.image_size, c.patch_size);
+  SHAPECHK(c.heads > 0 && c.width > 0 && c.width % c.heads == 0, "vision tower: width %d / heads %d", c.width, c.heads);
+  const int d = c.width / c.heads, nd = (d + 63) / 64, dp = 64 * nd, Cp = c.heads * dp;
+  SHAPECHK(d == 64 || d == 80, "vision tower: head width %d (width %d / %d heads); 64 and 80 are supported", d, c.width, c.heads);
+  SHAPECHK(c.width % 64 == 0 && c.width <= 4096 && c.intermediate > 0 && c.intermediate % 64 == 0 && c.layers >= 1 &&
+           c.proj_dim > 0 && c.proj_dim % 4 == 0 && (c.act == 1 || c.act == 3), "vision tower: dims");
+  const int G = c.image_size / c.patch_size, Np = G * G, K = 3 * c.patch_size * c.patch_size, Kpad = (K + 63) / 64 * 64;
+  SHAPECHK(L == Np + 1 && B > 0, "vision tower: %d tokens for a %d x %d patch grid", L, G, G);
+  Builder bd(*this);
+  const bool padded = dp != d;
+  const int W = c.width;
+  const std::string vm = "vision_model.";
+  t_vrows = bd.T((long long)B * Np, Kpad, B, G, G);
+  const int pe = bd.linear(t_vrows, vm + "embeddings.patch_embedding", W, false, -1, Kpad != K ? 2 : 0, K, Kpad);
+  int x = bd.T((long long)B * L, W, B, 1, L);
+  {
+    const int cls = bd.vec(vm + "embeddings.class_embedding", W);
+    const int pos = bd.lin(vm + "embeddings.position_embedding.weight", L, W);
+    const int g = bd.vec(vm + "pre_layrnorm.weight", W), b = bd.vec(vm + "pre_layrnorm.bias", W);
+    Op& o = bd.push(OP_VIS_EMBED);
+    o.a = pe; o.out = x; o.w = cls; o.bias = pos; o.p0 = g; o.p1 = b; o.f0 = c.eps;     // (p0 / p1: weight slots, not tensors)
+  }
+  hidden.push_back(x);
+  const std::vector<int> vd3{d, d, d}, vdp3{dp, dp, dp};
+  for (int i = 0; i < c.layers; ++i) {
+    const std::string p = vm + "encoder.layers." + std::to_string(i);
+    const int n1 = bd.ln(x, p + ".layer_norm1", c.eps);
+    const int qkv = bd.fused_linear(n1, {p + ".self_attn.q_proj", p + ".self_attn.k_proj", p + ".self_attn.v_proj"}, {Cp, Cp, Cp}, true,
+                                    &vd3, &vdp3);
+    const int att = bd.T((long long)B * L, Cp, B, 1, L);
+    {
+      Op& o = bd.push(OP_ATTN);
+      o.a = qkv; o.acol = 0; o.b = qkv; o.bcol = Cp; o.c = qkv; o.ccol = 2 * Cp; o.out = att;
+      o.p0 = c.heads; o.p1 = L; o.p2 = L; o.p3 = nd; o.f0 = 1.0f / sqrtf((float)d);
+    }
+    x = bd.linear(att, p + ".self_attn.out_proj", W, true, x, padded ? 2 : 0, d, dp);
+    const int n2 = bd.ln(x, p + ".layer_norm2", c.eps);
+    const int f = bd.linear(n2, p + ".mlp.fc1", c.intermediate, true);
+    ops.back().p2 = c.act;
+    x = bd.linear(f, p + ".mlp.fc2", W, true, x);
+    hidden.push_back(x);
+  }
+  t_final = x;
+  const int cls = bd.T(B, W, B);
+  { Op& o = bd.push(OP_CLS_ROW); o.a = x; o.out = cls; }
+  t_vpool = bd.ln(cls, vm + "post_layernorm", c.eps);
+  t_pooled = bd.linear(t_vpool, "visual_projection", c.proj_dim, false);
+  return PEA_OK;
+}
+
 // the attention backward takes query counts in multiples of 4 (attention.hip, launch_attention_bwd): a training context whose
 // token grid breaks that (an SD1.5 mid block at a 56 x 104 latent: 7 x 13 = 91 tokens) is refused when it is created, not in its
 // first backward pass
@@ -555,6 +617,7 @@ int Tape::check_attn_bwd_tokens() const {
 
 int Tape::build() {
   if (graph == 4) return build_text();
+  if (graph == 5) return build_vision();
   if (graph == 1) return build_vae_encoder();
   if (graph == 3) return build_vae_decoder();
   normalize_depths(cfg);
@@ -1105,6 +1168,7 @@ int Tape::load_weight(const char* name, const float* src, long long numel, hipSt
   switch (w.kind) {
     case W_VEC:
       if (w.pad_mode == 3) { RC(launch_permute_geglu_vec(src, w.f32, (int)(numel / 2), s)); break; }
+      if (w.pad_mode == 1) { RC(launch_pad_head_vec(src, w.f32, (int)(numel / w.pad_d), w.pad_d, w.pad_dp, s)); break; }
       HIPCHK(hipMemcpyAsync(w.f32, src, numel * 4, hipMemcpyDeviceToDevice, s));
       break;
     case W_CONV_IN:
@@ -1368,6 +1432,15 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
                                o.c >= 0 ? slots[o.c].w : nullptr, out.d, B, L, out.cols, tcfg.vocab, s));
         break;
       }
+      case OP_VIS_EMBED: {
+        Tn& out = tn[o.out];
+        RC(launch_vision_embed(tn[o.a].d, slots[o.w].f32, slots[o.bias].w, slots[o.p0].f32, slots[o.p1].f32, out.d, B, L, out.cols,
+                               o.f0, s));
+        break;
+      }
+      case OP_CLS_ROW:
+        RC(launch_copy2d(tn[o.a].d, L * tn[o.a].cols, tn[o.out].d, tn[o.out].cols, B, tn[o.out].cols, 0, s));
+        break;
       case OP_GATHER_EOS:
         RC(launch_gather_eos(ids_in, tn[o.a].d, tn[o.out].d, B, L, tn[o.a].cols, tcfg.eos_id, s));
         break;

@@ -253,3 +253,27 @@ int launch_embed_tokens(const long long* ids, const bf16* tok, const bf16* pos, 
 int launch_t5_rel_bias(const float* rel, const int* dist_bucket, float* bias, int H, int L, int pitch, int half_buckets, hipStream_t s);
 int launch_gather_eos(const long long* ids, const bf16* x, bf16* out, int B, int L, int width, long long eos_id, hipStream_t s);
 int launch_kv_len(const long long* ids, int* len, int B, int L, long long pad_id, hipStream_t s);
+
+// ---------------------------------------------------------------- vision.hip: CLIP image tower front end and CLIPScore
+// Per-coordinate tap table of one axis of the antialiased bicubic resample (built on the host in float64): output coordinate
+// i reads source coordinates first[i] .. first[i] + count[i] - 1 with weights w[i * taps + k] (sum 1, zero past count[i]).
+struct ResampleAxis { const int* first; const int* count; const float* w; int taps; };
+struct PreprocessP {
+  const float* img; int B, H, W;           // fp32 [B][3][H][W]
+  float lo, range; int quantize;           // v = clamp((x - lo) / range, 0, 1); quantize: round(v * 255) / 255
+  ResampleAxis y, x;                       // `size` entries each: the centre crop is folded into the tables
+  int size;
+  int tile_h, tile_w, win_h, win_w;        // output tile of one workgroup; capacity of its source window (win_w % 4 == 0)
+  float mean[3], istd[3];
+  float* out;                              // fp32 [B][3][size][size]
+};
+int launch_preprocess(const PreprocessP& p, hipStream_t s);
+// normalised pixels fp32 [B][3][S][S] -> bf16 rows [B * (S/P)^2][kpad], column (c, py, px), columns >= 3 P P zero
+int launch_patchify(const float* pixels, bf16* rows, int B, int S, int P, int kpad, hipStream_t s);
+// x[b][0] = cls + pos[0], x[b][1 + i] = pe[b][i] + pos[1 + i] (fp32), y = LayerNorm(x) * gamma + beta (bf16); width % 8 == 0, <= 4096
+int launch_vision_embed(const bf16* pe, const float* cls, const bf16* pos, const float* gamma, const float* beta, bf16* y, int B,
+                        int L, int width, float eps, hipStream_t s);
+// dst[h * dp + j] = j < d ? src[h * d + j] : 0  (bias of zero-padded heads)
+int launch_pad_head_vec(const float* src, float* dst, int heads, int d, int dp, hipStream_t s);
+// out[b] = w * cos(img[b], txt[b]) (clamp: negative cosines -> 0); fp32 [B][D]
+int launch_clip_score(const float* img, const float* txt, float* out, int B, int D, float w, int clamp, hipStream_t s);

@@ -410,3 +410,14 @@ def lora_compose(acc, down, up, scale, out=None):
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == acc.numel()
     check(lib().pea_op_lora_compose(ptr(acc), ptr(down), ptr(up), ptr(out), M, Kf, r, float(scale), stream_ptr()))
     return out
+
+
+def clip_score(image_embeds, text_embeds, w=2.5, clamp=True):
+    """CLIPScore (Hessel et al. 2021) per pair (pea_op_clip_score): w * max(cos(image_embeds[b], text_embeds[b]), 0), fp32
+    [B,D] -> fp32 [B]; `w=1, clamp=False` is the plain cosine.  One wave per pair, fixed reduction order (bit-reproducible)."""
+    assert image_embeds.shape == text_embeds.shape and image_embeds.dim() == 2
+    a = image_embeds.detach().to(torch.float32).contiguous()
+    t = text_embeds.detach().to(device=a.device, dtype=torch.float32).contiguous()
+    out = torch.empty(a.shape[0], device=a.device, dtype=torch.float32)
+    check(lib().pea_op_clip_score(ptr(a), ptr(t), ptr(out), a.shape[0], a.shape[1], float(w), int(bool(clamp)), stream_ptr()))
+    return out
