@@ -3,7 +3,7 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this file.
 
 The HIP path keeps every activation tensor AND every gradient tensor in bf16 between kernels (fp32 only inside a kernel:
-MFMA accumulators, epilogue arithmetic, statistics; pea_diffusion_amd/csrc/model.hip).  The plain
+MFMA accumulators, epilogue arithmetic, statistics; pea_diffusion_amd/csrc/tape.hip).  The plain
 oracle runs in fp32 throughout, so an end-to-end comparison against it carries the bf16 storage noise of ~900 chained ops
 (measured 6-8e-3 relative L2) and cannot see a defect smaller than that.  Inside `with bf16_storage():` the restatements
 round a tensor to bf16 wherever the product stores one -- forward value and, through autograd, the gradient that flows back

@@ -14,30 +14,20 @@ import torch
 
 from . import config as _cfg
 from ._lib import PeaError, check, lib, ptr, stream_ptr
+from .tape import HipTape
 from .unet import HipUNet, _Config
 
 
-class HipControlNet:
+class HipControlNet(HipTape):
     def __init__(self, cfg, batch: int, height: Optional[int] = None, width: Optional[int] = None, ctx_len: int = 77):
-        if not torch.cuda.is_available():
-            raise PeaError("HipControlNet needs a MI355X (no CPU fallback)")
+        self._open()
         self.cfg, self.config = cfg, _Config(cfg)
         self.B, self.H, self.W, self.L = batch, height or cfg.sample_size, width or cfg.sample_size, ctx_len
         self.in_channels = cfg.in_channels
         self.dtype = torch.bfloat16
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self._h = ctypes.c_void_p()
         c = _cfg.to_c(cfg)
         check(lib().pea_controlnet_create(ctypes.byref(c), self.B, self.H, self.W, self.L, ctypes.byref(self._h)))
         self._cond_ref, self._cond_version = None, None
-
-    __del__ = HipUNet.__del__
-    weight_table = HipUNet.weight_table
-    load_state_dict = HipUNet.load_state_dict
-    memory = HipUNet.memory
-
-    def init_random(self, seed: int = 0):
-        check(lib().pea_unet_init_random(self._h, seed, stream_ptr()))
 
     def output_shapes(self):
         out = []

@@ -105,7 +105,7 @@ int launch_gelu_bwd(const bf16* x, const bf16* dy, bf16* dx, long long n, int ac
 }
 
 // ---- concat / split along the channel (last) dimension
-// Depth-to-space storage of an upsampler output (the sub-pixel form of the upsample-folded conv, model.hip OP_CONV3 p1 == 2):
+// Depth-to-space storage of an upsampler output (the sub-pixel form of the upsample-folded conv, tape.hip OP_CONV3 p1 == 2):
 // [B][H/2][W/2][4 = (y & 1) * 2 + (x & 1)][C] instead of [B][H][W][C].  Seen as rows of C elements, full-resolution pixel row r
 // lives at row d2s_row(r).  The first operand of concat2 / split2 may be stored that way (H, W = the full resolution; 0 = plain).
 __device__ __forceinline__ long long d2s_row(long long r, int H, int W) {

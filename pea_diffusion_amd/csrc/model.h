@@ -1,14 +1,27 @@
 // Host runtime: the UNet as a static op tape (forward schedule + reverse data-gradient
 // schedule), the PEA adapter, and the fused KD training step.  No autograd, no tracing compiler:
 // the tape is built once per (config, batch, resolution, context length) and every launch is an
-// explicit kernel from pea_kernels.h.
+// explicit kernel from pea_kernels.h.  graph.hip builds the tapes, tape.hip allocates, loads and runs them, adapter.hip and
+// trainer.hip hold the PEA adapter and the KD step; api_model.hip / vision.hip are the C ABI over them.
 #pragma once
+#include <string.h>
+
 #include <deque>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "pea_kernels.h"
+
+#define RC(x)                \
+  do {                       \
+    int rc__ = (x);          \
+    if (rc__ != PEA_OK) return rc__; \
+  } while (0)
+
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline void fill_gemm(GemmP& p) { memset(&p, 0, sizeof(p)); p.alpha = 1.f; p.rows_per_batch = 1; }
+int pea_zero_page(const bf16** out);
 
 struct PeaUnetCfg {          // mirrors `pea_unet_config` of include/pea_hip.h
   int in_channels, out_channels;
@@ -308,7 +321,13 @@ struct Trainer {
   int* tmap_d = nullptr;                // device int[B]: teacher row of sample b (relative to the first teacher row) or -1
   std::vector<int> tmap_h;              // host copy of the last step's map, one entry per sample (export)
   bf16* tpool_c = nullptr;              // [B][pooled] bf16: teacher pooled embeds of all samples, before compaction
+  int new_context(int rows, Tape** out);   // weight-sharing merged-pass tape of `rows` samples differentiating the first B; deleted on failure
   int context_for(int nt, Tape** out);
+  // shared tail of step / step_merged: KD loss + gradient seeds over the taps of S (teacher taps: those of *Tt, or with Tt
+  // null the rows of the same tensors behind the B student samples), backward of S, adapter backward
+  int loss_and_backward(Tape& S, const Tape* Tt, const float* eps_student, const float* eps_teacher, const float* noise,
+                        const long long* zh, const unsigned char* prompt_mask, long long per_stok, long long per_tok,
+                        const int* tmap, float grad_scale, float* grads, int accumulate, float* losses_out, hipStream_t s);
   float *xt2 = nullptr, *eps2 = nullptr, *t2 = nullptr, *tid2 = nullptr;
   int step_merged(const float* latents, const float* noise, const long long* timesteps, const float* enc,
                   const float* enc_uncond, const unsigned char* prompt_mask, const long long* zh, const float* teacher_ehs,

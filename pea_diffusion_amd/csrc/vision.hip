@@ -9,7 +9,7 @@
 //   patchify_kernel     normalised pixels -> bf16 patch rows in the GEMM's A layout (K zero-padded to the K tile)
 //   vision_embed_kernel class row + position add + pre_layrnorm in one pass over [B][Np + 1][width]
 //   clip_score_kernel   w * max(cos(image, text), 0), one wave per pair, fixed-order fp32 reduction (bit-reproducible)
-// and the C ABI of the vision tower (Tape::build_vision, model.hip).  No atomics anywhere; explicit fmaf as in sampler.hip.
+// and the C ABI of the vision tower (Tape::build_vision, graph.hip).  No atomics anywhere; explicit fmaf as in sampler.hip.
 #include <string.h>
 
 #include "../../include/pea_hip.h"

@@ -16,7 +16,7 @@ import torch
 
 from . import config as _cfg
 from ._lib import PeaError, check, lib, ptr, stream_ptr
-from .unet import HipUNet
+from .tape import HipTape
 
 
 class _HiddenStates:
@@ -39,21 +39,14 @@ class _Output:
         return (self.text_embeds if self.text_embeds is not None else self.last_hidden_state, self.last_hidden_state)[i]
 
 
-class HipTextEncoder:
+class HipTextEncoder(HipTape):
     def __init__(self, cfg, batch: int, ctx_len: Optional[int] = None):
-        if not torch.cuda.is_available():
-            raise PeaError("HipTextEncoder needs a MI355X (no CPU fallback)")
+        self._open()
         self.cfg, self.config = cfg, cfg
         self.B, self.L = batch, ctx_len or cfg.max_position_embeddings
-        self.device = torch.device("cuda", torch.cuda.current_device())
         self.dtype = torch.bfloat16
-        self._h = ctypes.c_void_p()
         c = _cfg.text_to_c(cfg)
         check(lib().pea_text_create(ctypes.byref(c), self.B, self.L, ctypes.byref(self._h)))
-
-    __del__ = HipUNet.__del__
-    weight_table = HipUNet.weight_table
-    memory = HipUNet.memory
 
     @property
     def encoder(self):
@@ -71,10 +64,7 @@ class HipTextEncoder:
                 k2 = "shared.weight"
             if k2 in table:
                 fixed[k2] = v[: table[k2][0]] if (k2.endswith("position_embeddings.weight") or k2.endswith("token_type_embeddings.weight")) and v.shape[0] > table[k2][0] else v
-        return HipUNet.load_state_dict(self, fixed, strict)
-
-    def init_random(self, seed: int = 0):
-        check(lib().pea_unet_init_random(self._h, seed, stream_ptr()))
+        return super().load_state_dict(fixed, strict)
 
     def encode(self, input_ids, hidden_index: int = -2):
         """-> (hidden fp32 [B, L, width], pooled fp32 [B, proj] or None).  hidden_index: -1 last state (CLIP: after the

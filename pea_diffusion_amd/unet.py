@@ -12,6 +12,7 @@ import torch
 
 from . import config as _cfg
 from ._lib import PeaError, check, lib, ptr, stream_ptr
+from .tape import HipTape, _staged
 
 
 class _HookHandle:
@@ -41,31 +42,17 @@ class _Config:
         self.__dict__.update(cfg.__dict__)
 
 
-def _staged(device, k, shape, t):
-    """weight `k` of a state dict as contiguous fp32 on the device, size-checked against the table's shape (a free function:
-    HipControlNet, the VAE and the text encoders borrow `HipUNet.load_state_dict` unbound)"""
-    n = 1
-    for s in shape:
-        n *= s
-    if t.numel() != n:
-        raise PeaError(f"load_state_dict: {k} has shape {tuple(t.shape)}, expected {shape} (or 1x1 conv)")
-    return t.detach().to(device=device, dtype=torch.float32).contiguous()
-
-
-class HipUNet:
+class HipUNet(HipTape):
     def __init__(self, cfg, batch: int, height: Optional[int] = None, width: Optional[int] = None, ctx_len: int = 77,
                  needs_grad: bool = False, share_weights_from: Optional["HipUNet"] = None,
                  residual_inputs: bool = False, inpaint_inputs: bool = False):
-        if not torch.cuda.is_available():
-            raise PeaError("HipUNet needs a MI355X (no CPU fallback)")
+        self._open()
         self.cfg = cfg
         self.config = _Config(cfg)
         self.in_channels = cfg.in_channels
         self.B, self.H, self.W, self.L = batch, height or cfg.sample_size, width or cfg.sample_size, ctx_len
         self.needs_grad = needs_grad
         self.dtype = torch.bfloat16
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self._h = ctypes.c_void_p()
         c = _cfg.to_c(cfg)
         self.residual_inputs = residual_inputs
         self.inpaint_inputs = inpaint_inputs
@@ -90,51 +77,10 @@ class HipUNet:
         self.mid_block = _BlockShim("m", idx["m"], False) if "m" in idx else None
         self.up_blocks = [_BlockShim(f"u{i}", idx[f"u{i}"], False) for i in range(n)]
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                lib().pea_unet_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
-
     def release_activations(self):
         """free the activation / gradient arenas (weights stay); the next forward allocates them again"""
         check(lib().pea_unet_release_activations(self._h))
         self._tcond = None             # the context's conditioning input comes back zeroed
-
-    # ---------------------------------------------------------------- weights
-    def weight_table(self) -> Dict[str, tuple]:
-        """{diffusers key: torch shape}"""
-        out = {}
-        name = ctypes.create_string_buffer(256)
-        numel, kind, d0, d1 = ctypes.c_longlong(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        for i in range(lib().pea_unet_num_weights(self._h)):
-            check(lib().pea_unet_weight_info(self._h, i, name, 256, ctypes.byref(numel), ctypes.byref(kind),
-                                             ctypes.byref(d0), ctypes.byref(d1)))
-            k = kind.value
-            if k == 0:
-                shape = (d0.value,)
-            elif k == 1:
-                shape = (d0.value, d1.value)
-            else:
-                shape = (d0.value, d1.value, 3, 3)
-            out[name.value.decode()] = shape
-        return out
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        table = self.weight_table()
-        missing = [k for k in table if k not in sd]
-        unexpected = [k for k in sd if k not in table]
-        if strict and (missing or unexpected):
-            raise PeaError(f"load_state_dict: missing={missing[:5]} unexpected={unexpected[:5]}")
-        for k, shape in table.items():
-            if k not in sd:
-                continue
-            t = _staged(self.device, k, shape, sd[k])
-            check(lib().pea_unet_load_weight(self._h, k.encode(), ptr(t), t.numel(), stream_ptr()))
-        torch.cuda.current_stream().synchronize()      # staging tensors above are freed after this call
-        return missing, unexpected
 
     # ---------------------------------------------------------------- LoRA
     _fused: tuple = ()         # keys currently loaded as base + LoRA
@@ -192,14 +138,6 @@ class HipUNet:
         torch.cuda.current_stream().synchronize()
         restored, self._fused = list(self._fused), ()
         return restored
-
-    def init_random(self, seed: int = 0):
-        check(lib().pea_unet_init_random(self._h, seed, stream_ptr()))
-
-    def memory(self):
-        w, a, g, n = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int()
-        check(lib().pea_unet_memory(self._h, ctypes.byref(w), ctypes.byref(a), ctypes.byref(g), ctypes.byref(n)))
-        return {"weight_bytes": w.value, "activation_bytes": a.value, "grad_bytes": g.value, "n_ops": n.value}
 
     # ---------------------------------------------------------------- forward
     def __call__(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, cross_attention_kwargs=None,

@@ -14,7 +14,7 @@ import torch
 
 from . import config as _cfg
 from ._lib import PeaError, check, lib, ptr, stream_ptr
-from .unet import HipUNet
+from .tape import HipTape
 
 
 class DiagonalGaussian:
@@ -51,24 +51,17 @@ class _Cfg:
         self.__dict__.update(cfg.__dict__)
 
 
-class HipVAEEncoder:
+class HipVAEEncoder(HipTape):
     def __init__(self, cfg, batch: int, height: Optional[int] = None, width: Optional[int] = None):
-        if not torch.cuda.is_available():
-            raise PeaError("HipVAEEncoder needs a MI355X (no CPU fallback)")
+        self._open()
         self.cfg, self.config = cfg, _Cfg(cfg)
         self.B, self.H, self.W = batch, height or cfg.sample_size, width or cfg.sample_size
-        self.device = torch.device("cuda", torch.cuda.current_device())
         self.dtype = torch.float32
-        self._h = ctypes.c_void_p()
         c = _cfg.vae_to_c(cfg)
         check(lib().pea_vae_encoder_create(ctypes.byref(c), self.B, self.H, self.W, ctypes.byref(self._h)))
         C, h, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(lib().pea_vae_latent_shape(self._h, ctypes.byref(C), ctypes.byref(h), ctypes.byref(w)))
         self.latent_shape = (self.B, C.value, h.value, w.value)
-
-    __del__ = HipUNet.__del__
-    weight_table = HipUNet.weight_table
-    memory = HipUNet.memory
 
     def to(self, *a, **k):          # `self.vae.to(dtype=torch.float32)` (train_sdxl_zh.py:307) is a no-op here
         return self
@@ -77,10 +70,7 @@ class HipVAEEncoder:
         """accepts a full AutoencoderKL state dict: `decoder.*` / `post_quant_conv.*` entries are not part of the
         encode path and are skipped"""
         sd = {k: v for k, v in sd.items() if not (k.startswith("decoder.") or k.startswith("post_quant_conv."))}
-        return HipUNet.load_state_dict(self, sd, strict)
-
-    def init_random(self, seed: int = 0):
-        check(lib().pea_unet_init_random(self._h, seed, stream_ptr()))
+        return super().load_state_dict(sd, strict)
 
     # ------------------------------------------------------------------ encode
     def _pixels(self, x):
@@ -112,37 +102,27 @@ class HipVAEEncoder:
         return out
 
 
-class HipVAEDecoder:
+class HipVAEDecoder(HipTape):
     """`image = self.vae.decode(latents / self.vae.config.scaling_factor, return_dict=False)[0]`
     (tests/test_sdxl_zh.py:430; tests/test_sdxl_zh_controlnet.py:575) on the HIP tape.  Built for a LATENT size;
     weights by the AutoencoderKL keys `decoder.*`, `post_quant_conv.*` (encoder keys of a full checkpoint are skipped)."""
 
     def __init__(self, cfg, batch: int, latent_height: Optional[int] = None, latent_width: Optional[int] = None):
-        if not torch.cuda.is_available():
-            raise PeaError("HipVAEDecoder needs a MI355X (no CPU fallback)")
+        self._open()
         self.cfg, self.config = cfg, _Cfg(cfg)
         f = 2 ** (len(cfg.block_out_channels) - 1)
         self.B, self.h, self.w = batch, latent_height or cfg.sample_size // f, latent_width or cfg.sample_size // f
         self.scale_factor = f
-        self.device = torch.device("cuda", torch.cuda.current_device())
         self.dtype = torch.float32
-        self._h = ctypes.c_void_p()
         c = _cfg.vae_decoder_to_c(cfg)
         check(lib().pea_vae_decoder_create(ctypes.byref(c), self.B, self.h, self.w, ctypes.byref(self._h)))
-
-    __del__ = HipUNet.__del__
-    weight_table = HipUNet.weight_table
-    memory = HipUNet.memory
 
     def to(self, *a, **k):
         return self
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         sd = {k: v for k, v in sd.items() if not (k.startswith("encoder.") or k.startswith("quant_conv."))}
-        return HipUNet.load_state_dict(self, sd, strict)
-
-    def init_random(self, seed: int = 0):
-        check(lib().pea_unet_init_random(self._h, seed, stream_ptr()))
+        return super().load_state_dict(sd, strict)
 
     def decode(self, z, return_dict: bool = False, inv_scaling: float = 1.0):
         """z: [B, 4, h, w] (already divided by the scaling factor, as the reference passes it; or pass the raw latents

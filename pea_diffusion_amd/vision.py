@@ -21,7 +21,7 @@ import torch
 from . import config as _cfg
 from . import ops as _ops
 from ._lib import PeaError, check, lib, ptr, stream_ptr
-from .unet import HipUNet
+from .tape import HipTape
 
 
 # ---------------------------------------------------------------- resampling tables (host, float64)
@@ -175,25 +175,16 @@ class _Output:
         self.hidden_states = _HiddenStates(enc, pixels)
 
 
-class HipImageEncoder:
+class HipImageEncoder(HipTape):
+    """`load_state_dict` is strict by default; strict=False skips a full CLIP checkpoint's `text_model.*`, `logit_scale`"""
+
     def __init__(self, cfg, batch: int):
-        if not torch.cuda.is_available():
-            raise PeaError("HipImageEncoder needs a MI355X (no CPU fallback)")
+        self._open()
         self.cfg, self.config = cfg, cfg
         self.B, self.L = batch, cfg.num_tokens
-        self.device = torch.device("cuda", torch.cuda.current_device())
         self.dtype = torch.bfloat16
-        self._h = ctypes.c_void_p()
         c = _cfg.vision_to_c(cfg)
         check(lib().pea_vision_create(ctypes.byref(c), self.B, ctypes.byref(self._h)))
-
-    __del__ = HipUNet.__del__
-    weight_table = HipUNet.weight_table
-    memory = HipUNet.memory
-    load_state_dict = HipUNet.load_state_dict      # strict by default; strict=False skips a full CLIP checkpoint's `text_model.*`, `logit_scale`
-
-    def init_random(self, seed: int = 0):
-        check(lib().pea_unet_init_random(self._h, seed, stream_ptr()))
 
     def encode(self, pixels, hidden_index: int = -1):
         """pixels fp32 [B,3,S,S] (normalised: `preprocess`) -> (hidden fp32 [B, Np+1, width], pooler_output fp32 [B, width],

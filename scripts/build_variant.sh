@@ -8,7 +8,7 @@ FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-inline
 [ "$UNIT" = attention ] && FLAGS="$FLAGS -fno-honor-nans -fno-slp-vectorize"
 hipcc $FLAGS $EXTRA -c $UNIT.hip -o /tmp/${UNIT}_${TAG}.o
 OBJS=""
-for o in gemm norm elementwise kdloss attention sampler prof comm api_ops model api_model; do
+for o in gemm norm elementwise kdloss attention sampler lora prof comm api_ops graph tape adapter trainer api_model vision; do
   if [ "$o" = "$UNIT" ]; then OBJS="$OBJS /tmp/${UNIT}_${TAG}.o"; else OBJS="$OBJS $o.o"; fi
 done
 hipcc --offload-arch=gfx950 -shared -fPIC -o ../libpea_hip_${TAG}.so $OBJS -ldl

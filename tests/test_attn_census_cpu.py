@@ -1,5 +1,5 @@
 """CPU (no device): every attention op of every UNet graph the product builds is fed a PRESCALED Q (the producing projection's
-epilogue multiplied its Q block by softmax_scale * log2 e from the fp32 accumulator -- csrc/model.hip:Tape::tag_q_prescale).
+epilogue multiplied its Q block by softmax_scale * log2 e from the fp32 accumulator -- csrc/graph.hip:Tape::tag_q_prescale).
 An untagged op would silently run the operator-level plain-Q path of csrc/attention.hip, which rounds the scaled operand to
 bf16 once more (round-3 advisor finding): the planning pass of the C ABI reports the census, asserted here for the BASELINE
 configurations; the GPU tests assert it on the live handles of the VAE / ControlNet / text-encoder graphs as well."""

@@ -417,7 +417,7 @@ def test_ln_linear_offsets(ops, variant):
 # ------------------------------------------------------------------------------------ attention
 def kv_stack(cfg):
     """(column offset, padded width Cp) of every cross-attention layer's K block in the stacked K|V projection, in the order
-    model.hip builds them (down blocks, mid block, up blocks; K at kv_off, V at kv_off + Cp), and the stack's width"""
+    graph.hip builds them (down blocks, mid block, up blocks; K at kv_off, V at kv_off + Cp), and the stack's width"""
     from pea_diffusion_amd.config import depth_tables
     down, up, mid = depth_tables(cfg)
     n = len(cfg.block_out_channels)
