@@ -21,6 +21,15 @@
 // both orientations on specialised waves), xattn_bwd_kernel (round 3: any key count up to 128), each with an ordered
 // fp32 split reduce over query ranges (attn_dkv_reduce_kernel).  Every output tile (O, dQ, dK, dV) leaves through a
 // per-wave LDS image as whole 128-byte rows.
+// The three backward cross-attention kernels take their per-workgroup context (unit range, operand rows of the head, key
+// count, score factor) from xattn_ctx.  They still repeat, as text: K / V staging, the unit stage (stage_unit / fetch_o /
+// unit_head), the key-on-the-lane task, the query-on-the-lane key-block step, and the dQ and dK / dV exits -- so a fix to
+// one copy has to be carried to the others by hand.  Each of these was tried as a shared __forceinline__ helper; the table
+// in profiles/EXPERIMENTS.md ("Cross-attention backward: one launcher, one context helper") says per piece whether it
+// moved register counts (not wanted) or only the instruction order (open: needs a bit-identity and timing A/B on a GPU).
+// Host side (bottom of the file): launch_lds raises a kernel's dynamic-LDS limit once and launches it; launch_xattn_fwd /
+// launch_xattn_bwd1 / launch_xattn_bwd23 map the run-time (key blocks, prescaled Q) to the instantiation;
+// launch_dkv_reduce is the ordered split reduce behind any backward that wrote partials.
 #include <stdlib.h>
 
 #include "pea_kernels.h"
@@ -912,6 +921,32 @@ __global__ __launch_bounds__(256, (ND == 1 ? 2 : 1)) void attn_bwd_fused_kernel(
 // Q fragments straight from HBM (this lane's query row: four 16-byte loads), S^T over KB key blocks, the softmax in one
 // shot (all scores of a query are in registers: no running max, no rescale), O^T = V^T P^T, store.  Per-sample key counts
 // (merged passes with a shorter student context) mask through the same compare as the padding keys.
+// What a cross-attention workgroup knows about its (split, batch, head): its run of UQ-query units, the rows of that head in
+// every operand, the sample's key count, and the factor c that takes a score into the log2 domain (1 when Q arrives
+// prescaled).  PRE: 1 / 0 where the instantiation knows whether Q is prescaled, -1: AttnP::q_prescaled decides at run time.
+struct XattnCtx {
+  int split, head, b, u_begin, u_end, skv_b;
+  float c;
+  const bf16 *Qb, *dOb, *Ob, *Kb, *Vb;
+  const float* lseb;
+};
+template <int UQ, int PRE = -1>
+__device__ __forceinline__ XattnCtx xattn_ctx(const AttnP& p, int upw) {
+  XattnCtx x;
+  attn_block_coords(x.split, x.head, x.b);
+  const int nu = (p.Sq + UQ - 1) >> (UQ == 128 ? 7 : 6);         // a shift, not a division: Sq is signed
+  x.u_begin = x.split * upw;
+  x.u_end = min(nu, x.u_begin + upw);
+  x.c = (PRE < 0 ? p.q_prescaled != 0 : PRE != 0) ? 1.f : p.scale * LOG2E;
+  x.Qb = p.Q + (long long)x.b * p.Sq * p.ldq + x.head * 64;
+  x.dOb = p.dO + (long long)x.b * p.Sq * p.lddo + x.head * 64;
+  x.Ob = p.O + (long long)x.b * p.Sq * p.ldo + x.head * 64;
+  x.Kb = p.K + (long long)x.b * p.Skv * p.ldk + x.head * 64;
+  x.Vb = p.V + (long long)x.b * p.Skv * p.ldv + x.head * 64;
+  x.lseb = p.lse + ((long long)x.b * p.H + x.head) * p.Sq;
+  x.skv_b = __builtin_amdgcn_readfirstlane(p.kv_len ? p.kv_len[x.b] : p.Skv);
+  return x;
+}
 __device__ __forceinline__ float xhalf_sum(float x) {
   float a = x, b = x;
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
@@ -1084,20 +1119,11 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd_kernel(const AttnP p, int up
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
-  int split, head, b;
-  attn_block_coords(split, head, b);
-  const int nu = (p.Sq + 127) >> 7;
-  const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
-  const float c = p.q_prescaled ? 1.f : p.scale * LOG2E;         // prescaled Q: the scores are in the log2 domain already
-  const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq + head * 64;
-  const bf16* dOb = p.dO + (long long)b * p.Sq * p.lddo + head * 64;
-  const bf16* Ob = p.O + (long long)b * p.Sq * p.ldo + head * 64;
-  const bf16* Kb = p.K + (long long)b * p.Skv * p.ldk + head * 64;
-  const bf16* Vb = p.V + (long long)b * p.Skv * p.ldv + head * 64;
-  const float* lseb = p.lse + ((long long)b * p.H + head) * p.Sq;
-  const int skv_b = __builtin_amdgcn_readfirstlane(p.kv_len ? p.kv_len[b] : p.Skv);
+  const XattnCtx x = xattn_ctx<128>(p, upw);
+  const int head = x.head, b = x.b, u_begin = x.u_begin, u_end = x.u_end, skv_b = x.skv_b;
+  const float c = x.c;
 
-  const TileSrc qsrc = tile_src(Qb, p.ldq, p.Sq, wave, lane), dosrc = tile_src(dOb, p.lddo, p.Sq, wave, lane);
+  const TileSrc qsrc = tile_src(x.Qb, p.ldq, p.Sq, wave, lane), dosrc = tile_src(x.dOb, p.lddo, p.Sq, wave, lane);
   auto stage_unit = [&](int u) {
     const int r0 = u * 128;
     stage_tile(qsrc, r0, S0, wave);
@@ -1107,7 +1133,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd_kernel(const AttnP p, int up
     if (wave < 2) {
       int r = r0 + wave * 64 + lane;
       r = r < p.Sq ? r : p.Sq - 1;
-      lds_dma4(lseb + r, S0 + 4 * TILE_BYTES + wave * 256);
+      lds_dma4(x.lseb + r, S0 + 4 * TILE_BYTES + wave * 256);
     }
   };
   // delta: thread = (query of the unit, half of the head dimension); its O values are fetched together with the stage
@@ -1117,11 +1143,11 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd_kernel(const AttnP p, int up
     int r = u * 128 + dq_l;
     r = r < p.Sq ? r : p.Sq - 1;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) o_pf[i] = *(const bf16x8*)(Ob + (long long)r * p.ldo + dhalf * 32 + 8 * i);
+    for (int i = 0; i < 4; ++i) o_pf[i] = *(const bf16x8*)(x.Ob + (long long)r * p.ldo + dhalf * 32 + 8 * i);
   };
 
   {
-    const TileSrc ksrc = tile_src(Kb, p.ldk, p.Skv, wave, lane), vsrc = tile_src(Vb, p.ldv, p.Skv, wave, lane);
+    const TileSrc ksrc = tile_src(x.Kb, p.ldk, p.Skv, wave, lane), vsrc = tile_src(x.Vb, p.ldv, p.Skv, wave, lane);
     stage_tile(ksrc, 0, Ksm, wave);
     stage_tile(vsrc, 0, Vsm, wave);
     if (KB > 2) {
@@ -1328,7 +1354,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd_kernel(const AttnP p, int up
 #pragma unroll
     for (int r = 0; r < 16; ++r) dk[i][r] *= p.q_prescaled ? 0.6931471805599453f : p.scale;
   if (p.nsplit > 1) {
-    float* pr = p.dkv_part + ((((long long)split * p.B + b) * p.H + head) * p.Skv + krow) * 128;
+    float* pr = p.dkv_part + ((((long long)x.split * p.B + b) * p.H + head) * p.Skv + krow) * 128;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -1391,20 +1417,11 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd2_kernel(const AttnP p, int u
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
-  int split, head, b;
-  attn_block_coords(split, head, b);
-  const int nu = (p.Sq + 63) >> 6;
-  const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
-  const float c = PRE ? 1.f : p.scale * LOG2E;
-  const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq + head * 64;
-  const bf16* dOb = p.dO + (long long)b * p.Sq * p.lddo + head * 64;
-  const bf16* Ob = p.O + (long long)b * p.Sq * p.ldo + head * 64;
-  const bf16* Kb = p.K + (long long)b * p.Skv * p.ldk + head * 64;
-  const bf16* Vb = p.V + (long long)b * p.Skv * p.ldv + head * 64;
-  const float* lseb = p.lse + ((long long)b * p.H + head) * p.Sq;
-  const int skv_b = __builtin_amdgcn_readfirstlane(p.kv_len ? p.kv_len[b] : p.Skv);
+  const XattnCtx x = xattn_ctx<64, PRE>(p, upw);
+  const int head = x.head, b = x.b, u_begin = x.u_begin, u_end = x.u_end, skv_b = x.skv_b;
+  const float c = x.c;
 
-  const TileSrc qsrc = tile_src(Qb, p.ldq, p.Sq, wave, lane), dosrc = tile_src(dOb, p.lddo, p.Sq, wave, lane);
+  const TileSrc qsrc = tile_src(x.Qb, p.ldq, p.Sq, wave, lane), dosrc = tile_src(x.dOb, p.lddo, p.Sq, wave, lane);
   auto stage_unit = [&](int u, int st) {
     char* const S0 = St + st * STG;
     const int r0 = u * 64;
@@ -1413,7 +1430,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd2_kernel(const AttnP p, int u
     if (wave == 0) {
       int r = r0 + lane;
       r = r < p.Sq ? r : p.Sq - 1;
-      lds_dma4(lseb + r, S0 + 2 * TILE_BYTES);
+      lds_dma4(x.lseb + r, S0 + 2 * TILE_BYTES);
     }
   };
   // delta = rowsum(dO * O): thread = (query of the unit, quarter of the head dimension); O fetched one unit ahead
@@ -1423,10 +1440,10 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd2_kernel(const AttnP p, int u
     int r = u * 64 + dq_l;
     r = r < p.Sq ? r : p.Sq - 1;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) o_pf[i] = *(const bf16x8*)(Ob + (long long)r * p.ldo + dqt * 16 + 8 * i);
+    for (int i = 0; i < 2; ++i) o_pf[i] = *(const bf16x8*)(x.Ob + (long long)r * p.ldo + dqt * 16 + 8 * i);
   };
   {
-    const TileSrc ksrc = tile_src(Kb, p.ldk, p.Skv, wave, lane), vsrc = tile_src(Vb, p.ldv, p.Skv, wave, lane);
+    const TileSrc ksrc = tile_src(x.Kb, p.ldk, p.Skv, wave, lane), vsrc = tile_src(x.Vb, p.ldv, p.Skv, wave, lane);
     stage_tile(ksrc, 0, Ksm, wave);
     stage_tile(vsrc, 0, Vsm, wave);
     if (KB > 2) {
@@ -1703,7 +1720,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd2_kernel(const AttnP p, int u
     const int krow = kb * 32 + frow;
     if (krow >= p.Skv) continue;
     if (p.nsplit > 1) {
-      float* pr = p.dkv_part + ((((long long)split * p.B + b) * p.H + head) * p.Skv + krow) * 128;
+      float* pr = p.dkv_part + ((((long long)x.split * p.B + b) * p.H + head) * p.Skv + krow) * 128;
 #pragma unroll
       for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -1765,20 +1782,11 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd3_kernel(const AttnP p, int u
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
-  int split, head, b;
-  attn_block_coords(split, head, b);
-  const int nu = (p.Sq + 63) >> 6;
-  const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
-  const float c = PRE ? 1.f : p.scale * LOG2E;
-  const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq + head * 64;
-  const bf16* dOb = p.dO + (long long)b * p.Sq * p.lddo + head * 64;
-  const bf16* Ob = p.O + (long long)b * p.Sq * p.ldo + head * 64;
-  const bf16* Kb = p.K + (long long)b * p.Skv * p.ldk + head * 64;
-  const bf16* Vb = p.V + (long long)b * p.Skv * p.ldv + head * 64;
-  const float* lseb = p.lse + ((long long)b * p.H + head) * p.Sq;
-  const int skv_b = __builtin_amdgcn_readfirstlane(p.kv_len ? p.kv_len[b] : p.Skv);
+  const XattnCtx x = xattn_ctx<64, PRE>(p, upw);
+  const int head = x.head, b = x.b, u_begin = x.u_begin, u_end = x.u_end, skv_b = x.skv_b;
+  const float c = x.c;
 
-  const TileSrc qsrc = tile_src(Qb, p.ldq, p.Sq, wave, lane), dosrc = tile_src(dOb, p.lddo, p.Sq, wave, lane);
+  const TileSrc qsrc = tile_src(x.Qb, p.ldq, p.Sq, wave, lane), dosrc = tile_src(x.dOb, p.lddo, p.Sq, wave, lane);
   auto stage_unit = [&](int u, int st) {
     char* const S0 = St + st * STG;
     const int r0 = u * 64;
@@ -1787,7 +1795,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd3_kernel(const AttnP p, int u
     if (wave == 0) {
       int r = r0 + lane;
       r = r < p.Sq ? r : p.Sq - 1;
-      lds_dma4(lseb + r, S0 + 2 * TILE_BYTES);
+      lds_dma4(x.lseb + r, S0 + 2 * TILE_BYTES);
     }
   };
   const int dq_l = tid >> 2, dqt = tid & 3;                       // delta: thread = (query of the unit, quarter of the head dim)
@@ -1796,10 +1804,10 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd3_kernel(const AttnP p, int u
     int r = u * 64 + dq_l;
     r = r < p.Sq ? r : p.Sq - 1;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) o_pf[i] = *(const bf16x8*)(Ob + (long long)r * p.ldo + dqt * 16 + 8 * i);
+    for (int i = 0; i < 2; ++i) o_pf[i] = *(const bf16x8*)(x.Ob + (long long)r * p.ldo + dqt * 16 + 8 * i);
   };
   {
-    const TileSrc ksrc = tile_src(Kb, p.ldk, p.Skv, wave, lane), vsrc = tile_src(Vb, p.ldv, p.Skv, wave, lane);
+    const TileSrc ksrc = tile_src(x.Kb, p.ldk, p.Skv, wave, lane), vsrc = tile_src(x.Vb, p.ldv, p.Skv, wave, lane);
     stage_tile(ksrc, 0, Ksm, wave);
     stage_tile(vsrc, 0, Vsm, wave);
     if (KB > 2 && wave < 2) {                                     // rows 64..95: the first four 1 KiB pieces of the second tile
@@ -2012,7 +2020,7 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd3_kernel(const AttnP p, int u
   if (krow >= p.Skv) return;
   const float dks = PRE ? 0.6931471805599453f : p.scale;
   if (p.nsplit > 1) {
-    float* pr = p.dkv_part + ((((long long)split * p.B + b) * p.H + head) * p.Skv + krow) * 128;
+    float* pr = p.dkv_part + ((((long long)x.split * p.B + b) * p.H + head) * p.Skv + krow) * 128;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -2150,18 +2158,19 @@ __global__ void attn_dkv_reduce_kernel(const AttnP p) {
   *(bf16x4*)dst = o;
 }
 
-// query-range splitting of the cross-attention backward (few keys, many queries): a workgroup owns `u` consecutive
-// 128-query units of one (batch, head); pick the u that minimises (rounds of 512 workgroups: two per CU) x u, then the
-// split count (fp32 partials per split).  1024 tokens, B*H = 80: u = 2 -> 320 workgroups, 4 splits; 4096 tokens, 40:
-// u = 3 -> 440 workgroups, 11 splits.
-// v2 of the one-pass cross-attention backward (xattn_bwd2_kernel: 64-query units, specialised waves): 33 .. 96 keys
-// which one-pass kernel: 0 = round 3 (xattn_bwd_kernel) for every key count; 2 = xattn_bwd2_kernel where it applies (33..96
-// keys); 1 / 3 (default) = the newest that applies: xattn_bwd3_kernel for 33..80 keys, xattn_bwd2_kernel for 81..96.
-// PEA_XATTN_BWD_VER=n in the environment, pea_debug_set_xattn_bwd_v2(n) at run time (A/B, parity tests).
+// Which one-pass cross-attention backward kernel (PEA_XATTN_BWD_VER=n in the environment, pea_debug_set_xattn_bwd_v2(n) at
+// run time: A/B, parity tests):
+//   0              v1, xattn_bwd_kernel (round 3), for every key count
+//   2              v2, xattn_bwd2_kernel, where it applies (33..96 keys); v1 elsewhere
+//   1, 3 (default) the newest that applies: v3, xattn_bwd3_kernel, for 33..80 keys, v2 for 81..96, v1 elsewhere
 static int g_xattn_v2 = getenv("PEA_XATTN_BWD_VER") ? atoi(getenv("PEA_XATTN_BWD_VER")) : 3;
 extern "C" void pea_debug_set_xattn_bwd_v2(int v) { g_xattn_v2 = v; }
 static bool xattn_v2_keys(int Skv) { return g_xattn_v2 && Skv > 32 && Skv <= 96; }     // v2 OR v3: 64-query units
 static bool xattn_v3_keys(int Skv) { return g_xattn_v2 != 0 && g_xattn_v2 != 2 && Skv > 32 && Skv <= 80; }
+// query-range splitting of the cross-attention backward (few keys, many queries): a workgroup owns `u` consecutive
+// 128-query units of one (batch, head); pick the u that minimises (rounds of 512 workgroups: two per CU) x u, then the
+// split count (fp32 partials per split).  1024 tokens, B*H = 80: u = 2 -> 320 workgroups, 4 splits; 4096 tokens, 40:
+// u = 3 -> 440 workgroups, 11 splits.
 int attention_bwd_nsplit(int B, int H, int Sq, int Skv) {
   if (Skv > 128 || Sq < 512) return 1;
   const bool v2 = xattn_v2_keys(Skv);
@@ -2199,32 +2208,62 @@ static int attn_check(const AttnP& p) {
   return PEA_OK;
 }
 
-#define ATTN_DISPATCH(KERNEL_TR, KERNEL_NOTR, grid, lds)                                        \
-  do {                                                                                          \
-    if (g_attn_use_tr) hipLaunchKernelGGL(KERNEL_TR, grid, dim3(256), lds, s, p);               \
-    else hipLaunchKernelGGL(KERNEL_NOTR, grid, dim3(256), lds, s, p);                           \
-  } while (0)
-
-template <int ND>
-static int attn_set_lds_attr() {
-  static bool done = false;
-  if (done) return PEA_OK;
-  const int lq = 2 * 2 * ND * TILE_BYTES, lk = 2 * (2 * ND * TILE_BYTES + 512);
-  HIPCHK(hipFuncSetAttribute((const void*)attn_q_kernel<0, true, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, lq));
-  HIPCHK(hipFuncSetAttribute((const void*)attn_q_kernel<0, false, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, lq));
-  HIPCHK(hipFuncSetAttribute((const void*)attn_q_kernel<1, true, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, lq));
-  HIPCHK(hipFuncSetAttribute((const void*)attn_q_kernel<1, false, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, lq));
-  HIPCHK(hipFuncSetAttribute((const void*)attn_dkv_kernel<true, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, lk));
-  HIPCHK(hipFuncSetAttribute((const void*)attn_dkv_kernel<false, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, lk));
-  done = true;
+// hipFuncAttributeMaxDynamicSharedMemorySize of kernel K raised to `bytes`, once per process, then the launch: every
+// kernel of this file that takes dynamic LDS goes through here, so no list of instantiations has to be kept by hand.
+// The attribute call belongs to an instantiation's FIRST launch: if that launch is inside a stream capture, the call
+// happens during the capture (it is not a stream operation and is not recorded).
+template <auto K, typename... Args>
+static int launch_lds(dim3 grid, int bytes, hipStream_t s, const Args&... args) {
+  static bool raised = false;
+  if (!raised) {
+    HIPCHK(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    raised = true;
+  }
+  hipLaunchKernelGGL(K, grid, dim3(256), bytes, s, args...);
   return PEA_OK;
+}
+// the general kernels: the transpose-read instance, or (pea_debug_set_attn_tr(0)) the one that gathers its fragments
+#define ATTN_DISPATCH(KERNEL_TR, KERNEL_NOTR, grid, lds, ...)                           \
+  (g_attn_use_tr ? launch_lds<KERNEL_TR>(grid, lds, s, p, ##__VA_ARGS__)                \
+                 : launch_lds<KERNEL_NOTR>(grid, lds, s, p, ##__VA_ARGS__))
+
+// run-time (key blocks of 32, prescaled Q) -> instantiation, one dispatch per cross-attention kernel family
+static int launch_xattn_fwd(int kb, dim3 grid, int lds, hipStream_t s, const AttnP& p, int upw) {
+  switch (kb) {
+    case 1: return launch_lds<xattn_fwd_kernel<1>>(grid, lds, s, p, upw);
+    case 2: return launch_lds<xattn_fwd_kernel<2>>(grid, lds, s, p, upw);
+    case 3: return launch_lds<xattn_fwd_kernel<3>>(grid, lds, s, p, upw);
+    default: return launch_lds<xattn_fwd_kernel<4>>(grid, lds, s, p, upw);
+  }
+}
+static int launch_xattn_bwd1(int kb, dim3 grid, hipStream_t s, const AttnP& p, int upw) {
+  constexpr int lds = 4 * TILE_BYTES + (4 * TILE_BYTES + 1024);
+  switch (kb) {
+    case 1: return launch_lds<xattn_bwd_kernel<1>>(grid, lds, s, p, upw);
+    case 2: return launch_lds<xattn_bwd_kernel<2>>(grid, lds, s, p, upw);
+    case 3: return launch_lds<xattn_bwd_kernel<3>>(grid, lds, s, p, upw);
+    default: return launch_lds<xattn_bwd_kernel<4>>(grid, lds, s, p, upw);
+  }
+}
+template <int KB>                                                  // v2 / v3 exist for 2 and 3 key blocks (33..96 keys)
+static int launch_xattn_bwd23(bool v3, dim3 grid, hipStream_t s, const AttnP& p, int upw) {
+  constexpr int lds2 = 4 * TILE_BYTES + 2 * (2 * TILE_BYTES + 512) + 2 * 32 * 144;
+  constexpr int lds3 = 2 * (TILE_BYTES + TILE_BYTES / 2) + 2 * (2 * TILE_BYTES + 512) + 2 * (TILE_BYTES + 2048);
+  if (v3) return p.q_prescaled ? launch_lds<xattn_bwd3_kernel<KB, true>>(grid, lds3, s, p, upw)
+                               : launch_lds<xattn_bwd3_kernel<KB, false>>(grid, lds3, s, p, upw);
+  return p.q_prescaled ? launch_lds<xattn_bwd2_kernel<KB, true>>(grid, lds2, s, p, upw)
+                       : launch_lds<xattn_bwd2_kernel<KB, false>>(grid, lds2, s, p, upw);
+}
+// the ordered sum of the query-range splits' fp32 dK / dV partials, behind whichever kernel wrote them
+static void launch_dkv_reduce(const AttnP& p, int nd, hipStream_t s) {
+  const long long total = (long long)p.B * p.H * p.Skv * 2 * 16 * nd;
+  hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, p);
 }
 
 template <int ND>
 static int attn_fwd_nd(const AttnP& p, hipStream_t s) {
-  int rc = attn_set_lds_attr<ND>();
-  if (rc) return rc;
   const dim3 grid(cdiv(p.Sq, 128), p.H, p.B);
+  constexpr int lq = 2 * 2 * ND * TILE_BYTES;
   if constexpr (ND == 1) {
     if (g_attn_xattn && g_attn_use_tr && p.Skv <= 128 && !p.causal && !p.bias && p.Sq >= 128) {   // cross-attention: K / V resident
       const int kb = cdiv(p.Skv, 32), kt = (kb + 1) / 2;
@@ -2233,29 +2272,15 @@ static int attn_fwd_nd(const AttnP& p, hipStream_t s) {
       const long long units = (long long)p.B * p.H * nu;
       int upw = (int)((units + 511) / 512);                       // one round of two workgroups per CU (66 KB of LDS each)
       upw = upw < 1 ? 1 : (upw > nu ? nu : upw);
-      const dim3 g2(cdiv(nu, upw), p.H, p.B);
-      if (kb == 1) hipLaunchKernelGGL(xattn_fwd_kernel<1>, g2, dim3(256), lds, s, p, upw);
-      else if (kb == 2) hipLaunchKernelGGL(xattn_fwd_kernel<2>, g2, dim3(256), lds, s, p, upw);
-      else if (kb == 3) hipLaunchKernelGGL(xattn_fwd_kernel<3>, g2, dim3(256), lds, s, p, upw);
-      else hipLaunchKernelGGL(xattn_fwd_kernel<4>, g2, dim3(256), lds, s, p, upw);
-      return PEA_OK;
+      return launch_xattn_fwd(kb, dim3(cdiv(nu, upw), p.H, p.B), lds, s, p, upw);
     }
   }
   if (p.causal || p.kv_len || p.bias) {       // text-encoder masks / score bias: separate instance (head_dim 64 only)
     SHAPECHK(ND == 1, "attention: causal / key-length masks need head_dim 64");
-    if constexpr (ND == 1) {
-      static bool attr = false;
-      if (!attr) {
-        HIPCHK(hipFuncSetAttribute((const void*)attn_q_kernel<0, true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   2 * 2 * TILE_BYTES));
-        attr = true;
-      }
-      hipLaunchKernelGGL((attn_q_kernel<0, true, 1, true>), grid, dim3(256), 2 * 2 * TILE_BYTES, s, p);
-    }
+    if constexpr (ND == 1) return launch_lds<attn_q_kernel<0, true, 1, true>>(grid, lq, s, p);
     return PEA_OK;
   }
-  ATTN_DISPATCH((attn_q_kernel<0, true, ND>), (attn_q_kernel<0, false, ND>), grid, 2 * 2 * ND * TILE_BYTES);
-  return PEA_OK;
+  return ATTN_DISPATCH((attn_q_kernel<0, true, ND>), (attn_q_kernel<0, false, ND>), grid, lq);
 }
 static int g_attn_fused_bwd = getenv("PEA_ATTN_BWD_SPLIT") ? 0 : 1;      // PEA_ATTN_BWD_SPLIT=1: the two-launch form (A/B)
 // the one-pass cross-attention backward: head_dim 64, at most 128 keys, all three gradients wanted
@@ -2265,100 +2290,41 @@ static bool attn_use_xattn(const AttnP& p) {
 extern "C" void pea_debug_set_attn_fused_bwd(int v) { g_attn_fused_bwd = v; }
 template <int ND>
 static int attn_bwd_nd(const AttnP& p, hipStream_t s) {
-  int rc = attn_set_lds_attr<ND>();
-  if (rc) return rc;
+  const int ns = p.nsplit > 1 ? p.nsplit : 1;
+  constexpr int lq = 2 * 2 * ND * TILE_BYTES, lk = 2 * (2 * ND * TILE_BYTES + 512);
+  int rc = PEA_OK;
   if constexpr (ND == 1) {
     if (attn_use_xattn(p)) {
-      constexpr int lds = 4 * TILE_BYTES + (4 * TILE_BYTES + 1024);
-      static bool attr = false;
-      if (!attr) {
-        HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr = true;
-      }
-      const int ns = p.nsplit > 1 ? p.nsplit : 1;
       const dim3 grid(ns, p.H, p.B);
       const int kb = cdiv(p.Skv, 32);
-      if (xattn_v2_keys(p.Skv)) {
-        constexpr int lds2 = 4 * TILE_BYTES + 2 * (2 * TILE_BYTES + 512) + 2 * 32 * 144;
-        static bool attr2 = false;
-        if (!attr2) {
-          HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd2_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-          HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd2_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-          HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd2_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-          HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd2_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-          attr2 = true;
-        }
-        const int upw2 = cdiv(cdiv(p.Sq, 64), ns);
-        if (xattn_v3_keys(p.Skv)) {
-          constexpr int lds3 = 2 * (TILE_BYTES + TILE_BYTES / 2) + 2 * (2 * TILE_BYTES + 512) + 2 * (TILE_BYTES + 2048);
-          static bool attr3 = false;
-          if (!attr3) {
-            HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd3_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
-            HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd3_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
-            HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd3_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
-            HIPCHK(hipFuncSetAttribute((const void*)xattn_bwd3_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
-            attr3 = true;
-          }
-          if (kb == 2) {
-            if (p.q_prescaled) hipLaunchKernelGGL((xattn_bwd3_kernel<2, true>), grid, dim3(256), lds3, s, p, upw2);
-            else hipLaunchKernelGGL((xattn_bwd3_kernel<2, false>), grid, dim3(256), lds3, s, p, upw2);
-          } else {
-            if (p.q_prescaled) hipLaunchKernelGGL((xattn_bwd3_kernel<3, true>), grid, dim3(256), lds3, s, p, upw2);
-            else hipLaunchKernelGGL((xattn_bwd3_kernel<3, false>), grid, dim3(256), lds3, s, p, upw2);
-          }
-        } else if (kb == 2) {
-          if (p.q_prescaled) hipLaunchKernelGGL((xattn_bwd2_kernel<2, true>), grid, dim3(256), lds2, s, p, upw2);
-          else hipLaunchKernelGGL((xattn_bwd2_kernel<2, false>), grid, dim3(256), lds2, s, p, upw2);
-        } else {
-          if (p.q_prescaled) hipLaunchKernelGGL((xattn_bwd2_kernel<3, true>), grid, dim3(256), lds2, s, p, upw2);
-          else hipLaunchKernelGGL((xattn_bwd2_kernel<3, false>), grid, dim3(256), lds2, s, p, upw2);
-        }
-      } else {
-      const int nu = cdiv(p.Sq, 128), upw = cdiv(nu, ns);
-      if (kb == 1) hipLaunchKernelGGL(xattn_bwd_kernel<1>, grid, dim3(256), lds, s, p, upw);
-      else if (kb == 2) hipLaunchKernelGGL(xattn_bwd_kernel<2>, grid, dim3(256), lds, s, p, upw);
-      else if (kb == 3) hipLaunchKernelGGL(xattn_bwd_kernel<3>, grid, dim3(256), lds, s, p, upw);
-      else hipLaunchKernelGGL(xattn_bwd_kernel<4>, grid, dim3(256), lds, s, p, upw);
+      if (xattn_v2_keys(p.Skv)) {                                  // v2 or v3: 64-query units
+        const int upw = cdiv(cdiv(p.Sq, 64), ns);
+        rc = kb == 2 ? launch_xattn_bwd23<2>(xattn_v3_keys(p.Skv), grid, s, p, upw)
+                     : launch_xattn_bwd23<3>(xattn_v3_keys(p.Skv), grid, s, p, upw);
+      } else {                                                     // v1: 128-query units
+        rc = launch_xattn_bwd1(kb, grid, s, p, cdiv(cdiv(p.Sq, 128), ns));
       }
-      if (p.nsplit > 1) {
-        const long long total = (long long)p.B * p.H * p.Skv * 2 * 16;
-        hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, p);
-      }
+      if (rc) return rc;
+      if (p.nsplit > 1) launch_dkv_reduce(p, 1, s);
       return PEA_OK;
     }
   }
   if (p.dQ && p.dK && p.dV && g_attn_fused_bwd) {
-    static bool attr = false;
-    constexpr int lds = 2 * (2 * ND * TILE_BYTES + 512);
-    if (!attr) {
-      HIPCHK(hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<true, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      HIPCHK(hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<false, ND>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      attr = true;
-    }
-    const int n_dq = cdiv(p.Sq, 128) * ND, n_dkv = cdiv(p.Skv, 128) * (p.nsplit > 1 ? p.nsplit : 1) * ND;
+    const int n_dq = cdiv(p.Sq, 128) * ND, n_dkv = cdiv(p.Skv, 128) * ns * ND;
     const dim3 grid((unsigned)((n_dq + n_dkv) * p.H * p.B));
-    if (g_attn_use_tr) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, ND>), grid, dim3(256), lds, s, p, n_dq, n_dkv);
-    else hipLaunchKernelGGL((attn_bwd_fused_kernel<false, ND>), grid, dim3(256), lds, s, p, n_dq, n_dkv);
-    if (p.nsplit > 1) {
-      const long long total = (long long)p.B * p.H * p.Skv * 2 * 16 * ND;
-      hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, p);
-    }
+    rc = ATTN_DISPATCH((attn_bwd_fused_kernel<true, ND>), (attn_bwd_fused_kernel<false, ND>), grid, lk, n_dq, n_dkv);
+    if (rc) return rc;
+    if (p.nsplit > 1) launch_dkv_reduce(p, ND, s);
     return PEA_OK;
   }
   if (p.dQ) {
-    const dim3 grid(cdiv(p.Sq, 128) * ND, p.H, p.B);
-    ATTN_DISPATCH((attn_q_kernel<1, true, ND>), (attn_q_kernel<1, false, ND>), grid, 2 * 2 * ND * TILE_BYTES);
+    rc = ATTN_DISPATCH((attn_q_kernel<1, true, ND>), (attn_q_kernel<1, false, ND>), dim3(cdiv(p.Sq, 128) * ND, p.H, p.B), lq);
+    if (rc) return rc;
   }
   if (p.dK && p.dV) {
-    const dim3 grid(cdiv(p.Skv, 128) * (p.nsplit > 1 ? p.nsplit : 1) * ND, p.H, p.B);
-    ATTN_DISPATCH((attn_dkv_kernel<true, ND>), (attn_dkv_kernel<false, ND>), grid, 2 * (2 * ND * TILE_BYTES + 512));
-    if (p.nsplit > 1) {
-      const long long total = (long long)p.B * p.H * p.Skv * 2 * 16 * ND;
-      hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, p);
-    }
+    rc = ATTN_DISPATCH((attn_dkv_kernel<true, ND>), (attn_dkv_kernel<false, ND>), dim3(cdiv(p.Skv, 128) * ns * ND, p.H, p.B), lk);
+    if (rc) return rc;
+    if (p.nsplit > 1) launch_dkv_reduce(p, ND, s);
   }
   return PEA_OK;
 }
