@@ -629,6 +629,15 @@ void pea_debug_set_xattn_bwd_v2(int v);
 void pea_debug_set_geglu_bwd_fused(int v);
 /* benchmark aid: force GEMM tile variant (>= 0) or restore the shape-based choice (-1) */
 void pea_debug_set_gemm_variant(int v);
+/* Test aid, needs no device: which kernel instantiation launch_gemm launches for a problem.  Returns the launcher's enumerator:
+ * a variant id of the table (18 .. 41), 100 + id for the fused GEGLU-backward kernels (127, 128, 131), 200 + id for the
+ * folded-LayerNorm kernels (224, 225, 227, 228, 231).  mode: 0 GEMM, 1 conv gather; rows_per_batch: rows per sample of the row
+ * vector (<= 0: M); cus: CUs the launch may occupy (PEA_CU_LIMIT halves it); forced: a pinned variant id or -1.
+ * features: 1 residual, 2 row vector, 4 fp32 output, 8 activation, 16 pre-activation stash (with GEGLU: C takes the stash,
+ * without the bit a GEGLU problem has no C), 32 GEGLU output, 64 fused GEGLU backward, 128 folded-LayerNorm statistics,
+ * 256 column scale, 512 split-K, 1024 pointers 16-byte aligned and row strides multiples of 8 (else 4-byte / multiples of 4).
+ * M <= 0: the N-th entry of the enumerator list instead (-1 past its end). */
+int pea_debug_gemm_dispatch(int M, int N, int K, int mode, int rows_per_batch, int features, int cus, int forced);
 /* timing-only probes of the loader/consumer GEMM (results are wrong while set): 1 no DMA, 2 no barriers, 4 no ds_reads */
 void pea_debug_set_gemm_debug(int v);
 /* experiment aid (scripts/chain_probe.py): arms the NEXT GEMM / conv launch with a prefetch target -- its DMA waves touch

@@ -13,34 +13,18 @@
 // vector bias/residual loads.  gemm_lc_kernel: one tile per workgroup; gemm_lcp_kernel: persistent, one workgroup
 // per CU walking its tiles (XCD-aware order, 8 M-tiles grouped per N-tile so the tiles resident on one XCD share
 // operand panels).  DESIGN.md section 4 has the measured variant table and what was tried and dropped.
+#include <stdint.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "pea_kernels.h"
-#ifndef PEA_GEMM_BUFFER_DMA
-#define PEA_GEMM_BUFFER_DMA 1
-#endif
 
 #define BK 64
-#ifndef PEA_GEMM_ILV
-#define PEA_GEMM_ILV 1          // 1: fragment reads interleaved with the MFMAs of the 64-row-wave-tile K-loops (0: one burst behind the first n-tile)
-#endif
-#ifndef PEA_GEMM_ILV_M
-#define PEA_GEMM_ILV_M 1        // MFMAs between two interleaved ds_reads
-#endif
-#ifndef PEA_GEMM_ILV_HEAD
-#define PEA_GEMM_ILV_HEAD 4     // MFMAs in front of the first interleaved ds_read
-#endif
-#ifndef PEA_GEMM_ILV_EPI3
-#define PEA_GEMM_ILV_EPI3 1      // also in the fused GEGLU-backward instantiations (whole step 104.51 / 104.21 -> 103.98 / 103.79 ms)
-#endif
-#ifndef PEA_GEMM_ILV_LC
-#define PEA_GEMM_ILV_LC 0        // the one-tile-per-workgroup kernel: the burst form measures better there (104.1 vs 104.5 ms with it interleaved)
-#endif
-#ifndef PEA_GEMM_PRIO_YOUNG
-#define PEA_GEMM_PRIO_YOUNG 0   // 1: static s_setprio 1 for consumer waves 4..7 (the younger wave of every SIMD) -- experiment
-#endif
+// The fragment reads of the 64-row-wave-tile K-loops are interleaved with the MFMAs (mfma_half_interleaved: persistent kernel and
+// K-split consumers; the one-tile-per-workgroup kernel keeps its burst -- profiles/EXPERIMENTS.md has both A/Bs):
+constexpr int GEMM_ILV_M = 1;        // MFMAs between two interleaved ds_reads
+constexpr int GEMM_ILV_HEAD = 4;     // MFMAs in front of the first interleaved ds_read
 
 __device__ __forceinline__ int swz_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
@@ -326,20 +310,8 @@ __device__ __forceinline__ void gemm_epilogue16(const GemmP& p, f32x4 (&acc)[NT]
 //   value = rstd[m] * (acc - mean[m] * s[n]) + t[n]        (p.ln_stats = [M][2] (mean, rstd), p.ln_s = s[N]);
 // such GEMMs have no residual and no row vector (QKV, attn2.to_q, FF projection with GEGLU).
 // EK: 0 = common form, 1 = LNF, 2 = the fused GEGLU backward (p.gbwd_pre; own instantiations for the same reason)
-// Stores of the batched-load epilogue, HIDDEN from hipcc's s_waitcnt bookkeeping (inline assembly; PEA_EPI_HIDDEN_STORES = 0
-// restores plain stores for an A/B).  Why: gfx950 has ONE vmcnt for loads and stores, and hipcc treats the two kinds as
-// completing out of order -- with a store pending, the only wait it can emit for a load is vmcnt(0).  In the persistent kernel
-// the registers that received the epilogue's bias / residual loads are the next tile's fragment registers; on the paths where
-// a load's use is predicated away the compiler still sees it pending at the first ds_read into that register (a write-after-
-// write hazard), and because the tile's stores are pending too it put `s_waitcnt vmcnt(0)` INSIDE the K-loop (and vmcnt(2) in
-// its preheader): every consumer wave waited out its own 10 KB of stores in the first K-step of the next tile, with the MFMA
-// pipes idle -- the store drain the persistent form exists to hide.  With the stores invisible every wait hipcc emits is a
-// wait for loads only (all loads of the epilogue are issued, and their data consumed, before its first store -- an asm load
-// wait would be unsafe otherwise), nothing is pending after the epilogue, and the stores drain under the next tile's K-steps.
-// The s_nop 1 of the 16-byte form is the store-data hazard hipcc would have padded (a following write of the data registers).
-#ifndef PEA_EPI_HIDDEN_STORES
-#define PEA_EPI_HIDDEN_STORES 0
-#endif
+// (The stores were once hidden from hipcc's s_waitcnt bookkeeping as inline assembly, and once write-through: both A/Bs are in
+// profiles/EXPERIMENTS.md.  What keeps the loads' waits out of the next tile's K-loop are the empty asm uses below.)
 typedef __attribute__((ext_vector_type(4))) unsigned epi_u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned epi_u32x2;
 // "this loaded value has been consumed": an empty asm use.  Placed behind every predicated region of the epilogue for the loads
@@ -347,37 +319,10 @@ typedef __attribute__((ext_vector_type(2))) unsigned epi_u32x2;
 // load is still waited for -- otherwise hipcc carries it as pending into the next tile's K-loop (see above).  No instruction.
 template <typename T>
 __device__ __forceinline__ void epi_consumed(const T& v) { asm volatile("" :: "v"(v)); }
-// PEA_EPI_WT (experiment, one-tile kernels only): write-through (sc1) stores -- the lines leave the XCD's L2 as they are written
-// instead of at the end-of-kernel release
-#ifndef PEA_EPI_WT
-#define PEA_EPI_WT 0
-#endif
-template <bool WT = false>
-__device__ __forceinline__ void epi_store16(void* ptr, epi_u32x4 v) {
-  if constexpr (WT) { asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(ptr), "v"(v) : "memory"); return; }
-#if PEA_EPI_HIDDEN_STORES
-  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(ptr), "v"(v) : "memory");
-#else
-  *(epi_u32x4*)ptr = v;
-#endif
-}
-template <bool WT = false>
-__device__ __forceinline__ void epi_store8(void* ptr, epi_u32x2 v) {
-  if constexpr (WT) { asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(ptr), "v"(v) : "memory"); return; }
-#if PEA_EPI_HIDDEN_STORES
-  asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(ptr), "v"(v) : "memory");
-#else
-  *(epi_u32x2*)ptr = v;
-#endif
-}
-__device__ __forceinline__ void epi_store4(void* ptr, unsigned v) {
-#if PEA_EPI_HIDDEN_STORES
-  asm volatile("global_store_dword %0, %1, off" :: "v"(ptr), "v"(v) : "memory");
-#else
-  *(unsigned*)ptr = v;
-#endif
-}
-template <int MT, int NT, int EK = 0, bool WT = false>
+__device__ __forceinline__ void epi_store16(void* ptr, epi_u32x4 v) { *(epi_u32x4*)ptr = v; }
+__device__ __forceinline__ void epi_store8(void* ptr, epi_u32x2 v) { *(epi_u32x2*)ptr = v; }
+__device__ __forceinline__ void epi_store4(void* ptr, unsigned v) { *(unsigned*)ptr = v; }
+template <int MT, int NT, int EK = 0>
 __device__ __forceinline__ void gemm_epilogue16_fast(const GemmP& p, f32x4 (&acc)[NT][MT], int m_base, int n_base, int r16,
                                                      int q4) {
   constexpr bool LNF = EK == 1;
@@ -600,7 +545,7 @@ __device__ __forceinline__ void gemm_epilogue16_fast(const GemmP& p, f32x4 (&acc
                 o.h[j] = (bf16)(lo[j] + (float)r8[j]);
                 o.h[4 + j] = (bf16)(hi[j] + (float)r8[4 + j]);
               }
-              epi_store16<WT>(crow + n_base + (nt + (q4 & 1)) * 16 + 8 * (q4 >> 1), o.u);
+              epi_store16(crow + n_base + (nt + (q4 & 1)) * 16 + 8 * (q4 >> 1), o.u);
             } else {
               union { bf16x4 h; unsigned u[2]; } a, b;
 #pragma unroll
@@ -611,7 +556,7 @@ __device__ __forceinline__ void gemm_epilogue16_fast(const GemmP& p, f32x4 (&acc
               const auto lo = __builtin_amdgcn_permlane16_swap(a.u[0], b.u[0], false, false);
               const auto hi = __builtin_amdgcn_permlane16_swap(a.u[1], b.u[1], false, false);
               const u32x4 o = {lo[0], hi[0], lo[1], hi[1]};
-              epi_store16<WT>(crow + n_base + (nt + (q4 & 1)) * 16 + 8 * (q4 >> 1), o);
+              epi_store16(crow + n_base + (nt + (q4 & 1)) * 16 + 8 * (q4 >> 1), o);
             }
           } else {                                                     // the single last tile of an odd nv
             union { bf16x4 h; u32x2 u; } o;
@@ -621,7 +566,7 @@ __device__ __forceinline__ void gemm_epilogue16_fast(const GemmP& p, f32x4 (&acc
               if constexpr (HR) v += (float)rs[mt][j];
               o.h[j] = (bf16)v;
             }
-            epi_store8<WT>(crow + n_base + nt * 16 + 4 * q4, o.u);
+            epi_store8(crow + n_base + nt * 16 + 4 * q4, o.u);
           }
         }
       }
@@ -792,7 +737,7 @@ __device__ __forceinline__ void conv_tap(const GemmP& p, int tap, int& ky, int& 
   else { ky = tap / 3; kx = tap - ky * 3; }
 }
 
-#if PEA_GEMM_BUFFER_DMA && defined(__HIP_DEVICE_COMPILE__)
+#ifdef __HIP_DEVICE_COMPILE__                     // (the host pass has no buffer-resource type)
 // Buffer resource of one row-tile's A operand.  The resource starts at the tile's first row (plain GEMM) or at the first
 // sample the tile touches (conv gather), so the per-lane 32-bit offsets only span one tile / a couple of samples and the
 // operand itself may be any size (the SDXL VAE decoder's [4][1024][1024][256] activations are 2^31 bytes).  num_records
@@ -816,6 +761,26 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const GemmP& p, int 
 }
 #endif
 
+// ---- one k32 half of a 64-row-wave-tile K-step: all MT x NT MFMAs, their issue order pinned so that the MT + NT ds_reads the
+// caller has just requested (the other half's fragments) go out one per GEMM_ILV_M MFMAs behind the first GEMM_ILV_HEAD, instead
+// of one burst behind the first n-tile: the 8 consumer waves of a CU run in lockstep between barriers, so a burst is 72 KB hitting
+// the LDS at once while no wave issues an MFMA.  Whole step (round 4, alternating processes on one box): 104.38 / 103.99 ms ->
+// 103.68 / 103.55 (M = 1, HEAD = 4), 104.04 / 103.65 (M = 2, HEAD = 2).  The caller brackets reads + this with sched_barrier(0).
+template <int MT, int NT>
+__device__ __forceinline__ void mfma_half_interleaved(f32x4 (&acc)[NT][MT], const bf16x8 (&wf)[NT], const bf16x8 (&af)[MT]) {
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+      acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
+  __builtin_amdgcn_sched_group_barrier(0x008, GEMM_ILV_HEAD, 0);
+#pragma unroll
+  for (int i = 0; i < MT + NT; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, GEMM_ILV_M, 0);
+  }
+  __builtin_amdgcn_sched_group_barrier(0x008, MT * NT, 0);
+}
 // ------------------------------------------------------------------------------------------------
 // Loader / consumer kernel.  WM x WN consumer waves run ONLY ds_reads + MFMAs (register double-buffered
 // fragments as above); LW extra loader waves run ONLY the LDS-DMA stream (address arithmetic + pieces), so
@@ -884,7 +849,7 @@ __global__ __launch_bounds__((WM * WN * (KSW ? 2 : 1) + LW) * 64, MINW) void gem
     // ============================== loader waves
     const int lw = wave - NWC;
     const int lrow = lane >> 3, cpos = lane & 7;
-#if PEA_GEMM_BUFFER_DMA && defined(__HIP_DEVICE_COMPILE__)
+#ifdef __HIP_DEVICE_COMPILE__
     // buffer form of the LDS-DMA, as in gemm_lcp_kernel: no vector instruction per K-step in the DMA waves
     int org;
     const __amdgpu_buffer_rsrc_t rsrc_a = tile_rsrc<MODE, BM>(p, bm, org);
@@ -953,65 +918,7 @@ __global__ __launch_bounds__((WM * WN * (KSW ? 2 : 1) + LW) * 64, MINW) void gem
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, PEA_LDS(base + A_BYTES + (lw * PB + j) * 1024), 16, w_off[j], k0 * 2, 0, 0);
     };
 #else
-    const bf16* a_src[PA];
-    int a_iy0[PA], a_ix0[PA];
-    const bf16* w_src[PB];
-#pragma unroll
-    for (int j = 0; j < PA; ++j) {
-      const int r = (lw * PA + j) * 8 + lrow;
-      const int chunk = cpos ^ ((r >> 1) & 7);
-      int gm = bm * BM + r;
-      gm = gm < p.M ? gm : p.M - 1;
-      if (MODE == 0) {
-        a_src[j] = p.A + (long long)gm * p.lda + chunk * 8;
-        a_iy0[j] = a_ix0[j] = 0;
-      } else {
-        const int hw = p.Ho * p.Wo;
-        const int b = gm / hw;
-        const int rem = gm - b * hw;
-        const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-        a_iy0[j] = oy * p.stride - 1 + p.pad_off;
-        a_ix0[j] = ox * p.stride - 1 + p.pad_off + p.pad_dx;
-        a_src[j] = p.A + (long long)b * p.Hs * p.Ws * conv_pix(p) + chunk * 8;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < PB; ++j) {
-      const int r = (lw * PB + j) * 8 + lrow;
-      const int chunk = cpos ^ ((r >> 1) & 7);
-      int gn = bn * BN + r;
-      gn = gn < p.N ? gn : p.N - 1;
-      w_src[j] = p.W + (long long)gn * p.ldw + chunk * 8;
-    }
-    const int Hv = p.Hs << p.shift, Wv = p.Ws << p.shift;
-    auto issue = [&](int st, int k0) {
-      char* base = smem + st * STAGE;
-      int ky = 0, kx = 0, c0 = 0;
-      if (MODE == 1) {
-        const int tap = k0 / p.Cin;
-        int cblk;
-        conv_tap(p, tap, ky, kx, cblk);
-        c0 = k0 - tap * p.Cin + cblk;
-      }
-#pragma unroll
-      for (int j = 0; j < PA; ++j) {
-        const bf16* src;
-        if (MODE == 0) {
-          src = a_src[j] + k0;
-        } else {
-          const int iy = a_iy0[j] + ky, ix = a_ix0[j] + kx;
-          bool ok = ((unsigned)iy < (unsigned)Hv) && ((unsigned)ix < (unsigned)Wv);
-          if (p.parity) ok = ok && (((iy | ix) & 1) == 0);
-          const int sy = iy >> p.shift, sx = ix >> p.shift;
-          src = ok ? a_src[j] + ((long long)sy * p.Ws + sx) * conv_pix(p) + c0 : p.zeros;
-        }
-        __builtin_amdgcn_global_load_lds(PEA_GLB(src), PEA_LDS(base + (lw * PA + j) * 1024), 16, 0, 0);
-      }
-#pragma unroll
-      for (int j = 0; j < PB; ++j)
-        __builtin_amdgcn_global_load_lds(PEA_GLB(w_src[j] + k0), PEA_LDS(base + A_BYTES + (lw * PB + j) * 1024), 16,
-                                         0, 0);
-    };
+    auto issue = [](int, int) {};
 #endif
 #pragma unroll
     for (int i = 0; i < S; ++i)
@@ -1074,18 +981,7 @@ __global__ __launch_bounds__((WM * WN * (KSW ? 2 : 1) + LW) * 64, MINW) void gem
       if (t + 1 < nt) __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       load_frags(P ^ 1, smem + nxt * STAGE);
-#pragma unroll
-      for (int n_ = 0; n_ < NT; ++n_)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-          acc[n_][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[P][n_], af[P][mt], acc[n_][mt], 0, 0, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, PEA_GEMM_ILV_HEAD, 0);
-#pragma unroll
-      for (int i = 0; i < MT + NT; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, PEA_GEMM_ILV_M, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, MT * NT, 0);
+      mfma_half_interleaved<MT, NT>(acc, wf[P], af[P]);
       __builtin_amdgcn_sched_barrier(0);
       cur = nxt;
     };
@@ -1165,27 +1061,6 @@ __global__ __launch_bounds__((WM * WN * (KSW ? 2 : 1) + LW) * 64, MINW) void gem
         } else if (MT < 4) {
           load_frags(1, tile, 1);                              // (32-row wave tiles: hipcc's own placement measures better)
         }
-#if PEA_GEMM_ILV && PEA_GEMM_ILV_LC
-        if (MT >= 4) {                                         // (see gemm_lcp_kernel: fragment reads interleaved with the MFMAs)
-          __builtin_amdgcn_sched_barrier(0);
-          if (s2 == 0) load_frags(1, tile, 1);
-          else load_frags(0, smem + nxt * STAGE, 0);           // unconditional (last K-step: a harmless read of a stale slot)
-#pragma unroll
-          for (int nt_ = 0; nt_ < NT; ++nt_)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-              acc[nt_][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s2][nt_], af[s2][mt], acc[nt_][mt], 0, 0, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, PEA_GEMM_ILV_HEAD, 0);
-#pragma unroll
-          for (int i = 0; i < MT + NT; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, PEA_GEMM_ILV_M, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, MT * NT, 0);
-          __builtin_amdgcn_sched_barrier(0);
-          continue;
-        }
-#endif
 #pragma unroll
         for (int nt_ = 0; nt_ < NT; ++nt_) {
 #pragma unroll
@@ -1206,7 +1081,7 @@ __global__ __launch_bounds__((WM * WN * (KSW ? 2 : 1) + LW) * 64, MINW) void gem
       return;
     }
     if (p.epi_fast) {
-      gemm_epilogue16_fast<MT, NT, 0, PEA_EPI_WT != 0>(p, acc, bm * BM + wr * (BM / WM), bn * BN + wc * (BN / WN), r16, q4);
+      gemm_epilogue16_fast<MT, NT>(p, acc, bm * BM + wr * (BM / WM), bn * BN + wc * (BN / WN), r16, q4);
       return;
     }
     GemmP q = p;
@@ -1410,7 +1285,7 @@ __global__ __launch_bounds__((WM * WN + LW + SW) * 64, (OCC == 2 ? 3 : 1)) void 
     if (!(p.debug & 64)) __builtin_amdgcn_s_setprio(3);
     const int lw = wave - NWC;
     const int lrow = lane >> 3, cpos = lane & 7;
-#if PEA_GEMM_BUFFER_DMA && defined(__HIP_DEVICE_COMPILE__)   // (the host pass has no buffer-resource type; it only needs the stub)
+#ifdef __HIP_DEVICE_COMPILE__           // (the host pass has no buffer-resource type; it only needs the stubs)
     // Buffer form of the LDS-DMA (buffer_load_dwordx4 ... offen lds): a per-lane 32-bit byte offset + a scalar offset
     // instead of a 64-bit address per lane -- half the address registers handed to the memory pipe per piece, and for the
     // plain GEMM no vector instruction at all per K-step (the K offset is the scalar one).  Reads past num_records return
@@ -1486,69 +1361,8 @@ __global__ __launch_bounds__((WM * WN + LW + SW) * 64, (OCC == 2 ? 3 : 1)) void 
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, PEA_LDS(base + A_BYTES + (lw * PB + j) * 1024), 16, w_off[j], k0 * 2, 0, 0);
     };
 #else
-    const bf16* a_src[PA];
-    int a_iy0[PA], a_ix0[PA];
-    const bf16* w_src[PB];
-    auto setup = [&](int ti) {
-      int bm, bn;
-      tile_of(ti, bm, bn);
-#pragma unroll
-      for (int j = 0; j < PA; ++j) {
-        const int r = (lw * PA + j) * 8 + lrow;
-        const int chunk = cpos ^ ((r >> 1) & 7);
-        int gm = bm * BM + r;
-        gm = gm < p.M ? gm : p.M - 1;
-        if (MODE == 0) {
-          a_src[j] = p.A + (long long)gm * p.lda + chunk * 8;
-          a_iy0[j] = a_ix0[j] = 0;
-        } else {
-          const int hw = p.Ho * p.Wo;
-          const int b = gm / hw;
-          const int rem = gm - b * hw;
-          const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-          a_iy0[j] = oy * p.stride - 1 + p.pad_off;
-          a_ix0[j] = ox * p.stride - 1 + p.pad_off + p.pad_dx;
-          a_src[j] = p.A + (long long)b * p.Hs * p.Ws * conv_pix(p) + chunk * 8;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < PB; ++j) {
-        const int r = (lw * PB + j) * 8 + lrow;
-        const int chunk = cpos ^ ((r >> 1) & 7);
-        int gn = bn * BN + r;
-        gn = gn < p.N ? gn : p.N - 1;
-        w_src[j] = p.W + (long long)gn * p.ldw + chunk * 8;
-      }
-    };
-    const int Hv = p.Hs << p.shift, Wv = p.Ws << p.shift;
-    auto issue = [&](int st, int k0) {
-      char* base = smem + st * STAGE;
-      int ky = 0, kx = 0, c0 = 0;
-      if (MODE == 1) {
-        const int tap = k0 / p.Cin;
-        int cblk;
-        conv_tap(p, tap, ky, kx, cblk);
-        c0 = k0 - tap * p.Cin + cblk;
-      }
-#pragma unroll
-      for (int j = 0; j < PA; ++j) {
-        const bf16* src;
-        if (MODE == 0) {
-          src = a_src[j] + k0;
-        } else {
-          const int iy = a_iy0[j] + ky, ix = a_ix0[j] + kx;
-          bool ok = ((unsigned)iy < (unsigned)Hv) && ((unsigned)ix < (unsigned)Wv);
-          if (p.parity) ok = ok && (((iy | ix) & 1) == 0);
-          const int sy = iy >> p.shift, sx = ix >> p.shift;
-          src = ok ? a_src[j] + ((long long)sy * p.Ws + sx) * conv_pix(p) + c0 : p.zeros;
-        }
-        __builtin_amdgcn_global_load_lds(PEA_GLB(src), PEA_LDS(base + (lw * PA + j) * 1024), 16, 0, 0);
-      }
-#pragma unroll
-      for (int j = 0; j < PB; ++j)
-        __builtin_amdgcn_global_load_lds(PEA_GLB(w_src[j] + k0), PEA_LDS(base + A_BYTES + (lw * PB + j) * 1024), 16,
-                                         0, 0);
-    };
+    auto setup = [](int) {};
+    auto issue = [](int, int) {};
 #endif
     // producer position (tile ordinal, K-step) of the next stage to issue
     int ptile = 0, pt = 0;
@@ -1608,9 +1422,6 @@ __global__ __launch_bounds__((WM * WN + LW + SW) * 64, (OCC == 2 ? 3 : 1)) void 
 #pragma unroll
     for (int nt_ = 0; nt_ < NT; ++nt_) wf[which][nt_] = *(const bf16x8*)(tile + w_off[s2] + nt_ * 2048);
   };
-#if PEA_GEMM_PRIO_YOUNG
-  if (NWC == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   __builtin_amdgcn_s_barrier();                                // prologue barrier
   load_frags(0, smem, 0);
   int cur = 0, g = 0;
@@ -1655,41 +1466,19 @@ __global__ __launch_bounds__((WM * WN + LW + SW) * 64, (OCC == 2 ? 3 : 1)) void 
         } else if (MT < 4) {
           if (!PEA_PROBE(4)) load_frags(1, tile, 1);           // (32-row wave tiles: hipcc's own placement measures better)
         }
-#if PEA_GEMM_ILV
-        // the other half's fragment reads INTERLEAVED with this half's MFMAs (sched_group_barrier: HEAD MFMAs, then one ds_read per
-        // ILV_M MFMAs) instead of one burst of MT + NT reads behind the first n-tile: the 8 consumer waves of a CU run in lockstep
-        // between barriers, so a burst is 72 KB hitting the LDS at once while no wave issues an MFMA.  Whole step (round 4, alternating
-        // processes on one box): 104.38 / 103.99 ms -> 103.68 / 103.55 (M = 1, HEAD = 4), 104.04 / 103.65 (M = 2, HEAD = 2)
-        if (MT >= 4 && (EPI != 3 || PEA_GEMM_ILV_EPI3)) {
+        if (MT >= 4) {                                         // 64-row wave tiles: the other half's fragment reads interleaved with this half's MFMAs
           __builtin_amdgcn_sched_barrier(0);
           if (s2 == 0) { if (!PEA_PROBE(4)) load_frags(1, tile, 1); }
           else if (!PEA_PROBE(4)) load_frags(0, smem + nxt * STAGE, 0);     // unconditional (behind the block's last K-step: a harmless read of a stale slot)
-#pragma unroll
-          for (int nt_ = 0; nt_ < NT; ++nt_)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-              acc[nt_][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s2][nt_], af[s2][mt], acc[nt_][mt], 0, 0, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, PEA_GEMM_ILV_HEAD, 0);
-#pragma unroll
-          for (int i = 0; i < MT + NT; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, PEA_GEMM_ILV_M, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, MT * NT, 0);
+          mfma_half_interleaved<MT, NT>(acc, wf[s2], af[s2]);
           __builtin_amdgcn_sched_barrier(0);
           continue;
         }
-#endif
 #pragma unroll
         for (int nt_ = 0; nt_ < NT; ++nt_) {
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt)
             acc[nt_][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s2][nt_], af[s2][mt], acc[nt_][mt], 0, 0, 0);
-          if (MT >= 4 && s2 == 0 && nt_ == 0) {                // this K-step's second-half fragments, behind the first MFMAs as well
-            __builtin_amdgcn_sched_barrier(0);
-            if (!PEA_PROBE(4)) load_frags(1, tile, 1);
-            __builtin_amdgcn_sched_barrier(0);
-          }
           if (s2 == 1 && nt_ == 0) {
             // (issued right behind the barrier, hipcc's wait in front of this half's first MFMA covered these reads as well: every
             // wave of the CU then sat out an LDS round trip per K-step with the MFMA pipes idle)
@@ -1821,44 +1610,99 @@ static int launch_lcp(const GemmP& p, hipStream_t stream) {
   return PEA_OK;
 }
 
-// ---- variant table (tile shape x wave grid x ring depth); the launcher picks one per problem shape
-int g_gemm_variant = -1;   // >= 0: forced (benchmark / debug)
-extern "C" void pea_debug_set_gemm_variant(int v) { g_gemm_variant = v; }
+// ---- variant table (tile shape x wave grid x ring depth); gemm_decide picks one row per problem
+// X(id, launcher, carries column scale / GEGLU, has a row-vector + fused (GEGLU backward, folded LayerNorm) form,
+//   id to take for the generic epilogue (0: the row carries it itself), template arguments behind MODE...)
+//   24 / 27 = 256x160 tile, 4x2 consumer waves (64x80 each) + 4 DMA waves, 3 stages   (27: persistent)
+//   25 / 28 = 128x160 tile, 4x2 consumer waves (32x80 each) + 4 DMA waves, 3 stages   (28: persistent)
+//   29      = 128x160 tile, 2x2 consumer waves (64x80 each) + 4 DMA waves, 4 stages, persistent
+//   31      =  64x160 tile, 2x2 consumer waves (32x80 each) + 4 DMA waves, 4 stages, persistent
+// What a row's kernel cannot do is a fact of the row, not of the launcher:
+//   34 / 35 (staged / deferred epilogue) carry no column scale and no GEGLU epilogue (34 drops the stash, 35 the output);
+//   39 / 40 (192-row tiles) have no fused instantiation, and a 48-row wave tile of theirs would straddle two samples of a
+//           per-sample row vector in the batched-load epilogue (the shape rule never picks them with one; a pinned id must not either);
+//   27 / 40 / 33 (256- and 192-row persistent tiles) are compiled with the batched-load epilogue only (FASTONLY).
+//   (36 / 37 are FASTONLY too and have no generic stand-in: launch_lcp refuses them.)
+#define GEMM_TABLE(X)                                                                   \
+  X(18, launch_lc,  1, 1,  0, 128, 128, 2, 2, 4, 4)                                     \
+  X(19, launch_lc,  1, 1,  0, 128, 160, 4, 1, 4, 3)                                     \
+  X(20, launch_lc,  1, 1,  0, 128, 160, 4, 1, 4, 3, true)       /* timing probe only */ \
+  X(22, launch_lc,  1, 1,  0, 128, 160, 2, 2, 4, 4, false, true)                        \
+  X(23, launch_lc,  1, 1,  0, 128, 128, 2, 2, 4, 4, false, true)                        \
+  X(24, launch_lc,  1, 1,  0, 256, 160, 4, 2, 4, 3, false, true)                        \
+  X(25, launch_lc,  1, 1,  0, 128, 160, 4, 2, 4, 3, false, true)                        \
+  X(27, launch_lcp, 1, 1, 28, 256, 160, 4, 2, 4, 3, 0, 0, 1)                            \
+  X(28, launch_lcp, 1, 1,  0, 128, 160, 4, 2, 4, 3)                                     \
+  X(29, launch_lcp, 1, 1,  0, 128, 160, 2, 2, 4, 4)                                     \
+  X(30, launch_lcp, 1, 1,  0, 128, 128, 2, 2, 4, 4)                                     \
+  X(31, launch_lcp, 1, 1,  0, 64, 160, 2, 2, 4, 4)                                      \
+  X(33, launch_lcp, 1, 1, 30, 256, 128, 4, 2, 4, 3, 0, 0, 1)                            \
+  X(34, launch_lcp, 0, 1,  0, 128, 160, 4, 2, 4, 3, 4)          /* staged epilogue */   \
+  X(35, launch_lcp, 0, 1,  0, 128, 160, 4, 2, 4, 3, 0, 1)       /* deferred epilogue */ \
+  X(36, launch_lcp, 1, 1,  0, 128, 160, 2, 2, 2, 2, 0, 0, 1, 2) /* two workgroups per CU */ \
+  X(37, launch_lcp, 1, 1,  0, 128, 128, 2, 2, 2, 2, 0, 0, 1, 2)                         \
+  X(39, launch_lc,  1, 0,  0, 192, 160, 4, 2, 4, 3, false, true) /* 48 x 80 wave tiles: row counts that leave 128- / 256-row tiles a partial round */ \
+  X(40, launch_lcp, 1, 0, 28, 192, 160, 4, 2, 4, 3, 0, 0, 1)                            \
+  X(41, launch_lc,  1, 1,  0, 128, 160, 2, 2, 4, 3, false, true, 1, false, true) /* intra-workgroup K split */
 
-#define GEMM_VARIANTS(MODE)                                              \
-  switch (v) {                                                           \
-    case 18: rc = launch_lc<MODE, 128, 128, 2, 2, 4, 4>(p, stream); break; \
-    case 19: rc = launch_lc<MODE, 128, 160, 4, 1, 4, 3>(p, stream); break; \
-    case 20: rc = launch_lc<MODE, 128, 160, 4, 1, 4, 3, true>(p, stream); break; /* timing probe only */ \
-    case 22: rc = launch_lc<MODE, 128, 160, 2, 2, 4, 4, false, true>(p, stream); break; \
-    case 23: rc = launch_lc<MODE, 128, 128, 2, 2, 4, 4, false, true>(p, stream); break; \
-    case 24: rc = launch_lc<MODE, 256, 160, 4, 2, 4, 3, false, true>(p, stream); break; \
-    case 25: rc = launch_lc<MODE, 128, 160, 4, 2, 4, 3, false, true>(p, stream); break; \
-    case 27: rc = launch_lcp<MODE, 256, 160, 4, 2, 4, 3, 0, 0, 1>(p, stream); break; \
-    case 28: rc = launch_lcp<MODE, 128, 160, 4, 2, 4, 3>(p, stream); break; \
-    case 29: rc = launch_lcp<MODE, 128, 160, 2, 2, 4, 4>(p, stream); break; \
-    case 30: rc = launch_lcp<MODE, 128, 128, 2, 2, 4, 4>(p, stream); break; \
-    case 31: rc = launch_lcp<MODE, 64, 160, 2, 2, 4, 4>(p, stream); break; \
-    case 33: rc = launch_lcp<MODE, 256, 128, 4, 2, 4, 3, 0, 0, 1>(p, stream); break; \
-    case 34: rc = launch_lcp<MODE, 128, 160, 4, 2, 4, 3, 4>(p, stream); break; /* staged epilogue */ \
-    case 35: rc = launch_lcp<MODE, 128, 160, 4, 2, 4, 3, 0, 1>(p, stream); break; /* deferred epilogue */ \
-    case 39: rc = launch_lc<MODE, 192, 160, 4, 2, 4, 3, false, true>(p, stream); break; /* 48 x 80 wave tiles: row counts that leave 128- / 256-row tiles a partial round */ \
-    case 40: rc = launch_lcp<MODE, 192, 160, 4, 2, 4, 3, 0, 0, 1>(p, stream); break; \
-    case 41: rc = launch_lc<MODE, 128, 160, 2, 2, 4, 3, false, true, 1, false, true>(p, stream); break; /* intra-workgroup K split */ \
-    case 36: rc = launch_lcp<MODE, 128, 160, 2, 2, 2, 2, 0, 0, 1, 2>(p, stream); break; /* two workgroups per CU */ \
-    case 37: rc = launch_lcp<MODE, 128, 128, 2, 2, 2, 2, 0, 0, 1, 2>(p, stream); break; \
-    default: rc = launch_lc<MODE, 128, 128, 2, 2, 4, 4, false, true>(p, stream); break; \
-  }
+// One enumerator per kernel instantiation launch_gemm can launch (each table row exists for MODE 0 and 1, the fused forms for
+// MODE 0 only).  A table row's enumerator is its variant id; the fused forms are 100 / 200 + the id of the tile form they share.
+enum GemmInst : int {
+#define X(id, fn, cg, rf, gen, ...) GEMM_V##id = id,
+  GEMM_TABLE(X)
+#undef X
+  // fused GEGLU backward (GemmP::gbwd_pre): persistent kernels with EPI = 3
+  GEMM_GBWD_256 = 127, GEMM_GBWD_128 = 128, GEMM_GBWD_64 = 131,
+  // folded LayerNorm (GemmP::ln_stats): the five tile forms the shape rule can pick for a plain GEMM
+  GEMM_LNF_LC256 = 224, GEMM_LNF_LC128 = 225, GEMM_LNF_256 = 227, GEMM_LNF_128 = 228, GEMM_LNF_64 = 231,
+};
+static constexpr GemmInst kGemmInsts[] = {
+#define X(id, fn, cg, rf, gen, ...) GEMM_V##id,
+    GEMM_TABLE(X)
+#undef X
+    GEMM_GBWD_256, GEMM_GBWD_128, GEMM_GBWD_64, GEMM_LNF_LC256, GEMM_LNF_LC128, GEMM_LNF_256, GEMM_LNF_128, GEMM_LNF_64};
+struct GemmVariantRow { int id; bool colscale_geglu, rowvec_fused; int generic_id; };
+static constexpr GemmVariantRow kGemmRows[] = {
+#define X(id, fn, cg, rf, gen, ...) {id, cg != 0, rf != 0, gen},
+    GEMM_TABLE(X)
+#undef X
+};
+static const GemmVariantRow* gemm_row(int id) {
+  for (const GemmVariantRow& r : kGemmRows)
+    if (r.id == id) return &r;
+  return nullptr;
+}
 
-static int pick_variant(const GemmP& p) {
-  if (g_gemm_variant >= 0) return g_gemm_variant;
-  const int cus = g_num_cus > 0 ? g_num_cus : 256;
+// Environment switches of the launcher, read once per process.
+struct GemmEnv {
+  bool defer;            // PEA_GEMM_DEFER: variant 35 (deferred lean epilogue) where the shape rule would take 25 / 28 with a lean epilogue
+  int ksw_mink;          // PEA_GEMM_KSW_MINK: smallest K for the K-split form 41 on one-round launches (default 0 = never)
+  bool slow_epilogue;    // PEA_GEMM_SLOW_EPILOGUE: never the batched-load epilogue (A/B switch)
+  bool pf_on;            // PEA_GEMM_PF=0 switches the next-op weight prefetch off (A/B)
+  long long pf_max;      // PEA_GEMM_PF_MAX_MB caps what one launch touches (default 64)
+};
+static const GemmEnv& gemm_env() {
+  static const GemmEnv e = {getenv("PEA_GEMM_DEFER") != nullptr, getenv("PEA_GEMM_KSW_MINK") ? atoi(getenv("PEA_GEMM_KSW_MINK")) : 0,
+                            getenv("PEA_GEMM_SLOW_EPILOGUE") != nullptr, !(getenv("PEA_GEMM_PF") && atoi(getenv("PEA_GEMM_PF")) == 0),
+                            (getenv("PEA_GEMM_PF_MAX_MB") ? atoll(getenv("PEA_GEMM_PF_MAX_MB")) : 64) << 20};
+  return e;
+}
+
+// Whether the batched-load epilogue (gemm_epilogue16_fast) applies to p: its preconditions.
+static bool gemm_epi_fast(const GemmP& p, const GemmEnv& env) {
+  // wave-tile rows of the 16x16x32 kernels are 32 or 64: a per-sample row vector must not change inside them
+  const bool rv_ok = !p.rowvec || (p.rows_per_batch % 64 == 0);
+  const bool gg_ok = !p.geglu_y || (p.ldy % 4 == 0 && (((unsigned long long)p.geglu_y & 7) == 0) && !p.res && !p.rowvec && !p.geglu_tanh);
+  return !env.slow_epilogue && !p.out_f32 && p.act == 0 && !p.preact && p.ksplit <= 1 && p.N % 16 == 0 && rv_ok && gg_ok &&
+         (p.geglu_y ? (!p.C || (p.ldc % 8 == 0 && (((unsigned long long)p.C & 15) == 0)))
+                    : (p.ldc % 8 == 0 && (((unsigned long long)p.C & 15) == 0))) &&
+         (!p.res || (p.ldres % 8 == 0 && (((unsigned long long)p.res & 15) == 0)));      // residual read as 16-byte pieces
+}
+
+// The shape rule: the variant id for a problem nobody pinned.
+static int pick_variant(const GemmP& p, bool epi_fast, int cus, const GemmEnv& env) {
   // measured on the step's shapes with scripts/gemm_bench.py / gemm_ksweep.py (profiles/r01_gemm_variants.log); all
-  // loader/consumer kernels with 16x16x32 MFMAs:
-  //   24 / 27 = 256x160 tile, 4x2 consumer waves (64x80 each) + 4 DMA waves, 3 stages   (27: persistent)
-  //   25 / 28 = 128x160 tile, 4x2 consumer waves (32x80 each) + 4 DMA waves, 3 stages   (28: persistent)
-  //   29      = 128x160 tile, 2x2 consumer waves (64x80 each) + 4 DMA waves, 4 stages, persistent
-  //   31      =  64x160 tile, 2x2 consumer waves (32x80 each) + 4 DMA waves, 4 stages, persistent
+  // loader/consumer kernels with 16x16x32 MFMAs.
   // A launch of at most one tile per CU gains nothing from the persistent form; beyond that it hides every
   // tile's prologue behind the previous tile's epilogue.
   if (p.N % 160 != 0 && p.N % 128 == 0 && p.M >= 1024)                // VAE widths 128/256/512: exact 128-wide tiles
@@ -1875,14 +1719,13 @@ static int pick_variant(const GemmP& p) {
   // the next tile's K-steps, the two MFMA waves of a SIMD taking turns
   // measured (in-run A/B, profiles/r01_gemm_variants.log): +4..11 % in the hot microbenchmark, nothing in situ -> off
   // unless PEA_GEMM_DEFER is set
-  static const bool defer = getenv("PEA_GEMM_DEFER") != nullptr;
-  const bool lean = defer && !p.out_f32 && !p.res && !p.rowvec && !p.act && !p.geglu_y && !p.gbwd_pre && !p.preact && !p.qscale_cols && p.ksplit <= 1 &&
+  const bool lean = env.defer && !p.out_f32 && !p.res && !p.rowvec && !p.act && !p.geglu_y && !p.gbwd_pre && !p.preact && !p.qscale_cols && p.ksplit <= 1 &&
                     p.ldc % 8 == 0 && (((unsigned long long)p.C & 15) == 0);
   // Row counts between the multiples the rules below were tuned on (6144 = the merged pass of a batch with dead teacher rows,
   // batch 3 / 6 per GPU): both tile heights leave a partial last round.  A 192-row tile (48 x 80 wave tiles) is taken when it
   // cuts rounds x rows by at least 10 % against what the rules would pick (never for the SDXL batch-4 / batch-8 shapes: their
   // tile counts are whole rounds).  No per-sample row vector (a 48-row wave tile may straddle two samples), batched-load epilogue only.
-  if (!p.rowvec && p.mode == 0 && p.epi_fast && p.M >= 1024) {
+  if (!p.rowvec && p.mode == 0 && epi_fast && p.M >= 1024) {
     const int t192 = cdiv(p.M, 192) * cdiv(p.N, 160);
     const int r128 = cdiv(t128, cus) * 128, r192 = cdiv(t192, cus) * 192, r256 = cdiv(t256, cus) * 256;
     const int cur = t128 <= cus ? r128 : (t256 <= cus ? (t256 > cus * 3 / 4 ? r256 : r128)
@@ -1890,8 +1733,7 @@ static int pick_variant(const GemmP& p) {
     if (r192 * 10 <= cur * 9) return t192 <= cus ? 39 : 40;
   }
   // one round of 128 x 160 tiles with a long K: the K-split form (41); PEA_GEMM_KSW_MINK sets the threshold (0 = never)
-  static const int ksw_mink = getenv("PEA_GEMM_KSW_MINK") ? atoi(getenv("PEA_GEMM_KSW_MINK")) : 0;
-  if (t128 <= cus && ksw_mink > 0 && p.K >= ksw_mink && (p.K / BK) % 2 == 0 && p.epi_fast && p.ksplit <= 1 && p.mode == 0 && t128 > cus * 5 / 8) return 41;
+  if (t128 <= cus && env.ksw_mink > 0 && p.K >= env.ksw_mink && (p.K / BK) % 2 == 0 && epi_fast && p.ksplit <= 1 && p.mode == 0 && t128 > cus * 5 / 8) return 41;
   if (t128 <= cus) return lean ? 35 : 25;            // at most one 128x160 tile per CU
   if (t256 <= cus) return t256 > cus * 3 / 4 ? 24 : (lean ? 35 : 28);
   // more than one 256x160 tile per CU: the large tile wins (less L2 -> LDS traffic per flop) unless its tile count
@@ -1901,15 +1743,67 @@ static int pick_variant(const GemmP& p) {
   return lean ? 35 : 28;
 }
 
+// THE decision: which instantiation a problem launches.  Pure: no HIP call, no global state -- `cus` is the CU count the launch may
+// occupy (0: 256), `forced` a pinned variant id or -1.  launch_gemm launches what this returns and nothing else decides.
+struct GemmDecision { GemmInst inst; bool epi_fast; };
+static GemmDecision gemm_decide(const GemmP& p, int cus, int forced, const GemmEnv& env) {
+  const bool epi_fast = gemm_epi_fast(p, env);
+  int v = forced >= 0 ? forced : pick_variant(p, epi_fast, cus > 0 ? cus : 256, env);
+  const GemmVariantRow* row = gemm_row(v);
+  // a row that cannot carry what the problem asks of its epilogue gives way to the persistent 128 x 160 form
+  if (row && !row->colscale_geglu && (p.qscale_cols || p.geglu_y)) v = 28;
+  if (row && !row->rowvec_fused && (p.gbwd_pre || p.ln_stats || (p.rowvec && epi_fast))) v = 28;
+  if (p.ksplit > 1) v = 18;                         // loader/consumer 128x128 (the only kernel with the split-K path)
+  if (p.gbwd_pre) {
+    // every tile form the shape rule picks for the FF output projection's dgrad maps to one of the three
+    return {v == 27 || v == 24 ? GEMM_GBWD_256 : (v == 31 ? GEMM_GBWD_64 : GEMM_GBWD_128), epi_fast};   // (128-row tiles for 27 / 24: +1.0-1.5 ms per step)
+  }
+  row = gemm_row(v);
+  if (!epi_fast && row && row->generic_id) v = row->generic_id;
+  if (p.ln_stats) {
+    switch (v) {
+      case 27: return {GEMM_LNF_256, epi_fast};
+      case 24: return {GEMM_LNF_LC256, epi_fast};
+      case 28: case 35: return {GEMM_LNF_128, epi_fast};
+      case 31: return {GEMM_LNF_64, epi_fast};
+      default: return {GEMM_LNF_LC128, epi_fast};   // 25 and the rest
+    }
+  }
+  return {gemm_row(v) ? (GemmInst)v : GEMM_V23, epi_fast};   // an id outside the table: the loader/consumer 128 x 128 form
+}
+
+int g_gemm_variant = -1;   // >= 0: forced (benchmark / debug)
+extern "C" void pea_debug_set_gemm_variant(int v) { g_gemm_variant = v; }
 int g_gemm_debug = 0;
 extern "C" void pea_debug_set_gemm_debug(int v) { g_gemm_debug = v; }
-// next-op weight prefetch: PEA_GEMM_PF=0 switches it off (A/B), PEA_GEMM_PF_MAX_MB caps what one launch touches (default 64);
 // pea_debug_set_gemm_prefetch arms the NEXT launch_gemm with a target (operator-level experiments: scripts/chain_probe.py)
-static const bool g_gemm_pf_on = !(getenv("PEA_GEMM_PF") && atoi(getenv("PEA_GEMM_PF")) == 0);
-static const long long g_gemm_pf_max = (getenv("PEA_GEMM_PF_MAX_MB") ? atoll(getenv("PEA_GEMM_PF_MAX_MB")) : 64) << 20;
 static const void* g_dbg_pf_ptr = nullptr;
 static long long g_dbg_pf_bytes = 0;
 extern "C" void pea_debug_set_gemm_prefetch(const void* p, long long bytes) { g_dbg_pf_ptr = p; g_dbg_pf_bytes = bytes; }
+
+// gemm_decide for tests, on a problem described by integers (include/pea_hip.h has the feature bits); no device needed
+extern "C" int pea_debug_gemm_dispatch(int M, int N, int K, int mode, int rows_per_batch, int features, int cus, int forced) {
+  if (M <= 0) return N >= 0 && N < (int)(sizeof(kGemmInsts) / sizeof(kGemmInsts[0])) ? (int)kGemmInsts[N] : -1;
+  GemmP p = {};
+  const bool al = (features & 1024) != 0;
+  char* const base = (char*)(uintptr_t)(al ? 0x1000 : 0x1004);   // never dereferenced
+  const int pad = al ? 0 : 4;
+  p.mode = mode; p.M = M; p.N = N; p.K = K; p.alpha = 1.f;
+  p.lda = K; p.ldw = K;
+  p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : M;
+  p.C = base; p.ldc = ((features & 64) ? 2 * N : N) + pad;
+  if (features & 1) { p.res = (const bf16*)base; p.ldres = N + pad; }
+  if (features & 2) { p.rowvec = (const bf16*)base; p.ldrv = N; }
+  if (features & 4) p.out_f32 = 1;
+  if (features & 8) p.act = 1;
+  if (features & 32) { p.geglu_y = (bf16*)base; p.ldy = N / 2 + pad; if (!(features & 16)) p.C = nullptr; }
+  else if (features & 16) { p.preact = (bf16*)base; p.ldpre = N + pad; }
+  if (features & 64) { p.gbwd_pre = (const bf16*)base; p.ldgp = 2 * N + pad; }
+  if (features & 128) { p.ln_stats = (const float*)base; p.ln_s = (const float*)base; }
+  if (features & 256) { p.qscale_cols = 16; p.qscale = 1.f; }
+  if (features & 512) p.ksplit = 2;
+  return gemm_decide(p, cus, forced, gemm_env()).inst;
+}
 
 int launch_gemm(const GemmP& p_in, hipStream_t stream) {
   const GemmP& p0 = p_in;
@@ -1944,73 +1838,45 @@ int launch_gemm(const GemmP& p_in, hipStream_t stream) {
     if (g_prof_on) { g_prof_tag[0] = p0.M; g_prof_tag[1] = p0.N; g_prof_tag[2] = p0.K; g_prof_tag[3] = (p0.res ? 1 : 0) | (p0.bias ? 2 : 0) | (p0.rowvec ? 4 : 0); }
     PROF_BEGIN(p0.mode ? 1 : 0, fl, by, stream);
   }
+  const GemmEnv& env = gemm_env();
   GemmP p = p_in;
   p.debug = g_gemm_debug;
   if (g_dbg_pf_ptr) { p.pf_ptr = g_dbg_pf_ptr; p.pf_bytes = g_dbg_pf_bytes; g_dbg_pf_ptr = nullptr; }
-  if (!g_gemm_pf_on || p.pf_bytes <= 0) { p.pf_ptr = nullptr; p.pf_bytes = 0; }
-  if (p.pf_bytes > g_gemm_pf_max) p.pf_bytes = g_gemm_pf_max;
+  if (!env.pf_on || p.pf_bytes <= 0) { p.pf_ptr = nullptr; p.pf_bytes = 0; }
+  if (p.pf_bytes > env.pf_max) p.pf_bytes = env.pf_max;
   SHAPECHK(p.qscale_cols % 16 == 0 && p.qscale_cols >= 0 && p.qscale_cols <= p.N && (!p.qscale_cols || (!p.act && !p.geglu_y && !p.gbwd_pre && p.ksplit <= 1)),
            "gemm: qscale_cols=%d must be a multiple of 16 within N, on a plain (no activation / GEGLU / split-K) epilogue", p.qscale_cols);
   if (!g_num_cus) HIPCHK(gemm_query_cus());
-  {
-    // wave-tile rows of the 16x16x32 kernels are 32 or 64: a per-sample row vector must not change inside them
-    static const bool slow_epi = getenv("PEA_GEMM_SLOW_EPILOGUE") != nullptr;     // A/B switch
-    const bool rv_ok = !p.rowvec || (p.rows_per_batch % 64 == 0);
-    const bool gg_ok = !p.geglu_y || (p.ldy % 4 == 0 && (((unsigned long long)p.geglu_y & 7) == 0) && !p.res && !p.rowvec && !p.geglu_tanh);
-    p.epi_fast = !slow_epi && !p.out_f32 && p.act == 0 && !p.preact && p.ksplit <= 1 && p.N % 16 == 0 && rv_ok && gg_ok &&
-                 (p.geglu_y ? (!p.C || (p.ldc % 8 == 0 && (((unsigned long long)p.C & 15) == 0)))
-                            : (p.ldc % 8 == 0 && (((unsigned long long)p.C & 15) == 0))) &&
-                 (!p.res || (p.ldres % 8 == 0 && (((unsigned long long)p.res & 15) == 0)));      // residual read as 16-byte pieces
-  }
-  int v = pick_variant(p);                                  // (reads p.epi_fast)
-  if (p.qscale_cols && (v == 34 || v == 35)) v = 28;        // the staged / deferred forms carry no column scale
-  if (p.geglu_y && (v == 34 || v == 35)) v = 28;            // ... and no GEGLU epilogue (34 drops the stash, 35 the output)
-  if ((p.gbwd_pre || p.ln_stats) && (v == 39 || v == 40)) v = 28;     // (those epilogues have no 192-row instantiation)
-  // the batched-load epilogue reads one row-vector entry per wave tile: a 48-row wave tile of the 192-row forms would straddle
-  // two samples (the shape rule never picks them with a row vector; a pinned variant must not either)
-  if (p.rowvec && p.epi_fast && (v == 39 || v == 40)) v = 28;
+  const GemmDecision d = gemm_decide(p, g_num_cus, g_gemm_variant, env);
+  p.epi_fast = d.epi_fast;
   if (p.ksplit > 1) {
     SHAPECHK(p.out_f32 && !p.accum_f32 && !p.bias && !p.res && !p.rowvec && !p.preact && p.act == 0 && p.mode == 0,
              "gemm: split-K writes plain fp32 partials");
-    v = 18;                                         // loader/consumer 128x128 (the only kernel with the K-split path)
   }
   if (p.gbwd_pre) {
-    // fused GEGLU backward: own instantiations of the persistent kernels (every tile form the shape rule picks for the FF
-    // output projection's dgrad maps to one of the three)
+    // fused GEGLU backward: own instantiations of the persistent kernels
     SHAPECHK(p.epi_fast && p.mode == 0 && !p.res && !p.rowvec && !p.bias && !p.geglu_y && !p.ln_stats && p.ldgp % 8 == 0 &&
                  p.ldc >= 2 * p.N && (((unsigned long long)p.gbwd_pre & 15) == 0),
              "gemm: the fused GEGLU backward needs the batched-load epilogue (bf16 [M][2N] output, no bias / residual / row vector)");
-    int rc;
-    if (v == 27 || v == 24) rc = launch_lcp<0, 256, 160, 4, 2, 4, 3, 0, 0, 3>(p, stream);   // (128-row tiles here: +1.0-1.5 ms per step)
-    else if (v == 31) rc = launch_lcp<0, 64, 160, 2, 2, 4, 4, 0, 0, 3>(p, stream);
-    else rc = launch_lcp<0, 128, 160, 4, 2, 4, 3, 0, 0, 3>(p, stream);
-    PROF_END(stream);
-    if (rc != PEA_OK) return rc;
-    HIPCHK(hipGetLastError());
-    return PEA_OK;
-  }
-  if (!p.epi_fast) {                                // the 256-row persistent kernels carry the batched-load epilogue only
-    if (v == 27 || v == 40) v = 28;
-    if (v == 33) v = 30;
-  }
-  int rc = PEA_OK;
-  if (p.ln_stats) {
-    // folded-LayerNorm instantiations of the five tile forms the shape rule can pick for a plain GEMM
+  } else if (p.ln_stats) {
     SHAPECHK(p.epi_fast && p.ln_s && p.alpha == 1.f && p.mode == 0 && !p.res && !p.rowvec,
              "gemm: the folded-LayerNorm epilogue needs the batched-load epilogue (bf16 output, no activation / residual)");
-    switch (v) {
-      case 27: rc = launch_lcp<0, 256, 160, 4, 2, 4, 3, 0, 0, 2>(p, stream); break;
-      case 24: rc = launch_lc<0, 256, 160, 4, 2, 4, 3, false, true, 1, true>(p, stream); break;
-      case 28: case 35: rc = launch_lcp<0, 128, 160, 4, 2, 4, 3, 0, 0, 2>(p, stream); break;
-      case 31: rc = launch_lcp<0, 64, 160, 2, 2, 4, 4, 0, 0, 2>(p, stream); break;
-      default: rc = launch_lc<0, 128, 160, 4, 2, 4, 3, false, true, 1, true>(p, stream); break;   // 25 and the rest
-    }
-    PROF_END(stream);
-    if (rc != PEA_OK) return rc;
-    HIPCHK(hipGetLastError());
-    return PEA_OK;
   }
-  if (p.mode == 0) { GEMM_VARIANTS(0) } else { GEMM_VARIANTS(1) }
+  int rc = PEA_OK;
+  switch (d.inst) {
+#define X(id, fn, cg, rf, gen, ...) \
+    case GEMM_V##id: rc = p.mode == 0 ? fn<0, __VA_ARGS__>(p, stream) : fn<1, __VA_ARGS__>(p, stream); break;
+    GEMM_TABLE(X)
+#undef X
+    case GEMM_GBWD_256: rc = launch_lcp<0, 256, 160, 4, 2, 4, 3, 0, 0, 3>(p, stream); break;
+    case GEMM_GBWD_128: rc = launch_lcp<0, 128, 160, 4, 2, 4, 3, 0, 0, 3>(p, stream); break;
+    case GEMM_GBWD_64: rc = launch_lcp<0, 64, 160, 2, 2, 4, 4, 0, 0, 3>(p, stream); break;
+    case GEMM_LNF_256: rc = launch_lcp<0, 256, 160, 4, 2, 4, 3, 0, 0, 2>(p, stream); break;
+    case GEMM_LNF_LC256: rc = launch_lc<0, 256, 160, 4, 2, 4, 3, false, true, 1, true>(p, stream); break;
+    case GEMM_LNF_128: rc = launch_lcp<0, 128, 160, 4, 2, 4, 3, 0, 0, 2>(p, stream); break;
+    case GEMM_LNF_64: rc = launch_lcp<0, 64, 160, 2, 2, 4, 4, 0, 0, 2>(p, stream); break;
+    case GEMM_LNF_LC128: rc = launch_lc<0, 128, 160, 4, 2, 4, 3, false, true, 1, true>(p, stream); break;
+  }
   PROF_END(stream);
   if (rc != PEA_OK) return rc;
   HIPCHK(hipGetLastError());
