@@ -135,6 +135,9 @@ int pea_op_groupnorm_bwd(const void* x, const void* dy, const float* gamma, cons
 /* LayerNorm over rows; stats fp32 [R][2]; dgamma/dbeta (fp32, accumulated) may be NULL */
 int pea_op_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats, int R, int C,
                          float eps, void* stream);
+/* the same over fp32 rows with an fp32 result and no statistics (the image-prompt projection) */
+int pea_op_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, int R, int C, float eps,
+                             void* stream);
 int pea_op_layernorm_bwd(const void* x, const void* dy, const float* gamma, const float* stats, void* dx,
                          float* dgamma, float* dbeta, int R, int C, int accum, void* stream);
 
@@ -152,6 +155,15 @@ int pea_op_attention_fwd_prescaled(const void* Q, int ldq, const void* K, int ld
 int pea_op_attention_fwd_masked(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
                                 float* lse, int B, int H, int Sq, int Skv, float scale, int causal, const int* kv_len,
                                 void* stream);
+/* Decoupled cross-attention of an image prompt (IP-Adapter), forward only, head_dim 64:
+ *   O = softmax(scale Q K^T) V + ip_scale * softmax(scale Q K2^T) V2
+ * two separate softmaxes over the same Q, in ONE launch that writes O once.  1 <= Skv <= 128 text keys, 1 <= Skv2 <= 32 image
+ * keys (K2 / V2 bf16 [B][Skv2][ldk2 / ldv2], ld* multiples of 8), any Sq >= 1.  q_prescaled: Q already carries scale * log2(e)
+ * (the same factor serves both score products).  kv_len (device int[B] or NULL) masks text keys only; lse (may be NULL) is that
+ * of the text softmax.  causal != 0 is refused, like every other shape outside the above, before any launch. */
+int pea_op_attention_fwd_ip(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
+                            const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
+                            float scale, float ip_scale, int q_prescaled, int causal, const int* kv_len, void* stream);
 /* dQ/dK/dV (dQ may be NULL; dK and dV together); delta: fp32 scratch [2][B][H][Sq] (row constants of the backward kernels); scratch: optional device
  * buffer of pea_op_attention_bwd_scratch_bytes(...) bytes enabling the query-split dK/dV form used when the
  * key count is small (cross-attention); NULL = single pass                                            */
@@ -341,6 +353,28 @@ int pea_unet_set_residuals(void* unet, int n, const void* const* ptrs, int dtype
 int pea_unet_set_inpaint_cond(void* unet, const float* mask, const float* masked_latents, int cond_batch, int latent_batch,
                               void* stream);
 int pea_unet_clear_inpaint_cond(void* unet);
+/* Image prompt (IP-Adapter, `ip-adapter_sdxl_vit-h` and its kin): every cross-attention layer gets a second, independent
+ * key / value projection `to_k_ip` / `to_v_ip` over n_tokens image tokens (1..32) and runs the decoupled attention of
+ * pea_op_attention_fwd_ip.  The UNet's own weights do not change.
+ * pea_unet_ip_plan (host only): cross-attention layers, width of the stacked to_k_ip | to_v_ip projection (that of the text K|V
+ * stack) and its parameter count.  pea_unet_ip_create allocates that stack ([cols][cross_dim] bf16; column layout identical to
+ * the text stack: pea_unet_stacked_layout(which = 0) with to_k / to_v read as to_k_ip / to_v_ip) and the image K|V buffer
+ * [B * n_tokens][cols] bf16, both outside the activation arena (they survive pea_unet_release_activations).  Refused: contexts
+ * with PEA_UNET_GRAD (there is no backward through the image branch), ControlNet handles, configs with padded heads (head_dim
+ * != 64), a context length above 128.
+ * pea_unet_ip_load_weight: key `<attn2 prefix>.to_k_ip.weight` / `.to_v_ip.weight`, fp32 device [C][cross_dim].
+ * pea_unet_ip_set_tokens: fp32 device [B][n_tokens][cross_dim] -> ONE GEMM into the image K|V buffer, once per image; from then
+ * on every pea_unet_forward of this context runs the decoupled attention, with the scale of pea_unet_ip_set_scale (default 1,
+ * read at launch; 0 launches the plain attention) until pea_unet_ip_clear.  pea_unet_ip_destroy frees the state.
+ * pea_unet_ip_export_kv (parity instrumentation): the image K|V buffer as fp32 [rows][cols]; out may be NULL (sizes only). */
+int pea_unet_ip_plan(const pea_unet_config* cfg, int n_tokens, int* n_layers, int* cols, long long* n_params);
+int pea_unet_ip_create(void* unet, int n_tokens);
+int pea_unet_ip_load_weight(void* unet, const char* key, const float* src, long long numel, void* stream);
+int pea_unet_ip_set_tokens(void* unet, const float* tokens, void* stream);
+int pea_unet_ip_set_scale(void* unet, float scale);
+int pea_unet_ip_clear(void* unet);
+int pea_unet_ip_destroy(void* unet);
+int pea_unet_ip_export_kv(void* unet, float* out, long long* rows, int* cols, void* stream);
 int pea_unet_destroy(void* unet);
 
 /* ControlNet (`self.controlnet(control_model_input, t, encoder_hidden_states=..., controlnet_cond=image,

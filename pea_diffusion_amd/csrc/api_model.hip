@@ -448,6 +448,134 @@ int pea_unet_clear_inpaint_cond(void* h) {
   u->inp_cond_b = u->inp_lat_b = 0;
   return PEA_OK;
 }
+// ------------------------------------------------------------------------------ image prompt (IP-Adapter)
+// what a graph must be to take one; on success *kv_op is the stacked text K|V projection
+static int ip_check(const Tape& u, int n_tokens, const Op** kv_op) {
+  if (u.graph != 0 || u.t_kvall < 0) { pea_set_error("pea_unet_ip: not a UNet handle (ControlNet graphs get no image prompt)"); return PEA_E_INVALID; }
+  if (u.needs_grad) {
+    pea_set_error("pea_unet_ip: this context was created with PEA_UNET_GRAD; there is no backward through the image branch");
+    return PEA_E_STATE;
+  }
+  SHAPECHK(n_tokens >= 1 && n_tokens <= 32, "pea_unet_ip: n_tokens=%d (1..32 image tokens)", n_tokens);
+  SHAPECHK(u.L <= 128, "pea_unet_ip: context length %d (the decoupled attention takes at most 128 text keys)", u.L);
+  *kv_op = nullptr;
+  for (const Op& o : u.ops)
+    if (o.out == u.t_kvall && o.fused >= 0) *kv_op = &o;
+  if (!*kv_op) { pea_set_error("pea_unet_ip: stacked K|V projection not found"); return PEA_E_STATE; }
+  for (const WSlot& s : u.slots)
+    if (s.fused_parent == (*kv_op)->fused && s.pad_mode) {
+      pea_set_error("pea_unet_ip: '%s' has padded heads (head_dim %d); the decoupled attention is built for head_dim 64", s.name.c_str(), s.pad_d);
+      return PEA_E_SHAPE;
+    }
+  return PEA_OK;
+}
+#define IP_HANDLE(h, what)                                                                     \
+  NOTNULL(h, what);                                                                            \
+  Tape* u = (Tape*)h;                                                                          \
+  if (!u->ip) { pea_set_error("%s: call pea_unet_ip_create first", what); return PEA_E_STATE; }
+int pea_unet_ip_plan(const pea_unet_config* cfg, int n_tokens, int* n_layers, int* cols, long long* n_params) {
+  NOTNULL(cfg, "pea_unet_ip_plan");
+  Tape u;
+  memcpy(&u.cfg, cfg, sizeof(PeaUnetCfg));
+  // layers, stack width and parameters depend on the config alone: any batch / size / context length plans them.  The context
+  // length is therefore NOT validated here (ip_check's L <= 128 cannot fire); pea_unet_ip_create checks the real context
+  u.B = 1; u.H = 64; u.W = 64; u.L = 77; u.needs_grad = false;
+  u.plan_only = true;
+  int rc = u.build();
+  if (rc == PEA_OK) rc = u.alloc();
+  if (rc != PEA_OK) return rc;
+  const Op* kv = nullptr;
+  RCX(ip_check(u, n_tokens, &kv));
+  int members = 0;
+  for (const WSlot& s : u.slots) members += s.fused_parent == kv->fused && s.kind == W_LINEAR;
+  if (n_layers) *n_layers = members / 2;
+  if (cols) *cols = u.kvall_total;
+  if (n_params) *n_params = (long long)u.kvall_total * u.cfg.cross_dim;
+  return PEA_OK;
+}
+int pea_unet_ip_create(void* h, int n_tokens) {
+  NOTNULL(h, "pea_unet_ip_create");
+  Tape* u = (Tape*)h;
+  const Op* kv = nullptr;
+  RCX(ip_check(*u, n_tokens, &kv));
+  RCX(pea_unet_ip_destroy(h));                       // an adapter already loaded: replaced, behind whatever still reads it
+  Tape::IpState* ip = new Tape::IpState();
+  ip->n = n_tokens; ip->cols = u->kvall_total; ip->fused = kv->fused;
+  for (const WSlot& s : u->slots) ip->loaded.push_back(!(s.fused_parent == kv->fused && s.kind == W_LINEAR));
+  const size_t rows = (size_t)u->B * n_tokens, K = (size_t)u->cfg.cross_dim;
+  if (hipMalloc((void**)&ip->w, (size_t)ip->cols * K * 2) != hipSuccess || hipMalloc((void**)&ip->kv, rows * ip->cols * 2) != hipSuccess ||
+      hipMalloc((void**)&ip->tok, rows * K * 2) != hipSuccess) {
+    pea_set_error("pea_unet_ip_create: out of device memory (%zu bytes of weights)", (size_t)ip->cols * K * 2);
+    delete ip;
+    return PEA_E_HIP;
+  }
+  u->ip = ip;
+  return PEA_OK;
+}
+int pea_unet_ip_load_weight(void* h, const char* key, const float* src, long long numel, void* stream) {
+  IP_HANDLE(h, "pea_unet_ip_load_weight");
+  NOTNULL(key, "pea_unet_ip_load_weight");
+  NOTNULL(src, "pea_unet_ip_load_weight");
+  std::string name(key);
+  const size_t at = name.rfind("_ip.weight");
+  int slot = -1;
+  if (at != std::string::npos && at + 10 == name.size()) {
+    auto it = u->slot_by_name.find(name.substr(0, at) + ".weight");      // to_k_ip -> the text stack's to_k of the same layer
+    if (it != u->slot_by_name.end() && u->slots[it->second].fused_parent == u->ip->fused) slot = it->second;
+  }
+  if (slot < 0) { pea_set_error("pea_unet_ip_load_weight: '%s' is no to_k_ip / to_v_ip weight of this UNet", key); return PEA_E_NOTFOUND; }
+  const WSlot& w = u->slots[slot];
+  SHAPECHK(numel == w.numel, "pea_unet_ip_load_weight: '%s' has %lld elements, expected %lld ([%d][%d])", key, numel, w.numel, w.d0, w.d1);
+  RCX(launch_cast_f32_bf16(src, u->ip->w + (size_t)w.row_off * w.d1, numel, (hipStream_t)stream));
+  u->ip->loaded[slot] = 1;
+  return PEA_OK;
+}
+int pea_unet_ip_set_tokens(void* h, const float* tokens, void* stream) {
+  IP_HANDLE(h, "pea_unet_ip_set_tokens");
+  NOTNULL(tokens, "pea_unet_ip_set_tokens");
+  Tape::IpState& ip = *u->ip;
+  for (size_t i = 0; i < ip.loaded.size(); ++i)
+    if (!ip.loaded[i]) {
+      const std::string& n = u->slots[i].name;
+      pea_set_error("pea_unet_ip_set_tokens: '%s_ip.weight' was never loaded", n.substr(0, n.size() - 7).c_str());
+      return PEA_E_STATE;
+    }
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = u->B * ip.n, K = u->cfg.cross_dim;
+  RCX(launch_cast_f32_bf16(tokens, ip.tok, (long long)rows * K, s));
+  GemmP p; fill_gemm(p);
+  p.A = ip.tok; p.lda = K; p.M = rows; p.K = K; p.N = ip.cols; p.W = ip.w; p.ldw = K; p.C = ip.kv; p.ldc = ip.cols;
+  RCX(launch_gemm(p, s));
+  ip.live = true;
+  return PEA_OK;
+}
+int pea_unet_ip_set_scale(void* h, float scale) {
+  IP_HANDLE(h, "pea_unet_ip_set_scale");
+  u->ip->scale = scale;
+  return PEA_OK;
+}
+int pea_unet_ip_clear(void* h) {
+  NOTNULL(h, "pea_unet_ip_clear");
+  if (((Tape*)h)->ip) ((Tape*)h)->ip->live = false;
+  return PEA_OK;
+}
+int pea_unet_ip_destroy(void* h) {
+  NOTNULL(h, "pea_unet_ip_destroy");
+  Tape* u = (Tape*)h;
+  if (u->ip) HIPCHK(hipDeviceSynchronize());       // a queued forward may still read the buffers
+  delete u->ip;
+  u->ip = nullptr;
+  return PEA_OK;
+}
+int pea_unet_ip_export_kv(void* h, float* out, long long* rows, int* cols, void* stream) {
+  IP_HANDLE(h, "pea_unet_ip_export_kv");
+  const long long r = (long long)u->B * u->ip->n;
+  if (rows) *rows = r;
+  if (cols) *cols = u->ip->cols;
+  if (!out) return PEA_OK;
+  if (!u->ip->live) { pea_set_error("pea_unet_ip_export_kv: no tokens set"); return PEA_E_STATE; }
+  return launch_cast_bf16_f32(u->ip->kv, out, r * u->ip->cols, (hipStream_t)stream);
+}
 int pea_unet_num_weights(void* h) { return h ? (int)((Tape*)h)->slots.size() : 0; }
 int pea_unet_weight_info(void* h, int i, char* name, int name_len, long long* numel, int* kind, int* d0, int* d1) {
   NOTNULL(h, "pea_unet_weight_info");

@@ -235,6 +235,11 @@ int pea_op_layernorm_bwd(const void* x, const void* dy, const float* gamma, cons
                               accum ? (const bf16*)dx : nullptr, (hipStream_t)stream);
 }
 
+int pea_op_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, int R, int C, float eps,
+                             void* stream) {
+  return launch_layernorm_fwd_f32(x, gamma, beta, y, R, C, eps, (hipStream_t)stream);
+}
+
 int pea_op_attention_fwd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
                          float* lse, int B, int H, int Sq, int Skv, float scale, int nd, void* stream) {
   return attention_fwd_impl(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, nd, 0, stream);
@@ -253,6 +258,18 @@ int pea_op_attention_fwd_masked(const void* Q, int ldq, const void* K, int ldk, 
   p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
   p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = 1;
   p.causal = causal; p.kv_len = kv_len;
+  return launch_attention_fwd(p, (hipStream_t)stream);
+}
+int pea_op_attention_fwd_ip(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
+                            const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
+                            float scale, float ip_scale, int q_prescaled, int causal, const int* kv_len, void* stream) {
+  SHAPECHK(K2 && V2 && Skv2 >= 1, "pea_op_attention_fwd_ip: no image keys (Skv2=%d)", Skv2);
+  AttnP p;
+  memset(&p, 0, sizeof(p));
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
+  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = 1;
+  p.q_prescaled = q_prescaled; p.causal = causal; p.kv_len = kv_len;
+  p.K2 = (const bf16*)K2; p.V2 = (const bf16*)V2; p.ldk2 = ldk2; p.ldv2 = ldv2; p.Skv2 = Skv2; p.scale2 = ip_scale;
   return launch_attention_fwd(p, (hipStream_t)stream);
 }
 int pea_op_attention_bwd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O,

@@ -952,13 +952,28 @@ __device__ __forceinline__ float xhalf_sum(float x) {
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
   return a + b;
 }
-template <int KB>
-__global__ __launch_bounds__(256, 3) void xattn_fwd_kernel(const AttnP p, int upw) {
+//
+// IP: the decoupled cross-attention of an image prompt (IP-Adapter), O = softmax(s Q K^T) V + scale2 * softmax(s Q K2^T) V2
+// with 1..32 image keys (AttnP::K2 / V2 / Skv2).  Unfused that is two of these launches and an add: Q read twice, three
+// O-sized writes and two O-sized reads, where the output alone is already most of this kernel's traffic.  Here the image
+// keys are ONE more 32-key block on the resident Q fragments: S2 from the same qf, a softmax of its own (own max, own sum --
+// a spike in either key set cannot underflow the other), O2^T = V2^T P2^T, and oacc * inv + scale2 * (oacc2 * inv2) in fp32,
+// rounded to bf16 once, through the same LDS image.  K2 / V2 are staged as two 32-row HALF tiles behind the Q images
+// (2 x 4 096 bytes: 75 776 bytes with 77 text keys, still two workgroups per CU; two full tiles would not fit, and the free
+// fourth block of the text tiles would only serve <= 96 text keys).  kv_len masks text keys only; lse is the text softmax's.
+// scale2 rides in inv2 (scale2 / sum): one multiply per element fewer, and scale2 = 0 returns the text term bit for bit.
+// The LDS allows two workgroups per CU at most, so the launch bound asks for no more.  What hipcc makes of the four instances
+// (profiles/ip_adapter_bench_regs.txt): 104 / 106 / 131 / 163 VGPRs for 1..4 text key blocks, no AGPRs, no scratch -- against
+// 68 / 88 / 91 / 130 without the image keys; all under the 256 a two-workgroup CU leaves a wave.
+template <int KB, bool IP = false>
+__global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP p, int upw) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KT = (KB + 1) / 2;                               // 64-key tiles
   char* const Ksm = smem;
   char* const Vsm = smem + KT * TILE_BYTES;
   char* const Osm = smem + 2 * KT * TILE_BYTES;                  // 4 waves x 32 rows x 144 bytes
+  char* const K2sm = Osm + 4 * 32 * 144 + 4 * 4096;              // IP: image keys, then image values (32 rows x 128 bytes each)
+  char* const V2sm = K2sm + 4096;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
@@ -977,6 +992,12 @@ __global__ __launch_bounds__(256, 3) void xattn_fwd_kernel(const AttnP p, int up
     for (int t = 0; t < KT; ++t) {
       stage_tile(ksrc, t * 64, Ksm + t * TILE_BYTES, wave);
       stage_tile(vsrc, t * 64, Vsm + t * TILE_BYTES, wave);
+    }
+    if constexpr (IP) {                                          // waves 0 / 1: the 32 rows of K2, waves 2 / 3: those of V2
+      const bool isv = wave >= 2;
+      const bf16* b2 = isv ? p.V2 + (long long)b * p.Skv2 * p.ldv2 : p.K2 + (long long)b * p.Skv2 * p.ldk2;
+      const TileSrc src2 = tile_src(b2 + head * 64, isv ? p.ldv2 : p.ldk2, p.Skv2, wave & 1, lane);
+      stage_tile(src2, 0, isv ? V2sm : K2sm, wave & 1);
     }
   }
   int rf_off[4], tr_off[2][2];
@@ -1031,6 +1052,17 @@ __global__ __launch_bounds__(256, 3) void xattn_fwd_kernel(const AttnP p, int up
           sacc[kb][r] = key < skv_b ? sacc[kb][r] : -INFINITY;
         }
       }
+    [[maybe_unused]] f32x16 sacc2;                               // IP: S2^T = K2 . Q^T, slots past Skv2 -inf
+    if constexpr (IP) {
+      const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      sacc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(K2sm + rf_off[0]), qf[0], zero16, 0, 0, 0);
+#pragma unroll
+      for (int s = 1; s < 4; ++s) sacc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(K2sm + rf_off[s]), qf[s], sacc2, 0, 0, 0);
+      if (p.Skv2 < 32) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc2[r] = (r & 3) + 8 * (r >> 2) + 4 * fh < p.Skv2 ? sacc2[r] : -INFINITY;
+      }
+    }
     float mx = sacc[0][0];
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb)
@@ -1066,6 +1098,31 @@ __global__ __launch_bounds__(256, 3) void xattn_fwd_kernel(const AttnP p, int up
       }
     }
     const float inv = 1.f / l_tot;
+    [[maybe_unused]] f32x16 oacc2[2];
+    [[maybe_unused]] float inv2 = 0.f;                           // scale2 / (sum of the image softmax)
+    if constexpr (IP) {
+      float mx2 = sacc2[0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) mx2 = fmaxf(mx2, sacc2[r]);
+      const float mc2 = xhalf_max(mx2) * c;
+      float ls2 = 0.f;
+      bf16x8 pf2[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = fast_exp2(fmaf(sacc2[r], c, -mc2));
+        ls2 += e;
+        pf2[r >> 3][r & 7] = (bf16)e;
+      }
+      inv2 = p.scale2 / xhalf_sum(ls2);
+      const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int db = 0; db < 2; ++db) {
+        oacc2[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(read_transposed_frag_at(V2sm + tr_off[db][0], V2sm + tr_off[db][1]),
+                                                            pf2[0], zero16, 0, 0, 0);
+        oacc2[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            read_transposed_frag_at(V2sm + tr_off[db][0] + 2048, V2sm + tr_off[db][1] + 2048), pf2[1], oacc2[db], 0, 0, 0);
+      }
+    }
     if (qvalid && p.lse && fh == 0)
       p.lse[((long long)b * p.H + head) * p.Sq + qrow] = mx * (p.q_prescaled ? 0.6931471805599453f : p.scale) + log2f(l_tot) * 0.6931471805599453f;
     // O leaves through a per-wave LDS image (32 rows x 128 bytes, 144-byte pitch): the accumulator layout has a query row
@@ -1078,7 +1135,10 @@ __global__ __launch_bounds__(256, 3) void xattn_fwd_kernel(const AttnP p, int up
       for (int g = 0; g < 4; ++g) {
         bf16x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16)(oacc[db][4 * g + j] * inv);
+        for (int j = 0; j < 4; ++j) {
+          if constexpr (IP) o[j] = (bf16)(oacc[db][4 * g + j] * inv + oacc2[db][4 * g + j] * inv2);
+          else o[j] = (bf16)(oacc[db][4 * g + j] * inv);
+        }
         *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
       }
     {
@@ -2201,6 +2261,17 @@ static int g_attn_xattn = getenv("PEA_XATTN_OFF") ? 0 : 1;               // PEA_
 extern "C" void pea_debug_set_attn_xattn(int v) { g_attn_xattn = v; }
 extern "C" void pea_debug_set_attn_tr(int v) { g_attn_use_tr = v; }
 
+// a second key set (AttnP::K2, the image prompt's): forward only, served by xattn_fwd_kernel<KB, true> alone
+static int attn_check_ip(const AttnP& p) {
+  SHAPECHK(p.K2 != nullptr && p.V2 != nullptr, "attention: a second key set needs both K2 and V2");
+  SHAPECHK(p.nd == 1, "attention: a second key set needs head_dim 64 (nd=%d)", p.nd);
+  SHAPECHK(!p.causal && !p.bias, "attention: a second key set cannot be combined with a causal mask or a score bias");
+  SHAPECHK(p.Skv <= 128, "attention: a second key set needs at most 128 text keys (Skv=%d)", p.Skv);
+  SHAPECHK(p.Skv2 >= 1 && p.Skv2 <= 32, "attention: the second key set holds 1..32 keys (Skv2=%d)", p.Skv2);
+  SHAPECHK(p.ldk2 % 8 == 0 && p.ldv2 % 8 == 0 && p.ldk2 >= 64 * p.H && p.ldv2 >= 64 * p.H,
+           "attention: ldk2 / ldv2 must be multiples of 8 and hold every head (ldk2=%d ldv2=%d)", p.ldk2, p.ldv2);
+  return PEA_OK;
+}
 static int attn_check(const AttnP& p) {
   SHAPECHK(p.B > 0 && p.H > 0 && p.Sq > 0 && p.Skv > 0, "attention: empty problem");
   SHAPECHK(p.nd >= 1 && p.nd <= 3, "attention: padded head_dim must be 64, 128 or 192 (nd=%d)", p.nd);
@@ -2228,12 +2299,13 @@ static int launch_lds(dim3 grid, int bytes, hipStream_t s, const Args&... args) 
                  : launch_lds<KERNEL_NOTR>(grid, lds, s, p, ##__VA_ARGS__))
 
 // run-time (key blocks of 32, prescaled Q) -> instantiation, one dispatch per cross-attention kernel family
+template <bool IP = false>                                         // IP: with a second key set (AttnP::K2)
 static int launch_xattn_fwd(int kb, dim3 grid, int lds, hipStream_t s, const AttnP& p, int upw) {
   switch (kb) {
-    case 1: return launch_lds<xattn_fwd_kernel<1>>(grid, lds, s, p, upw);
-    case 2: return launch_lds<xattn_fwd_kernel<2>>(grid, lds, s, p, upw);
-    case 3: return launch_lds<xattn_fwd_kernel<3>>(grid, lds, s, p, upw);
-    default: return launch_lds<xattn_fwd_kernel<4>>(grid, lds, s, p, upw);
+    case 1: return launch_lds<xattn_fwd_kernel<1, IP>>(grid, lds, s, p, upw);
+    case 2: return launch_lds<xattn_fwd_kernel<2, IP>>(grid, lds, s, p, upw);
+    case 3: return launch_lds<xattn_fwd_kernel<3, IP>>(grid, lds, s, p, upw);
+    default: return launch_lds<xattn_fwd_kernel<4, IP>>(grid, lds, s, p, upw);
   }
 }
 static int launch_xattn_bwd1(int kb, dim3 grid, hipStream_t s, const AttnP& p, int upw) {
@@ -2265,14 +2337,17 @@ static int attn_fwd_nd(const AttnP& p, hipStream_t s) {
   const dim3 grid(cdiv(p.Sq, 128), p.H, p.B);
   constexpr int lq = 2 * 2 * ND * TILE_BYTES;
   if constexpr (ND == 1) {
-    if (g_attn_xattn && g_attn_use_tr && p.Skv <= 128 && !p.causal && !p.bias && p.Sq >= 128) {   // cross-attention: K / V resident
+    // cross-attention: K / V resident.  With a second key set (attn_check_ip has passed) always, at any query count: there
+    // is no other kernel for it
+    if (p.K2 || (g_attn_xattn && g_attn_use_tr && p.Skv <= 128 && !p.causal && !p.bias && p.Sq >= 128)) {
       const int kb = cdiv(p.Skv, 32), kt = (kb + 1) / 2;
-      const int lds = 2 * kt * TILE_BYTES + 4 * 32 * 144 + 4 * 4096;
+      const int lds = 2 * kt * TILE_BYTES + 4 * 32 * 144 + 4 * 4096 + (p.K2 ? 2 * 4096 : 0);
       const int nu = cdiv(p.Sq, 128);
       const long long units = (long long)p.B * p.H * nu;
-      int upw = (int)((units + 511) / 512);                       // one round of two workgroups per CU (66 KB of LDS each)
+      int upw = (int)((units + 511) / 512);                       // one round of two workgroups per CU (66 KB of LDS each, 74 KB with image keys)
       upw = upw < 1 ? 1 : (upw > nu ? nu : upw);
-      return launch_xattn_fwd(kb, dim3(cdiv(nu, upw), p.H, p.B), lds, s, p, upw);
+      const dim3 xgrid(cdiv(nu, upw), p.H, p.B);
+      return p.K2 ? launch_xattn_fwd<true>(kb, xgrid, lds, s, p, upw) : launch_xattn_fwd(kb, xgrid, lds, s, p, upw);
     }
   }
   if (p.causal || p.kv_len || p.bias) {       // text-encoder masks / score bias: separate instance (head_dim 64 only)
@@ -2335,8 +2410,13 @@ int launch_attention_fwd(const AttnP& p0, hipStream_t s) {
   int rc = attn_check(p);
   if (rc) return rc;
   SHAPECHK(p.ldo % 4 == 0, "attention: ldo %% 4");
+  if (p.K2 || p.V2) {
+    rc = attn_check_ip(p);
+    if (rc) return rc;
+  }
   if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = p.nd; }
-  PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * p.Skv * 64 * p.nd, 2.0 * p.B * p.H * 64 * p.nd * (2.0 * p.Sq + 2.0 * p.Skv), s);
+  const int keys = p.Skv + (p.K2 ? p.Skv2 : 0);                    // both key sets: one more score / value product each
+  PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * keys * 64 * p.nd, 2.0 * p.B * p.H * 64 * p.nd * (2.0 * p.Sq + 2.0 * keys), s);
   rc = p.nd == 1 ? attn_fwd_nd<1>(p, s) : p.nd == 2 ? attn_fwd_nd<2>(p, s) : attn_fwd_nd<3>(p, s);
   PROF_END(s);
   if (rc) return rc;

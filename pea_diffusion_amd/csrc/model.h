@@ -184,6 +184,18 @@ struct Tape {
   int time_cond_dim = 0;
   int t_tcond = -1;
   int set_timestep_cond(const float* cond, hipStream_t s);
+  // Image prompt (IP-Adapter, graph 0, inference only; api_model.hip: pea_unet_ip_*): a second K|V stack over n image tokens,
+  // columns laid out as the text stack's (t_kvall), so a cross-attention op finds its image keys / values at its own bcol / ccol.
+  // While `live` (and scale != 0) forward() hands them to the attention as AttnP::K2 / V2.  Outside the arenas: release_acts keeps it.
+  struct IpState {
+    int n = 0, cols = 0, fused = -1;       // image tokens per sample; width of the stack; the text stack's FusedMat
+    bf16 *w = nullptr, *kv = nullptr, *tok = nullptr;   // [cols][cross_dim], [B*n][cols], [B*n][cross_dim]
+    std::vector<char> loaded;              // per member of the stack, in slot order
+    bool live = false;
+    float scale = 1.f;
+    ~IpState() { for (bf16* b : {w, kv, tok}) if (b) (void)hipFree(b); }
+  };
+  IpState* ip = nullptr;
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

@@ -717,6 +717,34 @@ int launch_layernorm_fwd(const bf16* x, const float* gamma, const float* beta, b
   return PEA_OK;
 }
 
+// LayerNorm over fp32 rows with an fp32 result: the image-prompt projection's few rows (batch x image tokens), whose consumer
+// takes fp32.  One wave per row, two passes over the row (it is read from cache the second and third time).
+__global__ __launch_bounds__(256) void ln_fwd_f32_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* __restrict__ y, int R, int C,
+                                                         float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= R) return;
+  const float* xr = x + (long long)row * C;
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += xr[c];
+  const float mean = wave_sum(s) / (float)C;
+  float q = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float d = xr[c] - mean;
+    q += d * d;
+  }
+  const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+  for (int c = lane; c < C; c += 64) y[(long long)row * C + c] = (xr[c] - mean) * rstd * gamma[c] + beta[c];
+}
+int launch_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, int R, int C, float eps,
+                             hipStream_t s) {
+  SHAPECHK(R > 0 && C > 0, "layernorm (fp32): empty problem");
+  hipLaunchKernelGGL(ln_fwd_f32_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, x, gamma, beta, y, R, C, eps);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
 // T5LayerNorm (mT5 student text tower, train_sdxl_zh.py:108-112): y = x * rsqrt(mean(x^2) + eps) * w -- no mean
 // subtraction, no bias.  One wave per LN_NR rows, the rows live in registers (as ln_fwd_kernel).
 template <int NCH>

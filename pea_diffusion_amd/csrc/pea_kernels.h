@@ -92,6 +92,8 @@ int launch_layernorm_fwd(const bf16* x, const float* gamma, const float* beta, b
                          float eps, hipStream_t s);
 // (mean, rstd) per row only; and the LayerNorm -> Linear fold (norm.hip: ln_fold_kernel)
 int launch_rmsnorm_fwd(const bf16* x, const float* gamma, bf16* y, int R, int C, float eps, hipStream_t s);
+int launch_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, int R, int C, float eps,
+                             hipStream_t s);   // fp32 rows in, fp32 rows out (no statistics kept)
 int launch_layernorm_stats(const bf16* x, float* stats, int R, int C, float eps, hipStream_t s);
 int launch_ln_fold(const bf16* W, int ldw, const float* gamma, const float* beta, const float* bias, bf16* Wf, float* svec,
                    float* tvec, int N, int K, hipStream_t s);
@@ -120,6 +122,11 @@ struct AttnP {
   int q_prescaled;                 // Q already holds q * scale * log2(e) (GemmP::qscale in the producing projection): scores leave the
                                    // MFMA in the log2 domain with no further rounding; dQ is still the gradient w.r.t. the UNSCALED q
   const float* bias;               // forward, masked instance only: additive score bias [H][Sq][Skv] in the LOG2 domain (T5 relative positions), may be null
+  // forward only, head_dim 64, <= 128 keys: a second, independent key set over the same Q (IP-Adapter's image tokens),
+  //   O = softmax(scale Q K^T) V + scale2 * softmax(scale Q K2^T) V2,   1 <= Skv2 <= 32, batch stride Skv2 * ldk2 / ldv2.
+  // kv_len masks K / V only and lse stays that of the first softmax.  Null K2 (a memset struct): no second key set.
+  const bf16 *K2, *V2; int ldk2, ldv2, Skv2;
+  float scale2;
 };
 int attention_bwd_nsplit(int B, int H, int Sq, int Skv);
 size_t attention_bwd_scratch_bytes(int B, int H, int Sq, int Skv, int nd = 1);

@@ -266,6 +266,7 @@ Tape::~Tape() {
   if (rel_bucket) (void)hipFree(rel_bucket);
   if (cross_kvlen) (void)hipFree(cross_kvlen);
   if (inp_buf) (void)hipFree(inp_buf);
+  delete ip;
 }
 
 int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s) {
@@ -670,6 +671,9 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
         p.q_prescaled = o.pre;
         if (o.mask & 4) p.bias = rel_bias;
         if (cross_kvlen && o.b == t_kvall) p.kv_len = cross_kvlen;
+        if (ip && ip->live && ip->scale != 0.f && o.b == t_kvall) {    // image prompt: the layer's own columns of the image K|V
+          p.K2 = ip->kv + o.bcol; p.V2 = ip->kv + o.ccol; p.ldk2 = p.ldv2 = ip->cols; p.Skv2 = ip->n; p.scale2 = ip->scale;
+        }
         RC(launch_attention_fwd(p, s));
         break;
       }

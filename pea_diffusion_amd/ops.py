@@ -222,8 +222,12 @@ def groupnorm_bwd(x, dy, gamma, beta, stats, groups=32, silu=False, accum_into=N
 
 
 def layernorm_fwd(x, gamma, beta, eps=1e-5):
+    """bf16 rows -> (bf16 rows, stats [R,2]); fp32 rows -> (fp32 rows, None)"""
     R, C = x.shape
     y = torch.empty_like(x)
+    if x.dtype == torch.float32:
+        check(lib().pea_op_layernorm_fwd_f32(ptr(x), ptr(gamma), ptr(beta), ptr(y), R, C, eps, stream_ptr()))
+        return y, None
     stats = torch.empty(R, 2, device=x.device, dtype=torch.float32)
     check(lib().pea_op_layernorm_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(stats), R, C, eps, stream_ptr()))
     return y, stats
@@ -262,6 +266,22 @@ def attention_fwd(q, k, v, heads, scale=None, q_prescaled=False):
     check(fn(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, ptr(lse),
                                      B, heads, Sq, Skv, scale, nd, stream_ptr()))
     return o, lse
+
+
+def attention_fwd_ip(q, k, v, k_ip, v_ip, heads, ip_scale, scale=None, q_prescaled=False, kv_len=None, want_lse=False,
+                     causal=False):
+    """Decoupled cross-attention of an image prompt in one launch (pea_op_attention_fwd_ip):
+    softmax(scale q k^T) v + ip_scale * softmax(scale q k_ip^T) v_ip, head_dim 64.  q [B,Sq,H*64], k/v [B,Skv<=128,H*64],
+    k_ip/v_ip [B,N<=32,>=H*64] bf16; kv_len (int32 [B]) masks text keys only; the lse is the text softmax's.
+    -> o, or (o, lse [B,H,Sq]) with want_lse.  causal=True exists to be refused."""
+    B, Sq, C = q.shape
+    scale = scale if scale is not None else (C // heads) ** -0.5
+    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
+    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    check(lib().pea_op_attention_fwd_ip(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(k_ip), k_ip.stride(1),
+                                        ptr(v_ip), v_ip.stride(1), ptr(o), C, ptr(lse), B, heads, Sq, k.shape[1], k_ip.shape[1],
+                                        scale, float(ip_scale), int(q_prescaled), int(causal), ptr(kv_len), stream_ptr()))
+    return (o, lse) if want_lse else o
 
 
 def attention_fwd_masked(q, k, v, heads, causal=False, kv_len=None, scale=None):

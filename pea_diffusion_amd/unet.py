@@ -245,6 +245,64 @@ class HipUNet(HipTape):
             want += f" or latents [lb, {C}, {self.H}, {self.W}] with lb dividing {self.B}"
         raise PeaError(f"HipUNet built for {want}, got {shp}")
 
+    # ---------------------------------------------------------------- image prompt (IP-Adapter)
+    _ip = None             # the loaded ip_adapter.IPAdapter
+    _ip_tokens = None      # the tokens last handed to the context (kept alive while the cast may still be queued)
+
+    def load_ip_adapter(self, adapter_or_sd):
+        """Give every cross-attention layer the `to_k_ip` / `to_v_ip` projections of an IP-Adapter (an `ip_adapter.IPAdapter`, a
+        state dict or a file path).  The UNet's own weights -- `weight_table()`, `load_state_dict` -- do not change, and neither
+        does any launch until `set_ip_tokens`.  Returns the IPAdapter (its `.tokens()` is the image projection)."""
+        from .ip_adapter import IPAdapter
+        ad = adapter_or_sd if isinstance(adapter_or_sd, IPAdapter) else IPAdapter(adapter_or_sd, self.cfg)
+        if ad.cfg.cross_attention_dim != self.cfg.cross_attention_dim:
+            raise PeaError(f"load_ip_adapter: adapter built for cross_attention_dim {ad.cfg.cross_attention_dim}, UNet has "
+                           f"{self.cfg.cross_attention_dim}")
+        check(lib().pea_unet_ip_create(self._h, ad.n_tokens))
+        try:
+            for k, t in ad.layers.items():
+                t = t.to(self.device, torch.float32).contiguous()
+                check(lib().pea_unet_ip_load_weight(self._h, k.encode(), ptr(t), t.numel(), stream_ptr()))
+            torch.cuda.current_stream().synchronize()      # staging tensors above are freed after this call
+        except PeaError:
+            self.unload_ip_adapter()
+            raise
+        self._ip = ad
+        return ad
+
+    def set_ip_tokens(self, tokens):
+        """tokens [B, N, cross_dim] (`IPAdapter.tokens(image_embeds, do_cfg=...)`, or a "plus" adapter's, computed elsewhere):
+        projected to every layer's image keys / values once; every call reads them until `clear_ip_tokens()`."""
+        if self._ip is None:
+            raise PeaError("set_ip_tokens: call load_ip_adapter first")
+        want = (self.B, self._ip.n_tokens, self.cfg.cross_attention_dim)
+        if tuple(tokens.shape) != want:
+            raise PeaError(f"set_ip_tokens: tokens {tuple(tokens.shape)} != {want}")
+        t = tokens.detach().to(self.device, torch.float32).contiguous()
+        check(lib().pea_unet_ip_set_tokens(self._h, ptr(t), stream_ptr()))
+        self._ip_tokens = t
+
+    def set_ip_adapter_scale(self, scale: float):
+        """the weight of the image branch (default 1; 0 runs the plain attention)"""
+        check(lib().pea_unet_ip_set_scale(self._h, float(scale)))
+
+    def clear_ip_tokens(self):
+        """back to plain cross-attention launches; the adapter's weights stay loaded"""
+        check(lib().pea_unet_ip_clear(self._h))
+        self._ip_tokens = None
+
+    def unload_ip_adapter(self):
+        check(lib().pea_unet_ip_destroy(self._h))
+        self._ip = self._ip_tokens = None
+
+    def ip_kv(self):
+        """parity instrumentation: the image K|V of every layer, fp32 [B * N, cols] (columns: pea_unet_stacked_layout(which=0))"""
+        rows, cols = ctypes.c_longlong(), ctypes.c_int()
+        check(lib().pea_unet_ip_export_kv(self._h, None, ctypes.byref(rows), ctypes.byref(cols), None))
+        out = torch.empty(rows.value, cols.value, device=self.device, dtype=torch.float32)
+        check(lib().pea_unet_ip_export_kv(self._h, ptr(out), None, None, stream_ptr()))
+        return out
+
     # ---------------------------------------------------------------- ControlNet residual inputs
     _residuals_set = False
 
