@@ -164,6 +164,20 @@ int pea_op_attention_fwd_masked(const void* Q, int ldq, const void* K, int ldk, 
 int pea_op_attention_fwd_ip(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                             const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                             float scale, float ip_scale, int q_prescaled, int causal, const int* kv_len, void* stream);
+/* Few-query attention over the UNION of two key sets, forward only, head_dim 64 (nd must be 1):
+ *   O = softmax(scale [Q K^T | Q K2^T]) [V ; V2]
+ * ONE softmax (unlike pea_op_attention_fwd_ip), for 1 <= Sq <= 32 queries: the Perceiver Resampler of the IP-Adapter "plus" files,
+ * whose 16 latents attend over the image rows and over themselves, with the two key / value sets left where their projections
+ * wrote them.  Skv >= 1 without an upper limit; 0 <= Skv2 <= 32, and with 0 K2 / V2 are NULL (a plain few-query attention).
+ * The key range, not the query range, is shared among the waves of a workgroup; their partial (max, sum, O) triples are merged
+ * in a fixed order, so two runs give the same bits.  Batch strides Sq * ldq, Skv * ldk / ldv, Skv2 * ldk2 / ldv2; ldq / ldk /
+ * ldv / ldk2 / ldv2 multiples of 8 and >= 64 H, ldo a multiple of 4 and >= 64 H; Q / K / V 16-byte, O 8-byte aligned.  Rows of
+ * K / V behind a set's last key are never read.  lse (may be NULL) fp32 [B][H][Sq] over the union; q_prescaled as for
+ * pea_op_attention_fwd_ip.  Anything else (Sq > 32, Skv2 > 32, nd != 1, one of K2 / V2 alone, Skv2 and K2 disagreeing, a bad
+ * leading dimension) is refused with PEA_E_SHAPE before any launch. */
+int pea_op_attention_fwd_fewq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
+                              const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
+                              float scale, int nd, int q_prescaled, void* stream);
 /* dQ/dK/dV (dQ may be NULL; dK and dV together); delta: fp32 scratch [2][B][H][Sq] (row constants of the backward kernels); scratch: optional device
  * buffer of pea_op_attention_bwd_scratch_bytes(...) bytes enabling the query-split dK/dV form used when the
  * key count is small (cross-attention); NULL = single pass                                            */
@@ -454,6 +468,33 @@ int pea_vision_create(const pea_vision_config* cfg, int B, void** out);
 int pea_vision_plan(const pea_vision_config* cfg, int B, long long* n_params, int* n_tokens, int* n_attn);
 int pea_vision_forward(void* enc, const float* pixels, int hidden_index, float* hidden_out, float* pooled_out, float* embeds_out,
                        void* stream);
+/* Perceiver Resampler of the IP-Adapter "plus" files (ip-adapter-plus_sdxl_vit-h, ip-adapter-plus-face_sdxl_vit-h, the SD1.5
+ * plus files) on the same op tape, inference only: the image projection between the tower's hidden_states[-2] (pea_vision_forward,
+ * hidden_index -2) and the image tokens pea_unet_ip_set_tokens takes.  Keys as the files hold them under `image_proj.`: `latents`
+ * ([1][Nq][dim], stored [Nq][dim]), `proj_in.*`, `proj_out.*`, `norm_out.*`, `layers.L.0.{norm1,norm2}.*`, `layers.L.0.{to_q,
+ * to_kv,to_out}.weight`, `layers.L.1.0.*` (LayerNorm), `layers.L.1.1.weight`, `layers.L.1.3.weight`; the handle works with
+ * pea_unet_num_weights / weight_info / load_weight / init_random / memory / destroy.
+ *   x = proj_in(hidden);  latents = `latents` repeated over the batch
+ *   per layer:  q = to_q(norm2(latents));  k, v = to_kv([norm1(x) ; norm2(latents)])  -- S + Nq keys under ONE softmax, 1 / 8
+ *               latents += to_out(softmax(q k^T / 8) v);  latents += ff.3(gelu(ff.1(ff.0(latents))))     (GELU: erf form)
+ *   tokens = norm_out(proj_out(latents))
+ * to_kv runs where its rows are -- over the B S image rows, and stacked under to_q over the B Nq latent rows -- and
+ * pea_op_attention_fwd_fewq reads both key / value sets in place: no concatenation, no copy.  Heads are 64 wide (the only width
+ * the published files use); embed_dim, dim, ff_inner multiples of 64, out_dim a multiple of 8, 1 <= n_queries <= 32, else
+ * PEA_E_SHAPE.  SDXL plus (ViT-H): {1280, 1280, 20, 4, 16, 5120, 2048}, S = 257, 82 961 664 parameters.
+ * pea_resampler_plan: host only (no device needed): parameter total, attention ops (= depth), of those fed a prescaled Q (= depth).
+ * pea_resampler_plan_weight: host only: entry i of the weight table a handle of this configuration has (fields as
+ * pea_unet_weight_info); PEA_E_NOTFOUND past its end.
+ * pea_resampler_forward: hidden fp32 [B][S][embed_dim] -> tokens_out fp32 [B][n_queries][out_dim], both on the device. */
+typedef struct pea_resampler_config {
+  int embed_dim, dim, heads, depth, n_queries, ff_inner, out_dim;
+  float eps;
+} pea_resampler_config;
+int pea_resampler_create(const pea_resampler_config* cfg, int B, int S, void** out);
+int pea_resampler_plan(const pea_resampler_config* cfg, int B, int S, long long* n_params, int* n_attn, int* n_prescaled);
+int pea_resampler_plan_weight(const pea_resampler_config* cfg, int B, int S, int i, char* name, int name_len, long long* numel,
+                              int* kind, int* d0, int* d1);
+int pea_resampler_forward(void* resampler, const float* hidden, float* tokens_out, void* stream);
 /* Image preprocessing in front of the tower: images fp32 [B,3,H,W] -> v = clamp((x - lo) / (hi - lo), 0, 1), with `quantize`
  * round(v * 255) / 255 (what a saved 8-bit image holds) -> antialiased bicubic resample with the definition of
  * torch.nn.functional.interpolate(mode="bicubic", antialias=True, align_corners=False) (separable Keys kernel a = -0.5, support

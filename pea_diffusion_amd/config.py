@@ -423,3 +423,36 @@ def vision_to_c(cfg) -> CVisionConfig:
     c.act = {"quick_gelu": 3, "gelu": 1}[cfg.hidden_act]
     c.proj_dim, c.eps = cfg.projection_dim, cfg.layer_norm_eps
     return c
+
+
+# ---- Perceiver Resampler of the IP-Adapter "plus" files (the image projection between a ViT tower and the UNet; heads 64 wide)
+@dataclass
+class ResamplerConfig:
+    embed_dim: int = 1280               # width of the tower's hidden states
+    dim: int = 1280
+    heads: int = 20
+    depth: int = 4
+    n_queries: int = 16
+    ff_inner: int = 5120
+    out_dim: int = 2048                 # the UNet's cross_attention_dim
+    eps: float = 1e-5
+
+
+def sdxl_plus_resampler_config() -> ResamplerConfig:        # ip-adapter-plus_sdxl_vit-h, ip-adapter-plus-face_sdxl_vit-h
+    return ResamplerConfig()
+
+
+def sd15_plus_resampler_config() -> ResamplerConfig:        # ip-adapter-plus_sd15, ip-adapter-plus-face_sd15
+    return ResamplerConfig(dim=768, heads=12, ff_inner=3072, out_dim=768)
+
+
+class CResamplerConfig(ctypes.Structure):
+    _fields_ = [("embed_dim", ctypes.c_int), ("dim", ctypes.c_int), ("heads", ctypes.c_int), ("depth", ctypes.c_int),
+                ("n_queries", ctypes.c_int), ("ff_inner", ctypes.c_int), ("out_dim", ctypes.c_int), ("eps", ctypes.c_float)]
+
+
+def resampler_to_c(cfg) -> CResamplerConfig:
+    c = CResamplerConfig()
+    c.embed_dim, c.dim, c.heads, c.depth = cfg.embed_dim, cfg.dim, cfg.heads, cfg.depth
+    c.n_queries, c.ff_inner, c.out_dim, c.eps = cfg.n_queries, cfg.ff_inner, cfg.out_dim, cfg.eps
+    return c

@@ -272,6 +272,17 @@ int pea_op_attention_fwd_ip(const void* Q, int ldq, const void* K, int ldk, cons
   p.K2 = (const bf16*)K2; p.V2 = (const bf16*)V2; p.ldk2 = ldk2; p.ldv2 = ldv2; p.Skv2 = Skv2; p.scale2 = ip_scale;
   return launch_attention_fwd(p, (hipStream_t)stream);
 }
+int pea_op_attention_fwd_fewq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
+                              const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
+                              float scale, int nd, int q_prescaled, void* stream) {
+  AttnP p;
+  memset(&p, 0, sizeof(p));
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
+  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = nd;
+  p.q_prescaled = q_prescaled;
+  p.K2 = (const bf16*)K2; p.V2 = (const bf16*)V2; p.ldk2 = ldk2; p.ldv2 = ldv2; p.Skv2 = Skv2;
+  return launch_attention_fwd_fewq(p, (hipStream_t)stream);
+}
 int pea_op_attention_bwd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O,
                          int ldo, const void* dO, int lddo, const float* lse, float* delta, void* dQ, int lddq,
                          void* dK, int lddk, void* dV, int lddv, int B, int H, int Sq, int Skv, float scale,

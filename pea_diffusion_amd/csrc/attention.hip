@@ -21,6 +21,8 @@
 // both orientations on specialised waves), xattn_bwd_kernel (round 3: any key count up to 128), each with an ordered
 // fp32 split reduce over query ranges (attn_dkv_reduce_kernel).  Every output tile (O, dQ, dK, dV) leaves through a
 // per-wave LDS image as whole 128-byte rows.
+// Few queries (<= 32: the Resampler latents of the IP-Adapter "plus" files) over the union of two key sets under one softmax:
+// attn_fewq_kernel shares out the KEYS among a workgroup's waves and merges their partials in a fixed order.
 // The three backward cross-attention kernels take their per-workgroup context (unit range, operand rows of the head, key
 // count, score factor) from xattn_ctx.  They still repeat, as text: K / V staging, the unit stage (stage_unit / fetch_o /
 // unit_head), the key-on-the-lane task, the query-on-the-lane key-block step, and the dQ and dK / dV exits -- so a fix to
@@ -1153,6 +1155,150 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
       }
     }
   }
+}
+
+// ============================================================================= few queries, keys split across the waves
+// O = softmax(scale [Q K1^T | Q K2^T]) [V1 ; V2]: at most 32 queries over ONE softmax of two key sets read in place (the
+// Perceiver Resampler of the IP-Adapter "plus" files: 16 latents over 257 image rows and the 16 latents themselves; K1 / V1 and
+// K2 / V2 are column blocks of two different projections, Tape::build_resampler).  There is no parallelism over queries at this
+// shape -- attn_q_kernel would run one wave of four per (batch, head) down a serial key loop -- so the KEYS are what a
+// workgroup's waves share out: all four hold the same 32-query fragments (rows past Sq read as zeros and are never stored), the
+// 32-key blocks of set 1 followed by the block of set 2 are dealt round-robin (wave w: blocks w, w + 4, ...), and every wave
+// runs an online softmax over its blocks: own K / V half tiles (32 rows x 128 bytes each, the layout and the loader of every
+// other tile of this file) in a 2-deep ring of its own, the next block in flight under the current one, no barrier in the loop.
+// Every block is staged through a descriptor that STARTS at the block's first row and ends with the set's last row, so the
+// rows behind a set's tail -- the next sample's, another tensor's, or anything else the allocation holds -- are never read:
+// they arrive as zeros, their scores are set to -inf, and a NaN there cannot reach 0 x V.
+// The (max, sum, O^T) partials then meet in LDS (a wave's own, by now idle, ring) and all 256 threads merge them in wave order
+// 0..3 with fmaf: no atomics, the same bits every run.  A wave without a block leaves (-inf, 0, 0); its factor exp2(-inf - M)
+// is an exact zero, and M is finite because wave 0 always has block 0.  lse is that of the union.
+#define FEWQ_WAVE_BYTES 16384     // 2 x (K half tile + V half tile); afterwards [64 d][32 q] fp32 partial O^T + 32 maxima + 32 sums
+__global__ __launch_bounds__(256) void attn_fewq_kernel(const AttnP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const Qsm = smem + 4 * FEWQ_WAVE_BYTES;                  // 32 rows x 128 bytes
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int frow = lane & 31, fh = lane >> 5;
+  const int head = blockIdx.x, b = blockIdx.y;
+  const float c = p.q_prescaled ? 1.f : p.scale * LOG2E;
+  const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq + head * 64;
+  const bf16* K1b = p.K + (long long)b * p.Skv * p.ldk + head * 64;
+  const bf16* V1b = p.V + (long long)b * p.Skv * p.ldv + head * 64;
+  const bf16* K2b = p.K2 ? p.K2 + (long long)b * p.Skv2 * p.ldk2 + head * 64 : nullptr;
+  const bf16* V2b = p.V2 ? p.V2 + (long long)b * p.Skv2 * p.ldv2 + head * 64 : nullptr;
+  const int nb1 = (p.Skv + 31) >> 5, nb = nb1 + ((p.Skv2 + 31) >> 5);
+  // block `blk` of the union: its K rows -> dst, its V rows -> dst + 4096 (pieces 0 / 1 of a tile: rows 0..15, then 16..31)
+  auto stage_blk = [&](int blk, char* dst) {
+    const bool s2 = blk >= nb1;
+    const int r0 = (s2 ? blk - nb1 : blk) * 32, left = (s2 ? p.Skv2 : p.Skv) - r0;
+    const int ldk = s2 ? p.ldk2 : p.ldk, ldv = s2 ? p.ldv2 : p.ldv;
+    const bf16* kb = (s2 ? K2b : K1b) + (long long)r0 * ldk;
+    const bf16* vb = (s2 ? V2b : V1b) + (long long)r0 * ldv;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      stage_tile(tile_src(kb, ldk, left, h, lane), 0, dst, h);
+      stage_tile(tile_src(vb, ldv, left, h, lane), 0, dst + 4096, h);
+    }
+  };
+  char* const my = smem + wave * FEWQ_WAVE_BYTES;
+  if (wave < 2) stage_tile(tile_src(Qb, p.ldq, p.Sq, wave, lane), 0, Qsm, wave);
+  int blk = wave;
+  if (blk < nb) stage_blk(blk, my);
+  int rf_off[4], tr_off[2][2];
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
+  {
+    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
+  }
+  WAIT_VM0();
+  __syncthreads();                                               // the Q image (waves 0 / 1 staged it)
+  bf16x8 qf[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(Qsm + rf_off[s]);
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.f;                          // log2 domain; l_run: this half's 16 keys of every block
+  f32x16 oacc[2] = {zero16, zero16};
+  for (int i = 0; blk < nb; blk += 4, ++i) {
+    char* const cur = my + (i & 1) * 8192;
+    WAIT_VM0();                                                  // this block's rows have landed
+    if (blk + 4 < nb) stage_blk(blk + 4, my + ((i + 1) & 1) * 8192);   // (its last reader: iteration i - 1, closed below)
+    const bool s2 = blk >= nb1;
+    const int valid = (s2 ? p.Skv2 : p.Skv) - (s2 ? blk - nb1 : blk) * 32;     // >= 1; >= 32: a full block
+    // S^T[key][q] = K . Q^T
+    f32x16 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + rf_off[0]), qf[0], zero16, 0, 0, 0);
+#pragma unroll
+    for (int s = 1; s < 4; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + rf_off[s]), qf[s], sacc, 0, 0, 0);
+    if (valid < 32) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sacc[r] = (r & 3) + 8 * (r >> 2) + 4 * fh < valid ? sacc[r] : -INFINITY;
+    }
+    float mx = sacc[0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[r]);
+    const float m_new = fmaxf(m_run, xhalf_max(mx) * c);         // finite: the block holds a valid key
+    const float alpha = fast_exp2(m_run - m_new);                // first block: exp2(-inf) = 0 on a zero accumulator
+    float ls = 0.f;
+    bf16x8 pf[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float e = fast_exp2(fmaf(sacc[r], c, -m_new));       // masked key: exp2(-inf) = 0
+      ls += e;
+      pf[r >> 3][r & 7] = (bf16)e;
+    }
+    l_run = fmaf(l_run, alpha, ls);
+    m_run = m_new;
+    // O^T[d][q] = alpha O^T + V^T[d][key] P^T[key][q]
+#pragma unroll
+    for (int db = 0; db < 2; ++db) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) oacc[db][r] *= alpha;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            read_transposed_frag_at(cur + 4096 + tr_off[db][0] + ks * 2048, cur + 4096 + tr_off[db][1] + ks * 2048), pf[ks], oacc[db], 0, 0, 0);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // every read of `cur` is done before a later DMA may land in it
+  }
+  // this wave's partial into its own ring (no DMA is in flight: each staged block was waited for and consumed)
+  float* const part = (float*)my;
+  float* const ml = (float*)(my + 8192);
+  const float l_tot = xhalf_sum(l_run);                          // both halves rescaled by the same alpha every block
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[(db * 32 + 8 * (r >> 2) + 4 * fh + (r & 3)) * 32 + frow] = oacc[db][r];
+  if (fh == 0) { ml[frow] = m_run; ml[32 + frow] = l_tot; }
+  __syncthreads();
+  // merge: thread -> query tid & 31, eight output columns; partials in wave order
+  const int q = tid & 31, ch = tid >> 5;
+  float f[4], M = -INFINITY, L = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) M = fmaxf(M, *(const float*)(smem + w * FEWQ_WAVE_BYTES + 8192 + q * 4));
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    f[w] = fast_exp2(*(const float*)(smem + w * FEWQ_WAVE_BYTES + 8192 + q * 4) - M);
+    L = fmaf(f[w], *(const float*)(smem + w * FEWQ_WAVE_BYTES + 8192 + (32 + q) * 4), L);
+  }
+  if (q >= p.Sq) return;                                         // padded query rows
+  const float inv = 1.f / L;
+  bf16* const orow = p.O + ((long long)b * p.Sq + q) * p.ldo + head * 64 + ch * 8;
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    bf16x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float acc = 0.f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) acc = fmaf(f[w], *(const float*)(smem + w * FEWQ_WAVE_BYTES + ((ch * 8 + g * 4 + j) * 32 + q) * 4), acc);
+      o[j] = (bf16)(acc * inv);
+    }
+    *(bf16x4*)(orow + g * 4) = o;                                // 8-byte stores: ldo % 4
+  }
+  if (p.lse && ch == 0) p.lse[((long long)b * p.H + head) * p.Sq + q] = (M + log2f(L)) * 0.6931471805599453f;
 }
 
 // ============================================================================= cross-attention backward, ONE pass
@@ -2418,6 +2564,36 @@ int launch_attention_fwd(const AttnP& p0, hipStream_t s) {
   const int keys = p.Skv + (p.K2 ? p.Skv2 : 0);                    // both key sets: one more score / value product each
   PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * keys * 64 * p.nd, 2.0 * p.B * p.H * 64 * p.nd * (2.0 * p.Sq + 2.0 * keys), s);
   rc = p.nd == 1 ? attn_fwd_nd<1>(p, s) : p.nd == 2 ? attn_fwd_nd<2>(p, s) : attn_fwd_nd<3>(p, s);
+  PROF_END(s);
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
+// at most 32 queries over one softmax of two key sets (attn_fewq_kernel); AttnP::K2 / V2 / Skv2 are the second SET here, not
+// a second softmax.  Everything outside the kernel's shape is refused before any launch.
+int launch_attention_fwd_fewq(const AttnP& p, hipStream_t s) {
+  SHAPECHK(p.B > 0 && p.B <= 65535 && p.H > 0 && p.Sq >= 1 && p.Skv >= 1, "attention_fewq: empty problem (B=%d H=%d Sq=%d Skv=%d)", p.B, p.H, p.Sq, p.Skv);
+  SHAPECHK(p.Sq <= 32, "attention_fewq: at most 32 queries (Sq=%d); larger counts belong to pea_op_attention_fwd", p.Sq);
+  SHAPECHK(p.nd == 1, "attention_fewq: head_dim 64 only (nd=%d)", p.nd);
+  SHAPECHK((p.K2 != nullptr) == (p.V2 != nullptr), "attention_fewq: a second key set needs both K2 and V2");
+  SHAPECHK(p.Skv2 >= 0 && p.Skv2 <= 32, "attention_fewq: the second key set holds 0..32 keys (Skv2=%d)", p.Skv2);
+  SHAPECHK((p.Skv2 > 0) == (p.K2 != nullptr), "attention_fewq: Skv2=%d %s K2 / V2", p.Skv2, p.K2 ? "with" : "without");
+  SHAPECHK(p.Q && p.K && p.V && p.O, "attention_fewq: null operand");
+  SHAPECHK(p.scale > 0.f && !p.causal && !p.kv_len && !p.bias, "attention_fewq: a positive scale, no mask, no score bias");
+  const int C = 64 * p.H;
+  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldq >= C && p.ldk >= C && p.ldv >= C,
+           "attention_fewq: ldq / ldk / ldv must be multiples of 8 and hold every head (%d %d %d)", p.ldq, p.ldk, p.ldv);
+  SHAPECHK(!p.K2 || (p.ldk2 % 8 == 0 && p.ldv2 % 8 == 0 && p.ldk2 >= C && p.ldv2 >= C),
+           "attention_fewq: ldk2 / ldv2 must be multiples of 8 and hold every head (ldk2=%d ldv2=%d)", p.ldk2, p.ldv2);
+  SHAPECHK(p.ldo % 4 == 0 && p.ldo >= C, "attention_fewq: ldo %% 4, ldo >= 64 H (ldo=%d)", p.ldo);
+  const unsigned long long in_bits = (unsigned long long)p.Q | (unsigned long long)p.K | (unsigned long long)p.V |
+                                     (unsigned long long)p.K2 | (unsigned long long)p.V2;
+  SHAPECHK(in_bits % 16 == 0 && (unsigned long long)p.O % 8 == 0, "attention_fewq: Q / K / V 16-byte, O 8-byte aligned");
+  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv + p.Skv2; g_prof_tag[3] = 1; }
+  const int keys = p.Skv + p.Skv2;
+  PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * keys * 64, 2.0 * p.B * p.H * 64 * (2.0 * p.Sq + 2.0 * keys), s);
+  const int rc = launch_lds<attn_fewq_kernel>(dim3(p.H, p.B), 4 * FEWQ_WAVE_BYTES + 4096, s, p);
   PROF_END(s);
   if (rc) return rc;
   HIPCHK(hipGetLastError());

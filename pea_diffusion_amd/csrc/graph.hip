@@ -1,5 +1,5 @@
 // Graph construction: the Builder and the builders of every tape -- UNet2DConditionModel / ControlNetModel, the AutoencoderKL
-// encoder and decoder, the CLIP / BERT / T5 text encoders and the CLIP vision tower.  Each mirrors, op for op, the diffusers-0.23 /
+// encoder and decoder, the CLIP / BERT / T5 text encoders, the CLIP vision tower and the IP-Adapter Resampler.  Each mirrors, op for op, the diffusers-0.23 /
 // HF transformers graph the reference executes (train_sdxl_zh.py:397,415; restated on CPU in oracle/), with the state-dict key
 // names for every weight.  Construction order is a contract: slot order is pea_unet_weight_info order, tensor order is the arena
 // layout, op order is launch order.
@@ -578,6 +578,54 @@ int Tape::build_vision() {
   return PEA_OK;
 }
 
+// Perceiver Resampler of the IP-Adapter "plus" files (tencent-ailab/IP-Adapter resampler.py; keys as the files hold them under
+// `image_proj.`): the projection between the CLIP tower's hidden_states[-2] ([B][L][embed_dim]) and the Nq image tokens of
+// cross_attention_dim that HipUNet.set_ip_tokens takes.
+//   x = proj_in(hidden);  latents = `latents` repeated over the batch
+//   per layer l:  xn = norm1(x), ln = norm2(latents);  q = to_q(ln);  k, v = to_kv([xn ; ln])  (L + Nq keys, ONE softmax, 1 / 8)
+//                 latents += to_out(attn);  latents += ff.3(gelu(ff.1(ff.0(latents))))
+//   tokens = norm_out(proj_out(latents))
+// The reference concatenates xn and ln in front of to_kv.  Here to_kv runs where its rows are: one GEMM over the B L image
+// rows, and -- stacked under to_q, sharing the to_kv weight slot -- one over the B Nq latent rows; OP_ATTN_FEWQ reads K1 / V1
+// and K2 / V2 from the two outputs in place.  No concatenation and no copy on the tape; Q leaves its projection prescaled.
+int Tape::build_resampler() {
+  const PeaResamplerCfg& c = rcfg;
+  SHAPECHK(!needs_grad, "resampler: inference graph only");
+  SHAPECHK(c.heads > 0 && c.dim > 0 && c.dim % 64 == 0 && c.embed_dim > 0 && c.embed_dim % 64 == 0,
+           "resampler: embed_dim %d / dim %d must be multiples of 64, heads %d", c.embed_dim, c.dim, c.heads);
+  SHAPECHK(c.depth >= 1 && c.n_queries >= 1 && c.n_queries <= 32, "resampler: depth %d, %d queries (1..32)", c.depth, c.n_queries);
+  SHAPECHK(c.ff_inner > 0 && c.ff_inner % 64 == 0 && c.out_dim > 0 && c.out_dim % 8 == 0,
+           "resampler: ff_inner %d must be a multiple of 64, out_dim %d of 8", c.ff_inner, c.out_dim);
+  SHAPECHK(B > 0 && L >= 1, "resampler: batch %d, %d image rows", B, L);
+  Builder bd(*this);
+  const int Nq = c.n_queries, I = c.heads * 64;                  // head width is 64 in every published file
+  t_rs_in = bd.T((long long)B * L, c.embed_dim, B, 1, L);
+  t_rs_lat = bd.T((long long)B * Nq, c.dim, B, 1, Nq);
+  w_rs_lat = bd.lin("latents", Nq, c.dim);
+  const int x = bd.linear(t_rs_in, "proj_in", c.dim, true);
+  int lat = t_rs_lat;
+  for (int l = 0; l < c.depth; ++l) {
+    const std::string a = "layers." + std::to_string(l) + ".0", f = "layers." + std::to_string(l) + ".1";
+    const int xn = bd.ln(x, a + ".norm1", c.eps), ln = bd.ln(lat, a + ".norm2", c.eps);
+    const int qkv = bd.fused_linear(ln, {a + ".to_q", a + ".to_kv"}, {I, 2 * I}, false);      // Q | K2 | V2 over the latent rows
+    const int kv = bd.linear(xn, a + ".to_kv", 2 * I, false);                                  // K1 | V1 over the image rows (same slot)
+    const int att = bd.T((long long)B * Nq, I, B, 1, Nq);
+    {
+      Op& o = bd.push(OP_ATTN_FEWQ);
+      o.a = qkv; o.acol = 0; o.k2col = I; o.v2col = 2 * I; o.b = kv; o.bcol = 0; o.c = kv; o.ccol = I; o.out = att;
+      o.p0 = c.heads; o.p1 = Nq; o.p2 = L; o.p3 = 1; o.f0 = 0.125f;
+    }
+    lat = bd.linear(att, a + ".to_out", c.dim, false, lat);
+    const int n = bd.ln(lat, f + ".0", c.eps);
+    const int h = bd.linear(n, f + ".1", c.ff_inner, false);
+    ops.back().p2 = 1;                                           // GELU(erf)
+    lat = bd.linear(h, f + ".3", c.dim, false, lat);
+  }
+  const int y = bd.linear(lat, "proj_out", c.out_dim, true);
+  t_final = bd.ln(y, "norm_out", c.eps);
+  return PEA_OK;
+}
+
 // the attention backward takes query counts in multiples of 4 (attention.hip, launch_attention_bwd): a training context whose
 // token grid breaks that (an SD1.5 mid block at a 56 x 104 latent: 7 x 13 = 91 tokens) is refused when it is created, not in its
 // first backward pass
@@ -592,6 +640,7 @@ int Tape::check_attn_bwd_tokens() const {
 int Tape::build() {
   if (graph == 4) return build_text();
   if (graph == 5) return build_vision();
+  if (graph == 6) return build_resampler();
   if (graph == 1) return build_vae_encoder();
   if (graph == 3) return build_vae_decoder();
   normalize_depths(cfg);
@@ -799,7 +848,7 @@ int Tape::build() {
 void Tape::tag_q_prescale() {
   n_attn = n_attn_pre = 0;
   for (const Op& a : ops)
-    if (a.kind == OP_ATTN) { ++n_attn; n_attn_pre += a.pre ? 1 : 0; }
+    if (is_flash_attn(a.kind)) { ++n_attn; n_attn_pre += a.pre ? 1 : 0; }
   // An attention op that fails a condition below keeps a plain Q: the kernels then round Q * scale * log2(e) to bf16 themselves
   // (attention.hip: scale_frag), one more rounding than the tagged path.  Nothing on the product's graphs may take that path
   // silently: the census (pea_tape_attention_census) is asserted by the tests for every graph, and a miss is logged once here.
@@ -807,7 +856,7 @@ void Tape::tag_q_prescale() {
     Tape* t;
     ~Census() {
       t->n_attn_pre = 0;
-      for (const Op& a : t->ops) t->n_attn_pre += (a.kind == OP_ATTN && a.pre) ? 1 : 0;
+      for (const Op& a : t->ops) t->n_attn_pre += (is_flash_attn(a.kind) && a.pre) ? 1 : 0;
       if (t->n_attn_pre != t->n_attn && !t->plan_only)
         fprintf(stderr, "pea: graph %d: %d of %d attention ops run on a plain (not prescaled) Q\n", t->graph,
                 t->n_attn - t->n_attn_pre, t->n_attn);
@@ -815,7 +864,7 @@ void Tape::tag_q_prescale() {
   } census{this};
   for (size_t i = 0; i < ops.size(); ++i) {
     Op& a = ops[i];
-    if (a.kind != OP_ATTN || a.pre || a.acol != 0) continue;
+    if (!is_flash_attn(a.kind) || a.pre || a.acol != 0) continue;
     int prod = -1, readers = 0;
     for (size_t j = 0; j < ops.size(); ++j) {
       const Op& o = ops[j];

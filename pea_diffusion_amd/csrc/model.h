@@ -65,6 +65,11 @@ struct PeaVisionCfg {        // mirrors `pea_vision_config` of include/pea_hip.h
   float eps;
 };
 
+struct PeaResamplerCfg {     // mirrors `pea_resampler_config` of include/pea_hip.h
+  int embed_dim, dim, heads, depth, n_queries, ff_inner, out_dim;
+  float eps;
+};
+
 enum WKind { W_VEC, W_LINEAR, W_CONV3, W_CONV_IN, W_CONV_OUT };
 
 struct WSlot {
@@ -126,7 +131,8 @@ struct Tn {
 };
 
 enum OpKind { OP_CONV_IN, OP_CONV3, OP_LINEAR, OP_GN, OP_LN, OP_ATTN, OP_GEGLU, OP_CONCAT, OP_SILU, OP_TEMB,
-              OP_CONV_OUT, OP_ADD, OP_ATTN_MAT, OP_EMBED, OP_GATHER_EOS, OP_VIS_EMBED, OP_CLS_ROW };
+              OP_CONV_OUT, OP_ADD, OP_ATTN_MAT, OP_EMBED, OP_GATHER_EOS, OP_VIS_EMBED, OP_CLS_ROW, OP_ATTN_FEWQ };
+inline bool is_flash_attn(int kind) { return kind == OP_ATTN || kind == OP_ATTN_FEWQ; }   // ops with a Q the producer may prescale
 
 struct Op {
   int kind;
@@ -144,19 +150,21 @@ struct Op {
   int mask = 0;                   // OP_ATTN: 1 causal, 2 per-sample key count (text encoders), 4 additive T5 position bias
   int fold = -1;                  // OP_LN / OP_LINEAR: index into Tape::folds (LayerNorm folded into the consuming Linear)
   int qs_cols = 0; float qs = 1.f; // OP_LINEAR: output columns [0, qs_cols) leave multiplied by qs (the Q block of an attention's projection)
-  int pre = 0;                    // OP_ATTN: Q arrives multiplied by scale * log2(e) (Tape::tag_q_prescale)
+  int k2col = 0, v2col = 0;       // OP_ATTN_FEWQ: columns of the second key / value set in tensor `a` (the latent rows' to_q | to_kv output)
+  int pre = 0;                    // OP_ATTN / OP_ATTN_FEWQ: Q arrives multiplied by scale * log2(e) (Tape::tag_q_prescale)
   int stash_form = -1;            // fused-GEGLU OP_LINEAR: what the last FORWARD left in its stash (0: (h, gate), 1: the backward's
                                   // factors); written by Tape::forward, read by Tape::backward -- never re-derived there
 };
 
 // The static op tape: tensors, weight slots and ops of ONE graph, built once per (config, batch, size).  graph selects the
-// builder: the UNet of the KD step (0), AutoencoderKL encoder / decoder (1 / 3), ControlNet (2), a text encoder (4).
+// builder: the UNet of the KD step (0), AutoencoderKL encoder / decoder (1 / 3), ControlNet (2), a text encoder (4), a CLIP vision
+// tower (5), the Resampler of an IP-Adapter "plus" file (6).
 struct Tape {
   PeaUnetCfg cfg;
   int B, H, W, L;                 // batch, latent H/W, context length
   bool needs_grad;
   int bwd_batch = 0;                 // > 0: backward() differentiates only the first bwd_batch samples (merged passes)
-  int graph = 0;                     // 0: UNet2DConditionModel, 1: AutoencoderKL encoder, 2: ControlNetModel, 3: AutoencoderKL decoder, 4: text encoder, 5: CLIP vision tower (1-5: inference only)
+  int graph = 0;                     // 0: UNet2DConditionModel, 1: AutoencoderKL encoder, 2: ControlNetModel, 3: AutoencoderKL decoder, 4: text encoder, 5: CLIP vision tower, 6: IP-Adapter Resampler (1-6: inference only)
   std::vector<int> cn_out;           // ControlNet: output tensors (down residuals in diffusers order, mid last)
   int ce_begin = -1, ce_end = -1;    // ControlNet: op range of the conditioning embedding (constant over a generation)
   bool ce_valid = false;             // ... already computed for the current conditioning image
@@ -239,6 +247,10 @@ struct Tape {
   int build_vision();
   PeaVisionCfg vcfg{};               // graph 5: CLIP vision tower; hidden / t_final (last state, before post_layernorm) / t_pooled (image_embeds) as graph 4
   int t_vrows = -1, t_vpool = -1;    // graph 5: patch rows [B*Np][Kpad] (written by launch_patchify), post_layernorm(h_N[:, 0]) = pooler_output
+  int build_resampler();
+  PeaResamplerCfg rcfg{};            // graph 6: Perceiver Resampler of the IP-Adapter "plus" files; L = image rows per sample
+  int t_rs_in = -1, t_rs_lat = -1;   // graph 6: the tower's states [B*L][embed_dim] and the latents [B*Nq][dim] (pea_resampler_forward fills both)
+  int w_rs_lat = -1;                 // ... the `latents` slot, [Nq][dim]
   int* kvlen = nullptr;              // graph 4 (BERT): per-sample valid token count
   float* rel_bias = nullptr;         // graph 4 (T5): [heads][L][64*ceil(L/64)] relative-position bias in the log2 domain
   int* rel_bucket = nullptr;         // ... |key - query| -> sub-bucket table [L]

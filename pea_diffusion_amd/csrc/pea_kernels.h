@@ -131,6 +131,8 @@ struct AttnP {
 int attention_bwd_nsplit(int B, int H, int Sq, int Skv);
 size_t attention_bwd_scratch_bytes(int B, int H, int Sq, int Skv, int nd = 1);
 int launch_attention_fwd(const AttnP& p, hipStream_t s);
+// Sq <= 32 over ONE softmax of K | K2 (Skv2 <= 32, or none): the keys, not the queries, are shared out (attn_fewq_kernel)
+int launch_attention_fwd_fewq(const AttnP& p, hipStream_t s);
 int launch_attention_bwd(const AttnP& p, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise.hip

@@ -677,6 +677,16 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
         RC(launch_attention_fwd(p, s));
         break;
       }
+      case OP_ATTN_FEWQ: {             // the latents over the image rows' keys and their own, one softmax, both read in place
+        AttnP p; memset(&p, 0, sizeof(p));
+        const Tn &a = tn[o.a], &k = tn[o.b], &v = tn[o.c];
+        p.Q = a.d + o.acol; p.ldq = a.cols; p.K = k.d + o.bcol; p.ldk = k.cols; p.V = v.d + o.ccol; p.ldv = v.cols;
+        p.K2 = a.d + o.k2col; p.V2 = a.d + o.v2col; p.ldk2 = p.ldv2 = a.cols; p.Skv2 = o.p1;
+        p.O = tn[o.out].d; p.ldo = tn[o.out].cols;
+        p.B = B; p.H = o.p0; p.Sq = o.p1; p.Skv = o.p2; p.scale = o.f0; p.nd = o.p3; p.q_prescaled = o.pre;
+        RC(launch_attention_fwd_fewq(p, s));
+        break;
+      }
       case OP_GEGLU:
         RC(launch_geglu_fwd(tn[o.a].d, tn[o.out].d, tn[o.a].rows, tn[o.out].cols, s));
         break;

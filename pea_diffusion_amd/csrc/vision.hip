@@ -10,6 +10,7 @@
 //   vision_embed_kernel class row + position add + pre_layrnorm in one pass over [B][Np + 1][width]
 //   clip_score_kernel   w * max(cos(image, text), 0), one wave per pair, fixed-order fp32 reduction (bit-reproducible)
 // and the C ABI of the vision tower (Tape::build_vision, graph.hip).  No atomics anywhere; explicit fmaf as in sampler.hip.
+#include <stdio.h>
 #include <string.h>
 
 #include "../../include/pea_hip.h"
@@ -299,6 +300,7 @@ int launch_clip_score(const float* img, const float* txt, float* out, int B, int
 
 // ============================================================================ C ABI
 static_assert(sizeof(pea_vision_config) == sizeof(PeaVisionCfg), "vision config struct mismatch");
+static_assert(sizeof(pea_resampler_config) == sizeof(PeaResamplerCfg), "resampler config struct mismatch");
 #define VNOTNULL(p, what)                        \
   do {                                           \
     if (!(p)) {                                  \
@@ -387,6 +389,100 @@ int pea_vision_forward(void* h, const float* pixels, int hidden_index, float* hi
     if (rc != PEA_OK) return rc;
   }
   return PEA_OK;
+}
+
+// ---- Perceiver Resampler of the IP-Adapter "plus" files (Tape::build_resampler): the tower's hidden_states[-2] -> image tokens
+static void resampler_setup(Tape& u, const pea_resampler_config* cfg, int B, int S) {
+  memset(&u.cfg, 0, sizeof(PeaUnetCfg));
+  memcpy(&u.rcfg, cfg, sizeof(PeaResamplerCfg));
+  u.graph = 6;
+  u.B = B; u.H = 1; u.W = S; u.L = S; u.needs_grad = false; u.owns_weights = true;
+}
+
+int pea_resampler_create(const pea_resampler_config* cfg, int B, int S, void** out) {
+  VNOTNULL(cfg, "pea_resampler_create");
+  VNOTNULL(out, "pea_resampler_create");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    pea_set_error("pea_resampler_create: no HIP device (there is no CPU fallback)");
+    return PEA_E_HIP;
+  }
+  Tape* u = new Tape();
+  resampler_setup(*u, cfg, B, S);
+  int rc = u->build();
+  if (rc == PEA_OK) rc = u->alloc();
+  if (rc != PEA_OK) {
+    delete u;
+    return rc;
+  }
+  *out = u;
+  return PEA_OK;
+}
+
+int pea_resampler_plan(const pea_resampler_config* cfg, int B, int S, long long* n_params, int* n_attn, int* n_prescaled) {
+  VNOTNULL(cfg, "pea_resampler_plan");
+  Tape u;
+  resampler_setup(u, cfg, B, S);
+  u.plan_only = true;
+  int rc = u.build();
+  if (rc == PEA_OK) rc = u.alloc();
+  if (rc != PEA_OK) return rc;
+  long long np = 0;
+  for (const WSlot& s : u.slots) np += s.numel;
+  if (n_params) *n_params = np;
+  if (n_attn) *n_attn = u.n_attn;
+  if (n_prescaled) *n_prescaled = u.n_attn_pre;
+  return PEA_OK;
+}
+
+/* weight i of the table a handle for this configuration would have, host only: what pea_unet_weight_info says about a handle */
+int pea_resampler_plan_weight(const pea_resampler_config* cfg, int B, int S, int i, char* name, int name_len, long long* numel,
+                              int* kind, int* d0, int* d1) {
+  VNOTNULL(cfg, "pea_resampler_plan_weight");
+  Tape u;
+  resampler_setup(u, cfg, B, S);
+  u.plan_only = true;
+  int rc = u.build();
+  if (rc == PEA_OK) rc = u.alloc();
+  if (rc != PEA_OK) return rc;
+  if (i < 0 || i >= (int)u.slots.size()) {
+    pea_set_error("pea_resampler_plan_weight: index %d of %d weights", i, (int)u.slots.size());
+    return PEA_E_NOTFOUND;
+  }
+  const WSlot& w = u.slots[i];
+  if (name && name_len > 0) snprintf(name, (size_t)name_len, "%s", w.name.c_str());
+  if (numel) *numel = w.numel;
+  if (kind) *kind = w.kind;
+  if (d0) *d0 = w.d0;
+  if (d1) *d1 = w.d1;
+  return PEA_OK;
+}
+
+int pea_resampler_forward(void* h, const float* hidden, float* tokens_out, void* stream) {
+  VNOTNULL(h, "pea_resampler_forward");
+  VNOTNULL(hidden, "pea_resampler_forward");
+  VNOTNULL(tokens_out, "pea_resampler_forward");
+  Tape* u = (Tape*)h;
+  if (u->graph != 6) { pea_set_error("pea_resampler_forward: not a resampler handle"); return PEA_E_INVALID; }
+  hipStream_t s = (hipStream_t)stream;
+  std::string miss;
+  if (!u->all_loaded(&miss)) {
+    pea_set_error("resampler: weight '%s' was never loaded", miss.c_str());
+    return PEA_E_STATE;
+  }
+  int rc = u->ensure_acts();
+  if (rc != PEA_OK) return rc;
+  // the two inputs of the tape: the tower's states in bf16, and the `latents` rows once per sample (source row stride 0)
+  const Tn &in = u->tn[u->t_rs_in], &lat = u->tn[u->t_rs_lat];
+  rc = launch_cast_f32_bf16(hidden, in.d, in.rows * in.cols, s);
+  if (rc != PEA_OK) return rc;
+  const int per = u->rcfg.n_queries * lat.cols;
+  rc = launch_copy2d(u->slots[u->w_rs_lat].w, 0, lat.d, per, u->B, per, 0, s);
+  if (rc != PEA_OK) return rc;
+  rc = u->exec_ops(0, u->ops.size(), false, s);
+  if (rc != PEA_OK) return rc;
+  const Tn& t = u->tn[u->t_final];
+  return launch_cast_bf16_f32(t.d, tokens_out, t.rows * t.cols, s);
 }
 
 int pea_op_preprocess(const float* images, int B, int H, int W, float lo, float hi, int quantize, const int* y_first,

@@ -284,6 +284,24 @@ def attention_fwd_ip(q, k, v, k_ip, v_ip, heads, ip_scale, scale=None, q_prescal
     return (o, lse) if want_lse else o
 
 
+def attention_fwd_fewq(q, k, v, k2=None, v2=None, heads=1, scale=None, q_prescaled=False, want_lse=False, kv_rows=None,
+                       kv2_rows=None):
+    """Few-query attention over the union of two key sets in one launch (pea_op_attention_fwd_fewq):
+    softmax(scale [q k^T | q k2^T]) [v ; v2], ONE softmax, head_dim 64.  q [B,Sq<=32,H*64], k/v [B,Skv,>=H*64], k2/v2
+    [B,N<=32,>=H*64] bf16 or both None.  kv_rows / kv2_rows: use only the first so many rows of each sample of k, v / k2, v2
+    (buffers with rows to spare: the batch stride stays that of the tensor only for B == 1).  -> o, or (o, lse [B,H,Sq])."""
+    B, Sq, C = q.shape
+    scale = scale if scale is not None else 0.125
+    Skv = k.shape[1] if kv_rows is None else kv_rows
+    Skv2 = 0 if k2 is None else (k2.shape[1] if kv2_rows is None else kv2_rows)
+    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
+    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    check(lib().pea_op_attention_fwd_fewq(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(k2),
+                                          0 if k2 is None else k2.stride(1), ptr(v2), 0 if v2 is None else v2.stride(1), ptr(o), C,
+                                          ptr(lse), B, heads, Sq, Skv, Skv2, scale, C // heads // 64, int(q_prescaled), stream_ptr()))
+    return (o, lse) if want_lse else o
+
+
 def attention_fwd_masked(q, k, v, heads, causal=False, kv_len=None, scale=None):
     """text-encoder attention: head_dim 64, optional causal mask and per-sample key counts (int32 [B])"""
     B, Sq, C = q.shape

@@ -1,6 +1,6 @@
 """`HipTape`: what every wrapper around an op-tape handle of libpea_hip.so shares -- the device guard, the handle and its
-release, the weight table and the state-dict loader.  `HipUNet`, `HipControlNet`, the VAE halves, `HipTextEncoder` and
-`HipImageEncoder` derive from it and add their own create call and forward."""
+release, the weight table and the state-dict loader.  `HipUNet`, `HipControlNet`, the VAE halves, `HipTextEncoder`,
+`HipImageEncoder` and `ip_adapter.HipResampler` derive from it and add their own create call and forward."""
 from __future__ import annotations
 
 import ctypes

@@ -250,11 +250,11 @@ class HipUNet(HipTape):
     _ip_tokens = None      # the tokens last handed to the context (kept alive while the cast may still be queued)
 
     def load_ip_adapter(self, adapter_or_sd):
-        """Give every cross-attention layer the `to_k_ip` / `to_v_ip` projections of an IP-Adapter (an `ip_adapter.IPAdapter`, a
-        state dict or a file path).  The UNet's own weights -- `weight_table()`, `load_state_dict` -- do not change, and neither
+        """Give every cross-attention layer the `to_k_ip` / `to_v_ip` projections of an IP-Adapter (an `ip_adapter.IPAdapter` or
+        `IPAdapterPlus`, or the state dict or file path of a base adapter).  The UNet's own weights -- `weight_table()`, `load_state_dict` -- do not change, and neither
         does any launch until `set_ip_tokens`.  Returns the IPAdapter (its `.tokens()` is the image projection)."""
-        from .ip_adapter import IPAdapter
-        ad = adapter_or_sd if isinstance(adapter_or_sd, IPAdapter) else IPAdapter(adapter_or_sd, self.cfg)
+        from .ip_adapter import IPAdapter, _LayerMap
+        ad = adapter_or_sd if isinstance(adapter_or_sd, _LayerMap) else IPAdapter(adapter_or_sd, self.cfg)
         if ad.cfg.cross_attention_dim != self.cfg.cross_attention_dim:
             raise PeaError(f"load_ip_adapter: adapter built for cross_attention_dim {ad.cfg.cross_attention_dim}, UNet has "
                            f"{self.cfg.cross_attention_dim}")
@@ -271,7 +271,7 @@ class HipUNet(HipTape):
         return ad
 
     def set_ip_tokens(self, tokens):
-        """tokens [B, N, cross_dim] (`IPAdapter.tokens(image_embeds, do_cfg=...)`, or a "plus" adapter's, computed elsewhere):
+        """tokens [B, N, cross_dim] (`IPAdapter.tokens(image_embeds, do_cfg=...)`, or `IPAdapterPlus.tokens / encode`):
         projected to every layer's image keys / values once; every call reads them until `clear_ip_tokens()`."""
         if self._ip is None:
             raise PeaError("set_ip_tokens: call load_ip_adapter first")
