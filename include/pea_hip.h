@@ -164,6 +164,26 @@ int pea_op_attention_fwd_masked(const void* Q, int ldq, const void* K, int ldk, 
 int pea_op_attention_fwd_ip(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                             const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                             float scale, float ip_scale, int q_prescaled, int causal, const int* kv_len, void* stream);
+/* Several image prompts in one launch (two IP-Adapters, each with a weight and an optional region mask), forward only, head_dim 64:
+ *   O[b,q,:] = softmax(scale q K^T) V + sum_j weight[j] * mask[j][b,q] * softmax(scale q K2_j^T) V2_j,       j < n_sets
+ * 1 <= n_sets <= 4 sets of n_keys[j] >= 1 keys with sum n_keys <= 32, lying back to back in ONE K2 / V2 pair (bf16
+ * [B][sum n_keys][ldk2 / ldv2], ld* as for pea_op_attention_fwd_ip): set j is rows off_j .. off_j + n_keys[j] of every sample, and
+ * the boundaries need not be multiples of anything.  Every set has a softmax of its own (own maximum, own sum), like the text
+ * keys.  mask[j]: NULL (a mask of 1) or device fp32 [Bm][Sq] with batch stride mask_stride[j] elements, 0 (one mask shared by
+ * the batch) or >= Sq; any finite values (a bicubically reduced binary mask leaves [0, 1]); rows at or past Sq are never read.
+ * The struct is host memory, read during the call.  kv_len, lse, q_prescaled, causal and the limits (1..128 text keys, any
+ * Sq >= 1) are those of pea_op_attention_fwd_ip; every refusal is PEA_E_SHAPE before any launch.  One set without a mask runs
+ * the kernel instance of pea_op_attention_fwd_ip (same bits); all weights 0 run the plain attention. */
+typedef struct pea_attn_ip_sets {
+  int n_sets;
+  int n_keys[4];
+  float weight[4];
+  const float* mask[4];
+  long long mask_stride[4];
+} pea_attn_ip_sets;
+int pea_op_attention_fwd_ipn(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
+                             const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv,
+                             const pea_attn_ip_sets* sets, float scale, int q_prescaled, int causal, const int* kv_len, void* stream);
 /* Few-query attention over the UNION of two key sets, forward only, head_dim 64 (nd must be 1):
  *   O = softmax(scale [Q K^T | Q K2^T]) [V ; V2]
  * ONE softmax (unlike pea_op_attention_fwd_ip), for 1 <= Sq <= 32 queries: the Perceiver Resampler of the IP-Adapter "plus" files,
@@ -389,6 +409,31 @@ int pea_unet_ip_set_scale(void* unet, float scale);
 int pea_unet_ip_clear(void* unet);
 int pea_unet_ip_destroy(void* unet);
 int pea_unet_ip_export_kv(void* unet, float* out, long long* rows, int* cols, void* stream);
+/* Several image prompts at once (a style adapter plus a face adapter, each with a scale, optional per-block scales and an
+ * optional region mask): up to four adapters ("sets") with n_tokens[j] image tokens each, sum n_tokens <= 32 -- all sets share
+ * one packed image K|V buffer [B][sum n_tokens][cols], set j in rows off_j .. off_j + n_tokens[j] of every sample, and every
+ * cross-attention layer runs ONE launch of pea_op_attention_fwd_ipn over it.  The functions above are the one-set case of the
+ * same state: pea_unet_ip_create(u, n) == pea_unet_ip_create_sets(u, 1, &n), load_weight / set_tokens / set_scale address set 0,
+ * pea_unet_ip_clear clears every set, pea_unet_ip_export_kv returns the whole packed buffer.
+ * pea_unet_ip_load_weight_set / _set_tokens_set / _set_scale_set / _clear_set: as their namesakes, for set `set`; set_tokens
+ * takes fp32 device [B][n_tokens[set]][cross_dim] and fills only that set's rows.
+ * pea_unet_ip_set_layer_scales: host float[n_layers], one factor per cross-attention layer in the order an adapter file numbers
+ * them (ip_adapter.layer_keys: down blocks, up blocks, mid block); NULL = 1 everywhere.  The weight of set j in layer l is
+ * scale_j * layer_scale_j[l], read at launch.  A set that is not live or weighs 0 in a layer is dropped from that layer's launch;
+ * with none left the plain attention runs, with one left (and no mask) the one-set launch, bit for bit.
+ * pea_unet_ip_query_counts (host only): the distinct query counts of the context's cross-attention layers (SDXL at 1024^2:
+ * 4096 and 1024); counts may be NULL (the number only).
+ * pea_unet_ip_set_mask: device fp32 [Bm][Sq] (Bm 1 = shared by the batch, or B), copied; Sq must be one of those counts; any
+ * finite values.  NULL removes the mask of that count (Sq 0: all of the set).  A set with a mask for some counts but not for all
+ * makes pea_unet_forward return PEA_E_STATE before any launch, naming the missing count. */
+int pea_unet_ip_create_sets(void* unet, int n_sets, const int* n_tokens);
+int pea_unet_ip_load_weight_set(void* unet, int set, const char* key, const float* src, long long numel, void* stream);
+int pea_unet_ip_set_tokens_set(void* unet, int set, const float* tokens, void* stream);
+int pea_unet_ip_set_scale_set(void* unet, int set, float scale);
+int pea_unet_ip_clear_set(void* unet, int set);
+int pea_unet_ip_set_layer_scales(void* unet, int set, const float* scales, int n_layers);
+int pea_unet_ip_query_counts(void* unet, int* counts, int cap, int* n);
+int pea_unet_ip_set_mask(void* unet, int set, int Sq, const float* mask, int Bm, void* stream);
 int pea_unet_destroy(void* unet);
 
 /* ControlNet (`self.controlnet(control_model_input, t, encoder_hidden_states=..., controlnet_cond=image,

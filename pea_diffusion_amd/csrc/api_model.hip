@@ -1,6 +1,8 @@
 // C-ABI, model level (include/pea_hip.h): UNet contexts, the PEA adapter, the KD trainer.
 #include <string.h>
 
+#include <algorithm>
+
 #include "../../include/pea_hip.h"
 #include "model.h"
 
@@ -493,27 +495,55 @@ int pea_unet_ip_plan(const pea_unet_config* cfg, int n_tokens, int* n_layers, in
   if (n_params) *n_params = (long long)u.kvall_total * u.cfg.cross_dim;
   return PEA_OK;
 }
-int pea_unet_ip_create(void* h, int n_tokens) {
-  NOTNULL(h, "pea_unet_ip_create");
+#define IP_SET(h, set, what)                                                                   \
+  IP_HANDLE(h, what);                                                                          \
+  SHAPECHK(set >= 0 && set < u->ip->nsets, "%s: set %d of %d", what, set, u->ip->nsets);      \
+  Tape::IpSet& e = u->ip->set[set];
+int pea_unet_ip_create_sets(void* h, int n_sets, const int* n_tokens) {
+  NOTNULL(h, "pea_unet_ip_create_sets");
+  NOTNULL(n_tokens, "pea_unet_ip_create_sets");
   Tape* u = (Tape*)h;
+  SHAPECHK(n_sets >= 1 && n_sets <= 4, "pea_unet_ip_create_sets: %d adapters (1..4)", n_sets);
   const Op* kv = nullptr;
-  RCX(ip_check(*u, n_tokens, &kv));
-  RCX(pea_unet_ip_destroy(h));                       // an adapter already loaded: replaced, behind whatever still reads it
+  int total = 0;
+  for (int j = 0; j < n_sets; ++j) {
+    RCX(ip_check(*u, n_tokens[j], &kv));
+    total += n_tokens[j];
+  }
+  SHAPECHK(total <= 32, "pea_unet_ip_create_sets: %d image tokens over all adapters (one launch takes at most 32)", total);
+  RCX(pea_unet_ip_destroy(h));                       // adapters already loaded: replaced, behind whatever still reads them
   Tape::IpState* ip = new Tape::IpState();
-  ip->n = n_tokens; ip->cols = u->kvall_total; ip->fused = kv->fused;
-  for (const WSlot& s : u->slots) ip->loaded.push_back(!(s.fused_parent == kv->fused && s.kind == W_LINEAR));
-  const size_t rows = (size_t)u->B * n_tokens, K = (size_t)u->cfg.cross_dim;
-  if (hipMalloc((void**)&ip->w, (size_t)ip->cols * K * 2) != hipSuccess || hipMalloc((void**)&ip->kv, rows * ip->cols * 2) != hipSuccess ||
-      hipMalloc((void**)&ip->tok, rows * K * 2) != hipSuccess) {
-    pea_set_error("pea_unet_ip_create: out of device memory (%zu bytes of weights)", (size_t)ip->cols * K * 2);
+  ip->nsets = n_sets; ip->total = total; ip->cols = u->kvall_total; ip->fused = kv->fused;
+  // the file's layer order (ip_adapter.layer_keys): every down block, then every up block, then the mid block; inside a group
+  // the order of the modules, which is the order of the slots
+  for (int group = 0; group < 3; ++group)
+    for (const WSlot& s : u->slots) {
+      const std::string& n = s.name;
+      if (s.fused_parent != kv->fused || s.kind != W_LINEAR || n.size() < 12 || n.compare(n.size() - 12, 12, ".to_k.weight")) continue;
+      if ((n.rfind("down_blocks.", 0) == 0 ? 0 : n.rfind("up_blocks.", 0) == 0 ? 1 : 2) != group) continue;
+      const int idx = (int)ip->layer_of_col.size();
+      ip->layer_of_col[s.row_off] = idx;
+    }
+  const size_t B = (size_t)u->B, K = (size_t)u->cfg.cross_dim;
+  bool ok = hipMalloc((void**)&ip->kv, B * total * ip->cols * 2) == hipSuccess &&
+            hipMemset(ip->kv, 0, B * total * ip->cols * 2) == hipSuccess;
+  for (int j = 0, off = 0; j < n_sets && ok; off += n_tokens[j++]) {
+    Tape::IpSet& e = ip->set[j];
+    e.n = n_tokens[j]; e.off = off;
+    for (const WSlot& s : u->slots) e.loaded.push_back(!(s.fused_parent == kv->fused && s.kind == W_LINEAR));
+    ok = hipMalloc((void**)&e.w, (size_t)ip->cols * K * 2) == hipSuccess && hipMalloc((void**)&e.tok, B * e.n * K * 2) == hipSuccess;
+  }
+  if (!ok) {
+    pea_set_error("pea_unet_ip_create: out of device memory (%zu bytes of weights per adapter)", (size_t)ip->cols * K * 2);
     delete ip;
     return PEA_E_HIP;
   }
   u->ip = ip;
   return PEA_OK;
 }
-int pea_unet_ip_load_weight(void* h, const char* key, const float* src, long long numel, void* stream) {
-  IP_HANDLE(h, "pea_unet_ip_load_weight");
+int pea_unet_ip_create(void* h, int n_tokens) { return pea_unet_ip_create_sets(h, 1, &n_tokens); }
+int pea_unet_ip_load_weight_set(void* h, int set, const char* key, const float* src, long long numel, void* stream) {
+  IP_SET(h, set, "pea_unet_ip_load_weight");
   NOTNULL(key, "pea_unet_ip_load_weight");
   NOTNULL(src, "pea_unet_ip_load_weight");
   std::string name(key);
@@ -526,37 +556,107 @@ int pea_unet_ip_load_weight(void* h, const char* key, const float* src, long lon
   if (slot < 0) { pea_set_error("pea_unet_ip_load_weight: '%s' is no to_k_ip / to_v_ip weight of this UNet", key); return PEA_E_NOTFOUND; }
   const WSlot& w = u->slots[slot];
   SHAPECHK(numel == w.numel, "pea_unet_ip_load_weight: '%s' has %lld elements, expected %lld ([%d][%d])", key, numel, w.numel, w.d0, w.d1);
-  RCX(launch_cast_f32_bf16(src, u->ip->w + (size_t)w.row_off * w.d1, numel, (hipStream_t)stream));
-  u->ip->loaded[slot] = 1;
+  RCX(launch_cast_f32_bf16(src, e.w + (size_t)w.row_off * w.d1, numel, (hipStream_t)stream));
+  e.loaded[slot] = 1;
   return PEA_OK;
 }
-int pea_unet_ip_set_tokens(void* h, const float* tokens, void* stream) {
-  IP_HANDLE(h, "pea_unet_ip_set_tokens");
+int pea_unet_ip_load_weight(void* h, const char* key, const float* src, long long numel, void* stream) {
+  return pea_unet_ip_load_weight_set(h, 0, key, src, numel, stream);
+}
+int pea_unet_ip_set_tokens_set(void* h, int set, const float* tokens, void* stream) {
+  IP_SET(h, set, "pea_unet_ip_set_tokens");
   NOTNULL(tokens, "pea_unet_ip_set_tokens");
   Tape::IpState& ip = *u->ip;
-  for (size_t i = 0; i < ip.loaded.size(); ++i)
-    if (!ip.loaded[i]) {
+  for (size_t i = 0; i < e.loaded.size(); ++i)
+    if (!e.loaded[i]) {
       const std::string& n = u->slots[i].name;
       pea_set_error("pea_unet_ip_set_tokens: '%s_ip.weight' was never loaded", n.substr(0, n.size() - 7).c_str());
       return PEA_E_STATE;
     }
   hipStream_t s = (hipStream_t)stream;
-  const int rows = u->B * ip.n, K = u->cfg.cross_dim;
-  RCX(launch_cast_f32_bf16(tokens, ip.tok, (long long)rows * K, s));
-  GemmP p; fill_gemm(p);
-  p.A = ip.tok; p.lda = K; p.M = rows; p.K = K; p.N = ip.cols; p.W = ip.w; p.ldw = K; p.C = ip.kv; p.ldc = ip.cols;
-  RCX(launch_gemm(p, s));
-  ip.live = true;
+  const int rows = u->B * e.n, K = u->cfg.cross_dim;
+  RCX(launch_cast_f32_bf16(tokens, e.tok, (long long)rows * K, s));
+  // one adapter: ONE GEMM over all samples.  Several: the set's rows of a sample are not adjacent to those of the next, so one
+  // GEMM per sample straight into its rows of the packed buffer (once per image, B is the CFG batch)
+  const int launches = ip.nsets == 1 ? 1 : u->B, m = rows / launches;
+  for (int b = 0; b < launches; ++b) {
+    GemmP p; fill_gemm(p);
+    p.A = e.tok + (size_t)b * m * K; p.lda = K; p.M = m; p.K = K; p.N = ip.cols; p.W = e.w; p.ldw = K;
+    p.C = ip.kv + ((size_t)b * ip.total + e.off) * ip.cols; p.ldc = ip.cols;
+    RCX(launch_gemm(p, s));
+  }
+  e.live = true;
   return PEA_OK;
 }
-int pea_unet_ip_set_scale(void* h, float scale) {
-  IP_HANDLE(h, "pea_unet_ip_set_scale");
-  u->ip->scale = scale;
+int pea_unet_ip_set_tokens(void* h, const float* tokens, void* stream) { return pea_unet_ip_set_tokens_set(h, 0, tokens, stream); }
+int pea_unet_ip_set_scale_set(void* h, int set, float scale) {
+  IP_SET(h, set, "pea_unet_ip_set_scale");
+  e.scale = scale;
+  return PEA_OK;
+}
+int pea_unet_ip_set_scale(void* h, float scale) { return pea_unet_ip_set_scale_set(h, 0, scale); }
+int pea_unet_ip_set_layer_scales(void* h, int set, const float* scales, int n_layers) {
+  IP_SET(h, set, "pea_unet_ip_set_layer_scales");
+  if (!scales) {                                     // back to 1 in every layer
+    e.layer_scale.clear();
+    return PEA_OK;
+  }
+  const int want = (int)u->ip->layer_of_col.size();
+  SHAPECHK(n_layers == want, "pea_unet_ip_set_layer_scales: %d scales, this UNet has %d cross-attention layers", n_layers, want);
+  e.layer_scale.assign(scales, scales + n_layers);
+  return PEA_OK;
+}
+static void ip_query_counts(const Tape& u, std::vector<int>& out) {
+  for (const Op& o : u.ops)
+    if (o.kind == OP_ATTN && o.b == u.t_kvall && std::find(out.begin(), out.end(), o.p1) == out.end()) out.push_back(o.p1);
+}
+int pea_unet_ip_query_counts(void* h, int* counts, int cap, int* n) {
+  NOTNULL(h, "pea_unet_ip_query_counts");
+  std::vector<int> c;
+  ip_query_counts(*(Tape*)h, c);
+  if (n) *n = (int)c.size();
+  for (int i = 0; counts && i < cap && i < (int)c.size(); ++i) counts[i] = c[i];
+  return PEA_OK;
+}
+int pea_unet_ip_set_mask(void* h, int set, int Sq, const float* mask, int Bm, void* stream) {
+  IP_SET(h, set, "pea_unet_ip_set_mask");
+  if (!mask) {                                       // drop the mask of that count, or (Sq == 0) all of them
+    HIPCHK(hipDeviceSynchronize());                  // a queued forward may still read them
+    for (auto it = e.mask.begin(); it != e.mask.end();)
+      if (Sq == 0 || it->first == Sq) { (void)hipFree(it->second.first); it = e.mask.erase(it); } else ++it;
+    return PEA_OK;
+  }
+  std::vector<int> c;
+  ip_query_counts(*u, c);
+  if (std::find(c.begin(), c.end(), Sq) == c.end()) {
+    pea_set_error("pea_unet_ip_set_mask: no cross-attention layer of this context has %d queries (pea_unet_ip_query_counts)", Sq);
+    return PEA_E_SHAPE;
+  }
+  SHAPECHK(Bm == 1 || Bm == u->B, "pea_unet_ip_set_mask: Bm=%d (1, or the context's batch %d)", Bm, u->B);
+  auto it = e.mask.find(Sq);
+  if (it != e.mask.end() && it->second.second != Bm) {
+    HIPCHK(hipDeviceSynchronize());
+    (void)hipFree(it->second.first);
+    e.mask.erase(it);
+    it = e.mask.end();
+  }
+  if (it == e.mask.end()) {
+    float* buf = nullptr;
+    HIPCHK(hipMalloc((void**)&buf, (size_t)Bm * Sq * sizeof(float)));
+    it = e.mask.emplace(Sq, std::make_pair(buf, Bm)).first;
+  }
+  HIPCHK(hipMemcpyAsync(it->second.first, mask, (size_t)Bm * Sq * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return PEA_OK;
+}
+int pea_unet_ip_clear_set(void* h, int set) {
+  IP_SET(h, set, "pea_unet_ip_clear");
+  e.live = false;
   return PEA_OK;
 }
 int pea_unet_ip_clear(void* h) {
   NOTNULL(h, "pea_unet_ip_clear");
-  if (((Tape*)h)->ip) ((Tape*)h)->ip->live = false;
+  if (((Tape*)h)->ip)
+    for (Tape::IpSet& e : ((Tape*)h)->ip->set) e.live = false;
   return PEA_OK;
 }
 int pea_unet_ip_destroy(void* h) {
@@ -569,11 +669,13 @@ int pea_unet_ip_destroy(void* h) {
 }
 int pea_unet_ip_export_kv(void* h, float* out, long long* rows, int* cols, void* stream) {
   IP_HANDLE(h, "pea_unet_ip_export_kv");
-  const long long r = (long long)u->B * u->ip->n;
+  const long long r = (long long)u->B * u->ip->total;
   if (rows) *rows = r;
   if (cols) *cols = u->ip->cols;
   if (!out) return PEA_OK;
-  if (!u->ip->live) { pea_set_error("pea_unet_ip_export_kv: no tokens set"); return PEA_E_STATE; }
+  bool live = false;
+  for (const Tape::IpSet& e : u->ip->set) live = live || e.live;
+  if (!live) { pea_set_error("pea_unet_ip_export_kv: no tokens set"); return PEA_E_STATE; }
   return launch_cast_bf16_f32(u->ip->kv, out, r * u->ip->cols, (hipStream_t)stream);
 }
 int pea_unet_num_weights(void* h) { return h ? (int)((Tape*)h)->slots.size() : 0; }

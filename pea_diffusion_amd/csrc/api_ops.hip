@@ -272,6 +272,28 @@ int pea_op_attention_fwd_ip(const void* Q, int ldq, const void* K, int ldk, cons
   p.K2 = (const bf16*)K2; p.V2 = (const bf16*)V2; p.ldk2 = ldk2; p.ldv2 = ldv2; p.Skv2 = Skv2; p.scale2 = ip_scale;
   return launch_attention_fwd(p, (hipStream_t)stream);
 }
+int pea_op_attention_fwd_ipn(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
+                             const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv,
+                             const pea_attn_ip_sets* sets, float scale, int q_prescaled, int causal, const int* kv_len, void* stream) {
+  SHAPECHK(sets && K2 && V2, "pea_op_attention_fwd_ipn: no image keys");
+  SHAPECHK(sets->n_sets >= 1 && sets->n_sets <= 4, "pea_op_attention_fwd_ipn: 1..4 image key sets (n_sets=%d)", sets->n_sets);
+  AttnP p;
+  memset(&p, 0, sizeof(p));
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
+  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = 1;
+  p.q_prescaled = q_prescaled; p.causal = causal; p.kv_len = kv_len;
+  p.K2 = (const bf16*)K2; p.V2 = (const bf16*)V2; p.ldk2 = ldk2; p.ldv2 = ldv2;
+  p.nset = sets->n_sets;
+  int total = 0;
+  for (int j = 0; j < p.nset; ++j) {
+    SHAPECHK(sets->n_keys[j] >= 1 && sets->n_keys[j] <= 32, "pea_op_attention_fwd_ipn: image key set %d holds %d keys (1..32)", j, sets->n_keys[j]);
+    total += sets->n_keys[j];
+    p.set_end[j] = total; p.set_w[j] = sets->weight[j]; p.set_mask[j] = sets->mask[j]; p.set_mstride[j] = sets->mask_stride[j];
+  }
+  SHAPECHK(total <= 32, "pea_op_attention_fwd_ipn: the image key sets hold %d keys together, at most 32", total);
+  p.Skv2 = total;
+  return launch_attention_fwd(p, (hipStream_t)stream);
+}
 int pea_op_attention_fwd_fewq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                               const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                               float scale, int nd, int q_prescaled, void* stream) {

@@ -967,8 +967,20 @@ __device__ __forceinline__ float xhalf_sum(float x) {
 // The LDS allows two workgroups per CU at most, so the launch bound asks for no more.  What hipcc makes of the four instances
 // (profiles/ip_adapter_bench_regs.txt): 104 / 106 / 131 / 163 VGPRs for 1..4 text key blocks, no AGPRs, no scratch -- against
 // 68 / 88 / 91 / 130 without the image keys; all under the 256 a two-workgroup CU leaves a wave.
-template <int KB, bool IP = false>
+//
+// MS (with IP): several image prompts at once, O = o_text + sum_j w_j m_j[b][q] softmax(s Q K2_j^T) V2_j for 1..4 sets that lie
+// back to back in the SAME 32-key block (4 + 16, 16 + 16, 4 + 4 + 16 slots of it), each with a weight and an optional per-query
+// mask (AttnP::nset / set_end / set_w / set_mask).  No more LDS and no more MFMAs than one set: what is added is a softmax per
+// set -- every set its own maximum and its own sum over its rows of the one score tile, so a spike in one set cannot underflow
+// another set or the text term.  A query row lives on one lane (both half-waves), so w_j m_j is one scalar per lane, set and
+// unit.  Normalisation: w_j m_j / sum_j is folded into P BEFORE its bf16 rounding (|factor x e| <= |w_j m_j|: the product is
+// rounded once, like P of the one-set instance), and all sets go through the ONE PV product of the block; one accumulator per
+// set would cost 32 more VGPRs and 4 more MFMAs per set.  A set with w_j m_j = 0 therefore contributes exact zeros, and a mask
+// of ones gives the bits of no mask (w x 1.0f).  Padding slots (score -inf, e = 0) count as keys of the last set.  The instance
+// serves whatever the one-set instance does not: its launch is decided in launch_attention_fwd (attn_resolve_sets).
+template <int KB, bool IP = false, bool MS = false>
 __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP p, int upw) {
+  static_assert(IP || !MS, "several image key sets are sets of the image key block");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KT = (KB + 1) / 2;                               // 64-key tiles
   char* const Ksm = smem;
@@ -997,7 +1009,7 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
     }
     if constexpr (IP) {                                          // waves 0 / 1: the 32 rows of K2, waves 2 / 3: those of V2
       const bool isv = wave >= 2;
-      const bf16* b2 = isv ? p.V2 + (long long)b * p.Skv2 * p.ldv2 : p.K2 + (long long)b * p.Skv2 * p.ldk2;
+      const bf16* b2 = isv ? p.V2 + (long long)b * p.k2_brows * p.ldv2 : p.K2 + (long long)b * p.k2_brows * p.ldk2;
       const TileSrc src2 = tile_src(b2 + head * 64, isv ? p.ldv2 : p.ldk2, p.Skv2, wave & 1, lane);
       stage_tile(src2, 0, isv ? V2sm : K2sm, wave & 1);
     }
@@ -1032,6 +1044,17 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
     for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qst + rf_off[s]);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (u + 1 < u_end) stage_q((u + 1) * 128 + wave * 32);      // next unit's rows fly under this unit's work
+    [[maybe_unused]] float wm[4];                                // MS: w_j m_j[b][this lane's query]; the loads fly under the score products
+    if constexpr (MS) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        wm[j] = 0.f;
+        if (j < p.nset) {
+          const float* mj = p.set_mask[j];
+          wm[j] = p.set_w[j] * (mj && qvalid ? mj[(long long)b * p.set_mstride[j] + qrow] : 1.f);
+        }
+      }
+    }
     // S^T[key][q] = K . Q^T over the KB key blocks
     f32x16 sacc[KB];
 #pragma unroll
@@ -1103,19 +1126,90 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
     [[maybe_unused]] f32x16 oacc2[2];
     [[maybe_unused]] float inv2 = 0.f;                           // scale2 / (sum of the image softmax)
     if constexpr (IP) {
-      float mx2 = sacc2[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx2 = fmaxf(mx2, sacc2[r]);
-      const float mc2 = xhalf_max(mx2) * c;
-      float ls2 = 0.f;
       bf16x8 pf2[2];
+      if constexpr (MS) {
+        // slot r of this lane holds key kc(r) + 4 fh, kc(r) = (r & 3) + 8 (r >> 2); set j owns keys set_end[j - 1] .. set_end[j].
+        // The sets lie in key order and padding slots score -inf, so "at or behind the first key of set j" is all that is ever
+        // asked: kb >= set_end[j - 1] - kc(r), a lane value against a scalar.  Sets are peeled off from the last one down -- what
+        // is left when set 0's turn comes is set 0 -- and the passes of a set that is not there are skipped as a whole.
+        const int kb = 4 * fh;
+        const auto from = [&](int j, int r) { return kb >= p.set_end[j - 1] - ((r & 3) + 8 * (r >> 2)); };
+        float mcs[4], fs[4], cur[16], mcr[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = fast_exp2(fmaf(sacc2[r], c, -mc2));
-        ls2 += e;
-        pf2[r >> 3][r & 7] = (bf16)e;
+        for (int r = 0; r < 16; ++r) cur[r] = sacc2[r];
+#pragma unroll
+        for (int j = 3; j >= 1; --j) {
+          mcs[j] = 0.f;
+          if (j < p.nset) {
+            float m = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              m = fmaxf(m, from(j, r) ? cur[r] : -INFINITY);
+              cur[r] = from(j, r) ? -INFINITY : cur[r];
+            }
+            mcs[j] = xhalf_max(m) * c;
+          }
+        }
+        {
+          float m = cur[0];
+#pragma unroll
+          for (int r = 1; r < 16; ++r) m = fmaxf(m, cur[r]);
+          mcs[0] = xhalf_max(m) * c;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mcr[r] = mcs[0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j)
+          if (j < p.nset) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mcr[r] = from(j, r) ? mcs[j] : mcr[r];
+          }
+        float e2[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cur[r] = e2[r] = fast_exp2(fmaf(sacc2[r], c, -mcr[r]));
+#pragma unroll
+        for (int j = 3; j >= 1; --j) {
+          fs[j] = 0.f;
+          if (j < p.nset) {
+            float ls2 = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              ls2 += from(j, r) ? cur[r] : 0.f;
+              cur[r] = from(j, r) ? 0.f : cur[r];
+            }
+            fs[j] = wm[j] / xhalf_sum(ls2);
+          }
+        }
+        {
+          float ls2 = cur[0];
+#pragma unroll
+          for (int r = 1; r < 16; ++r) ls2 += cur[r];
+          fs[0] = wm[0] / xhalf_sum(ls2);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mcr[r] = fs[0];                // (the register array serves both chains)
+#pragma unroll
+        for (int j = 1; j < 4; ++j)
+          if (j < p.nset) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mcr[r] = from(j, r) ? fs[j] : mcr[r];
+          }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) pf2[r >> 3][r & 7] = (bf16)(e2[r] * mcr[r]);
+      } else {
+        float mx2 = sacc2[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mx2 = fmaxf(mx2, sacc2[r]);
+        const float mc2 = xhalf_max(mx2) * c;
+        float ls2 = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float e = fast_exp2(fmaf(sacc2[r], c, -mc2));
+          ls2 += e;
+          pf2[r >> 3][r & 7] = (bf16)e;
+        }
+        inv2 = p.scale2 / xhalf_sum(ls2);
       }
-      inv2 = p.scale2 / xhalf_sum(ls2);
       const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int db = 0; db < 2; ++db) {
@@ -1138,7 +1232,8 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
         bf16x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          if constexpr (IP) o[j] = (bf16)(oacc[db][4 * g + j] * inv + oacc2[db][4 * g + j] * inv2);
+          if constexpr (MS) o[j] = (bf16)(oacc[db][4 * g + j] * inv + oacc2[db][4 * g + j]);       // the factors are in P
+          else if constexpr (IP) o[j] = (bf16)(oacc[db][4 * g + j] * inv + oacc2[db][4 * g + j] * inv2);
           else o[j] = (bf16)(oacc[db][4 * g + j] * inv);
         }
         *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
@@ -2416,7 +2511,30 @@ static int attn_check_ip(const AttnP& p) {
   SHAPECHK(p.Skv2 >= 1 && p.Skv2 <= 32, "attention: the second key set holds 1..32 keys (Skv2=%d)", p.Skv2);
   SHAPECHK(p.ldk2 % 8 == 0 && p.ldv2 % 8 == 0 && p.ldk2 >= 64 * p.H && p.ldv2 >= 64 * p.H,
            "attention: ldk2 / ldv2 must be multiples of 8 and hold every head (ldk2=%d ldv2=%d)", p.ldk2, p.ldv2);
+  SHAPECHK(p.nset >= 0 && p.nset <= 4, "attention: 1..4 image key sets (%d)", p.nset);
+  for (int j = 0, lo = 0; j < p.nset; lo = p.set_end[j++]) {
+    SHAPECHK(p.set_end[j] > lo, "attention: image key set %d is empty", j);
+    SHAPECHK(!p.set_mask[j] || p.set_mstride[j] == 0 || p.set_mstride[j] >= p.Sq,
+             "attention: the mask of image key set %d has batch stride %lld: 0 (shared) or >= Sq=%d", j, p.set_mstride[j], p.Sq);
+  }
+  SHAPECHK(p.nset == 0 || p.set_end[p.nset - 1] == p.Skv2, "attention: the image key sets end at row %d of %d", p.set_end[p.nset - 1], p.Skv2);
   return PEA_OK;
+}
+// several image key sets -> the launch that serves them: all weights 0 is the plain attention (as the one-set caller does at scale
+// 0), one set without a mask is the one-set instance (same bits as pea_op_attention_fwd_ip), everything else the MS instances
+static void attn_resolve_sets(AttnP& p) {
+  if (!p.nset) return;
+  bool any = false;
+  for (int j = 0; j < p.nset; ++j) any = any || p.set_w[j] != 0.f;
+  if (!any) {
+    p.K2 = p.V2 = nullptr;
+    p.nset = 0;
+  } else if (p.nset == 1 && !p.set_mask[0]) {
+    p.scale2 = p.set_w[0];
+    p.nset = 0;
+  } else {
+    for (int j = p.nset; j < 4; ++j) { p.set_end[j] = p.Skv2; p.set_w[j] = 0.f; p.set_mask[j] = nullptr; }
+  }
 }
 static int attn_check(const AttnP& p) {
   SHAPECHK(p.B > 0 && p.H > 0 && p.Sq > 0 && p.Skv > 0, "attention: empty problem");
@@ -2445,13 +2563,13 @@ static int launch_lds(dim3 grid, int bytes, hipStream_t s, const Args&... args) 
                  : launch_lds<KERNEL_NOTR>(grid, lds, s, p, ##__VA_ARGS__))
 
 // run-time (key blocks of 32, prescaled Q) -> instantiation, one dispatch per cross-attention kernel family
-template <bool IP = false>                                         // IP: with a second key set (AttnP::K2)
+template <bool IP = false, bool MS = false>                        // IP: with a second key set (AttnP::K2); MS: that set is several
 static int launch_xattn_fwd(int kb, dim3 grid, int lds, hipStream_t s, const AttnP& p, int upw) {
   switch (kb) {
-    case 1: return launch_lds<xattn_fwd_kernel<1, IP>>(grid, lds, s, p, upw);
-    case 2: return launch_lds<xattn_fwd_kernel<2, IP>>(grid, lds, s, p, upw);
-    case 3: return launch_lds<xattn_fwd_kernel<3, IP>>(grid, lds, s, p, upw);
-    default: return launch_lds<xattn_fwd_kernel<4, IP>>(grid, lds, s, p, upw);
+    case 1: return launch_lds<xattn_fwd_kernel<1, IP, MS>>(grid, lds, s, p, upw);
+    case 2: return launch_lds<xattn_fwd_kernel<2, IP, MS>>(grid, lds, s, p, upw);
+    case 3: return launch_lds<xattn_fwd_kernel<3, IP, MS>>(grid, lds, s, p, upw);
+    default: return launch_lds<xattn_fwd_kernel<4, IP, MS>>(grid, lds, s, p, upw);
   }
 }
 static int launch_xattn_bwd1(int kb, dim3 grid, hipStream_t s, const AttnP& p, int upw) {
@@ -2493,6 +2611,7 @@ static int attn_fwd_nd(const AttnP& p, hipStream_t s) {
       int upw = (int)((units + 511) / 512);                       // one round of two workgroups per CU (66 KB of LDS each, 74 KB with image keys)
       upw = upw < 1 ? 1 : (upw > nu ? nu : upw);
       const dim3 xgrid(cdiv(nu, upw), p.H, p.B);
+      if (p.K2 && p.nset) return launch_xattn_fwd<true, true>(kb, xgrid, lds, s, p, upw);
       return p.K2 ? launch_xattn_fwd<true>(kb, xgrid, lds, s, p, upw) : launch_xattn_fwd(kb, xgrid, lds, s, p, upw);
     }
   }
@@ -2559,6 +2678,9 @@ int launch_attention_fwd(const AttnP& p0, hipStream_t s) {
   if (p.K2 || p.V2) {
     rc = attn_check_ip(p);
     if (rc) return rc;
+    SHAPECHK(p.k2_brows == 0 || p.k2_brows >= p.Skv2, "attention: %d image key rows per sample hold no %d keys", p.k2_brows, p.Skv2);
+    if (!p.k2_brows) p.k2_brows = p.Skv2;
+    attn_resolve_sets(p);
   }
   if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = p.nd; }
   const int keys = p.Skv + (p.K2 ? p.Skv2 : 0);                    // both key sets: one more score / value product each

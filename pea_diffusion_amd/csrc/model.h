@@ -192,17 +192,34 @@ struct Tape {
   int time_cond_dim = 0;
   int t_tcond = -1;
   int set_timestep_cond(const float* cond, hipStream_t s);
-  // Image prompt (IP-Adapter, graph 0, inference only; api_model.hip: pea_unet_ip_*): a second K|V stack over n image tokens,
-  // columns laid out as the text stack's (t_kvall), so a cross-attention op finds its image keys / values at its own bcol / ccol.
-  // While `live` (and scale != 0) forward() hands them to the attention as AttnP::K2 / V2.  Outside the arenas: release_acts keeps it.
-  struct IpState {
-    int n = 0, cols = 0, fused = -1;       // image tokens per sample; width of the stack; the text stack's FusedMat
-    bf16 *w = nullptr, *kv = nullptr, *tok = nullptr;   // [cols][cross_dim], [B*n][cols], [B*n][cross_dim]
+  // Image prompts (IP-Adapter, graph 0, inference only; api_model.hip: pea_unet_ip_*): up to four adapters ("sets"), each a
+  // second K|V stack over its own n image tokens, columns laid out as the text stack's (t_kvall), so a cross-attention op finds
+  // its image keys / values at its own bcol / ccol.  All sets share ONE packed image K|V buffer [B][total][cols], set j in rows
+  // off .. off + n of every sample, so a layer hands the attention one K2 / V2 pair plus the table of sets (Tape::ip_attach: the
+  // run of sets that are live with a non-zero weight in that layer).  Outside the arenas: release_acts keeps it.
+  struct IpSet {
+    int n = 0, off = 0;                    // image tokens per sample; first row of the set in a sample of the packed buffer
+    bf16 *w = nullptr, *tok = nullptr;     // [cols][cross_dim], [B*n][cross_dim]
     std::vector<char> loaded;              // per member of the stack, in slot order
     bool live = false;
     float scale = 1.f;
-    ~IpState() { for (bf16* b : {w, kv, tok}) if (b) (void)hipFree(b); }
+    std::vector<float> layer_scale;        // per cross-attention layer in the adapter file's order; empty = 1 everywhere
+    std::map<int, std::pair<float*, int>> mask;   // query count -> (device fp32 [Bm][Sq], Bm in {1, B}); empty = no mask
   };
+  struct IpState {
+    int nsets = 0, total = 0, cols = 0, fused = -1;   // sets, rows per sample, width of the stack, the text stack's FusedMat
+    bf16* kv = nullptr;                    // [B][total][cols], zero until a set's tokens fill its rows
+    IpSet set[4];
+    std::map<int, int> layer_of_col;       // K column of a cross-attention layer in the stack -> its index in the file's order
+    ~IpState() {
+      if (kv) (void)hipFree(kv);
+      for (IpSet& s : set) {
+        for (bf16* b : {s.w, s.tok}) if (b) (void)hipFree(b);
+        for (auto& m : s.mask) (void)hipFree(m.second.first);
+      }
+    }
+  };
+  int ip_attach(const Op& o, AttnP& p);   // the image key sets of cross-attention op o, or none (tape.hip)
   IpState* ip = nullptr;
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;

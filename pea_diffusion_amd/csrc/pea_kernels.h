@@ -123,10 +123,17 @@ struct AttnP {
                                    // MFMA in the log2 domain with no further rounding; dQ is still the gradient w.r.t. the UNSCALED q
   const float* bias;               // forward, masked instance only: additive score bias [H][Sq][Skv] in the LOG2 domain (T5 relative positions), may be null
   // forward only, head_dim 64, <= 128 keys: a second, independent key set over the same Q (IP-Adapter's image tokens),
-  //   O = softmax(scale Q K^T) V + scale2 * softmax(scale Q K2^T) V2,   1 <= Skv2 <= 32, batch stride Skv2 * ldk2 / ldv2.
+  //   O = softmax(scale Q K^T) V + scale2 * softmax(scale Q K2^T) V2,   1 <= Skv2 <= 32, batch stride Skv2 * ldk2 / ldv2 (k2_brows below: more rows per sample).
   // kv_len masks K / V only and lse stays that of the first softmax.  Null K2 (a memset struct): no second key set.
   const bf16 *K2, *V2; int ldk2, ldv2, Skv2;
   float scale2;
+  // nset >= 1: the Skv2 image keys are nset (<= 4) sets lying back to back, set j ending before row set_end[j] (set_end[nset - 1]
+  // == Skv2), each with a softmax, a weight and an optional per-query mask of its own,
+  //   O = softmax(scale Q K^T) V + sum_j set_w[j] * set_mask[j][b][q] * softmax(scale Q K2_j^T) V2_j.
+  // set_mask[j]: fp32 [.][Sq] with batch stride set_mstride[j] (0: shared by the batch), null = 1.  nset == 0: one set, scale2.
+  // k2_brows: rows per sample of the K2 / V2 buffer where that is more than Skv2 (a run of sets inside a packed buffer), 0 = Skv2.
+  int nset; int set_end[4]; float set_w[4]; int k2_brows;
+  const float* set_mask[4]; long long set_mstride[4];
 };
 int attention_bwd_nsplit(int B, int H, int Sq, int Skv);
 size_t attention_bwd_scratch_bytes(int B, int H, int Sq, int Skv, int nd = 1);

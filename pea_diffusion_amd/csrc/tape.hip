@@ -457,6 +457,64 @@ static int geglu_stash_form(const Op& o) {
   return (o.p3 == 3 && o.c >= 0 && o.p1 == 0) ? 1 : 0;
 }
 
+// Image prompts of cross-attention op o.  The weight of set j in this layer is scale_j * layer_scale_j[layer], read here, at
+// launch.  A set that is not live or weighs 0 here is dropped: the launch takes the run of rows from the first to the last
+// remaining set (AttnP::k2_brows keeps the packed buffer's batch stride), so one remaining set without a mask is the one-set
+// launch of a context that holds that adapter alone, bit for bit, and none is the plain attention.  A dropped set BETWEEN two
+// remaining ones stays in the run with weight 0 -- exact zeros in P; its rows are zero or an earlier image's, finite either way.
+int Tape::ip_attach(const Op& o, AttnP& p) {
+  IpState& st = *ip;
+  const auto lay = st.layer_of_col.find(o.bcol);
+  float w[4] = {0.f, 0.f, 0.f, 0.f};
+  int first = -1, last = -1;
+  for (int j = 0; j < st.nsets; ++j) {
+    const IpSet& e = st.set[j];
+    if (!e.live) continue;
+    w[j] = e.scale * (e.layer_scale.empty() || lay == st.layer_of_col.end() ? 1.f : e.layer_scale[lay->second]);
+    if (w[j] == 0.f) continue;
+    if (first < 0) first = j;
+    last = j;
+  }
+  if (first < 0) return PEA_OK;
+  const int row0 = st.set[first].off;
+  p.K2 = st.kv + (size_t)row0 * st.cols + o.bcol; p.V2 = st.kv + (size_t)row0 * st.cols + o.ccol; p.ldk2 = p.ldv2 = st.cols;
+  p.Skv2 = st.set[last].off + st.set[last].n - row0; p.k2_brows = st.total;
+  if (first == last && st.set[first].mask.empty()) {
+    p.scale2 = w[first];
+    return PEA_OK;
+  }
+  p.nset = last - first + 1;
+  for (int j = first; j <= last; ++j) {
+    const IpSet& e = st.set[j];
+    const int i = j - first;
+    p.set_end[i] = e.off + e.n - row0; p.set_w[i] = w[j];
+    if (w[j] == 0.f || e.mask.empty()) continue;
+    const auto m = e.mask.find(o.p1);
+    if (m == e.mask.end()) {                                       // ip_masks_complete has passed: not reached from forward()
+      pea_set_error("unet: image prompt %d has masks, but none for the %d queries of this layer (pea_unet_ip_set_mask)", j, o.p1);
+      return PEA_E_STATE;
+    }
+    p.set_mask[i] = m->second.first; p.set_mstride[i] = m->second.second == 1 ? 0 : o.p1;
+  }
+  return PEA_OK;
+}
+// a live set with a mask for some of the context's cross-attention query counts needs one for each: a layer without would
+// silently run with a mask of 1.  Checked before the first launch of a forward.
+static int ip_masks_complete(const Tape& u) {
+  if (!u.ip) return PEA_OK;
+  for (int j = 0; j < u.ip->nsets; ++j) {
+    const Tape::IpSet& e = u.ip->set[j];
+    if (!e.live || e.mask.empty()) continue;
+    for (const Op& o : u.ops)
+      if (o.kind == OP_ATTN && o.b == u.t_kvall && !e.mask.count(o.p1)) {
+        pea_set_error("pea_unet_forward: image prompt %d has a mask for %d queries but none for the layers with %d queries; "
+                      "pea_unet_ip_set_mask needs every count of pea_unet_ip_query_counts", j, e.mask.begin()->first, o.p1);
+        return PEA_E_STATE;
+      }
+  }
+  return PEA_OK;
+}
+
 int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype, const void* text, int text_dtype,
                   const float* time_ids, float* eps, hipStream_t s) {
   std::string miss;
@@ -464,6 +522,7 @@ int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype
     pea_set_error("unet: weight '%s' was never loaded", miss.c_str());
     return PEA_E_STATE;
   }
+  RC(ip_masks_complete(*this));
   RC(ensure_acts());
   RC(ensure_folded(s));
   x_in = x; t_in = t; tid_in = time_ids; eps_out = eps;
@@ -671,9 +730,7 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
         p.q_prescaled = o.pre;
         if (o.mask & 4) p.bias = rel_bias;
         if (cross_kvlen && o.b == t_kvall) p.kv_len = cross_kvlen;
-        if (ip && ip->live && ip->scale != 0.f && o.b == t_kvall) {    // image prompt: the layer's own columns of the image K|V
-          p.K2 = ip->kv + o.bcol; p.V2 = ip->kv + o.ccol; p.ldk2 = p.ldv2 = ip->cols; p.Skv2 = ip->n; p.scale2 = ip->scale;
-        }
+        if (ip && o.b == t_kvall) RC(ip_attach(o, p));               // image prompts: the layer's own columns of the image K|V
         RC(launch_attention_fwd(p, s));
         break;
       }

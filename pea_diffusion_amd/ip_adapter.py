@@ -65,6 +65,52 @@ def layer_keys(cfg) -> List[Tuple[int, str]]:
     return [(2 * n + 1, pfx) for n, (pfx, _) in enumerate(_cross_layers(cfg))]
 
 
+def downsample_mask(mask, h_l: int, w_l: int) -> torch.Tensor:
+    """A region mask [h, w] or [1|B, h, w] (any resolution, any float or bool dtype) reduced to the h_l x w_l grid of one
+    cross-attention layer: `F.interpolate(mode="bicubic", align_corners=False)` without antialiasing, flattened row-major to fp32
+    [1|B, h_l * w_l] -- the rule of diffusers' IPAdapterMaskProcessor.downsample as restated in DESIGN.md section 2 (unpinned:
+    diffusers is not installed here).  Bicubic taps are negative at distance > 1, so a binary mask comes out below 0 and above 1
+    next to its edges; the attention takes the values as they are."""
+    m = torch.as_tensor(mask)
+    if m.dim() == 2:
+        m = m[None]
+    if m.dim() != 3:
+        raise PeaError(f"downsample_mask: mask {tuple(m.shape)}, expected [h, w] or [1|B, h, w]")
+    out = torch.nn.functional.interpolate(m[:, None].to(torch.float32), size=(int(h_l), int(w_l)), mode="bicubic", align_corners=False)
+    return out.reshape(m.shape[0], int(h_l) * int(w_l)).contiguous()
+
+
+BLOCK_SCALE_KEYS = "down | up | mid, `down_blocks.<i>` / `up_blocks.<i>` / `mid_block`, any longer prefix of an attn2 module name, or `default`"
+
+
+def resolve_layer_scales(cfg, spec) -> List[float]:
+    """One adapter's scale as a per-layer vector in the order of `layer_keys(cfg)`.  spec: a number (every layer), or a dict of
+    per-block scales (InstantStyle: `{"up": {"block_0": ...}}` is written here as `{"up_blocks.0": ...}`).  Accepted keys:
+      "down", "up", "mid"                       every cross-attention layer of the down blocks / up blocks / mid block
+      "down_blocks.1", "up_blocks.0", "mid_block", "up_blocks.0.attentions.1", ...
+                                                any prefix of the names `_cross_layers(cfg)` lists, cut at a `.`
+      "default"                                 layers no other key names (0 when absent: a dict switches off what it leaves out)
+    The longest matching key wins.  A key that matches no layer is refused."""
+    names = [pfx for pfx, _ in _cross_layers(cfg)]
+    if not isinstance(spec, dict):
+        return [float(spec)] * len(names)
+    short = {"down": "down_blocks", "up": "up_blocks", "mid": "mid_block"}
+    keys = {}
+    for k, v in spec.items():
+        if k == "default":
+            continue
+        full = short.get(k, k)
+        if not any(n == full or n.startswith(full + ".") for n in names):
+            raise PeaError(f"resolve_layer_scales: '{k}' names no cross-attention layer of this UNet (keys: {BLOCK_SCALE_KEYS})")
+        keys[full] = float(v)
+    default = float(spec.get("default", 0.0))
+    out = []
+    for n in names:
+        hit = [k for k in keys if n == k or n.startswith(k + ".")]
+        out.append(keys[max(hit, key=len)] if hit else default)
+    return out
+
+
 def _groups(path_or_dict, who: str) -> Dict[str, Dict[str, torch.Tensor]]:
     """the two groups of a file of either kind, from the nested dict itself, a pickle of it, or the flat `.safetensors` form"""
     from .lora import load_lora_state_dict

@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import PeaError, check, lib, ptr, stream_ptr
 
 BF = torch.bfloat16
 
@@ -281,6 +281,49 @@ def attention_fwd_ip(q, k, v, k_ip, v_ip, heads, ip_scale, scale=None, q_prescal
     check(lib().pea_op_attention_fwd_ip(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(k_ip), k_ip.stride(1),
                                         ptr(v_ip), v_ip.stride(1), ptr(o), C, ptr(lse), B, heads, Sq, k.shape[1], k_ip.shape[1],
                                         scale, float(ip_scale), int(q_prescaled), int(causal), ptr(kv_len), stream_ptr()))
+    return (o, lse) if want_lse else o
+
+
+class IpSets(ctypes.Structure):
+    """pea_attn_ip_sets of include/pea_hip.h"""
+    _fields_ = [("n_sets", ctypes.c_int), ("n_keys", ctypes.c_int * 4), ("weight", ctypes.c_float * 4),
+                ("mask", ctypes.c_void_p * 4), ("mask_stride", ctypes.c_longlong * 4)]
+
+
+def ip_sets(n_keys, scales, masks=None, mask_strides=None) -> IpSets:
+    """the per-set table of attention_fwd_ipn.  The struct has room for four sets: of more, the first four are written and
+    n_sets carries the real count, which the library refuses"""
+    n_keys, scales = list(n_keys), list(scales)
+    masks = [None] * len(n_keys) if masks is None else list(masks)
+    if not (len(n_keys) == len(scales) == len(masks)):
+        raise PeaError(f"ip_sets: {len(n_keys)} key counts, {len(scales)} scales, {len(masks)} masks")
+    st = IpSets()
+    st.n_sets = len(n_keys)
+    for j, (n, w, m) in enumerate(list(zip(n_keys, scales, masks))[:4]):
+        st.n_keys[j], st.weight[j] = int(n), float(w)
+        if m is not None:
+            assert m.dtype == torch.float32 and m.dim() == 2 and m.stride(1) == 1, "mask: fp32 [1|B, Sq]"
+            st.mask[j] = m.data_ptr()
+            st.mask_stride[j] = (0 if m.shape[0] == 1 else m.stride(0)) if mask_strides is None else int(mask_strides[j])
+    return st
+
+
+def attention_fwd_ipn(q, k, v, k2, v2, heads, n_keys, scales, masks=None, scale=None, q_prescaled=False, kv_len=None,
+                      want_lse=False, causal=False, mask_strides=None):
+    """Several image prompts in one launch (pea_op_attention_fwd_ipn):
+    softmax(scale q k^T) v + sum_j scales[j] * masks[j][b, q] * softmax(scale q k2_j^T) v2_j, head_dim 64, one softmax per set.
+    q [B,Sq,H*64], k/v [B,Skv<=128,H*64]; k2/v2 [B,sum(n_keys)<=32,>=H*64] bf16 hold the 1..4 sets back to back, set j in rows
+    sum(n_keys[:j]) .. + n_keys[j].  masks: None, or per set None / fp32 [1,Sq] (shared by the batch) / [B,Sq], any finite
+    values.  kv_len (int32 [B]) masks text keys only; the lse is the text softmax's.  -> o, or (o, lse [B,H,Sq]) with want_lse.
+    causal=True and mask_strides (the batch stride handed over instead of the tensor's) exist to be refused."""
+    B, Sq, C = q.shape
+    scale = scale if scale is not None else (C // heads) ** -0.5
+    sets = ip_sets(n_keys, scales, masks, mask_strides)
+    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
+    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    check(lib().pea_op_attention_fwd_ipn(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(k2), k2.stride(1),
+                                         ptr(v2), v2.stride(1), ptr(o), C, ptr(lse), B, heads, Sq, k.shape[1], ctypes.byref(sets),
+                                         scale, int(q_prescaled), int(causal), ptr(kv_len), stream_ptr()))
     return (o, lse) if want_lse else o
 
 

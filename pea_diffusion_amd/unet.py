@@ -245,58 +245,154 @@ class HipUNet(HipTape):
             want += f" or latents [lb, {C}, {self.H}, {self.W}] with lb dividing {self.B}"
         raise PeaError(f"HipUNet built for {want}, got {shp}")
 
-    # ---------------------------------------------------------------- image prompt (IP-Adapter)
-    _ip = None             # the loaded ip_adapter.IPAdapter
+    # ---------------------------------------------------------------- image prompts (IP-Adapter)
+    _ip = None             # the loaded ip_adapter.IPAdapter / IPAdapterPlus, or the list of them (the list form)
+    _ips = ()              # ... always as a sequence, one entry per set of the context
     _ip_tokens = None      # the tokens last handed to the context (kept alive while the cast may still be queued)
 
     def load_ip_adapter(self, adapter_or_sd):
         """Give every cross-attention layer the `to_k_ip` / `to_v_ip` projections of an IP-Adapter (an `ip_adapter.IPAdapter` or
-        `IPAdapterPlus`, or the state dict or file path of a base adapter).  The UNet's own weights -- `weight_table()`, `load_state_dict` -- do not change, and neither
-        does any launch until `set_ip_tokens`.  Returns the IPAdapter (its `.tokens()` is the image projection)."""
+        `IPAdapterPlus`, or the state dict or file path of a base adapter), or of up to four of them: a list, one entry per
+        adapter, base and plus files mixed as needed, with at most 32 image tokens together (4 + 16, 16 + 16, 4 + 4 + 16).  The
+        UNet's own weights -- `weight_table()`, `load_state_dict` -- do not change, and neither does any launch until
+        `set_ip_tokens`.  Returns the adapter (its `.tokens()` is the image projection), or the list of them."""
         from .ip_adapter import IPAdapter, _LayerMap
-        ad = adapter_or_sd if isinstance(adapter_or_sd, _LayerMap) else IPAdapter(adapter_or_sd, self.cfg)
-        if ad.cfg.cross_attention_dim != self.cfg.cross_attention_dim:
-            raise PeaError(f"load_ip_adapter: adapter built for cross_attention_dim {ad.cfg.cross_attention_dim}, UNet has "
-                           f"{self.cfg.cross_attention_dim}")
-        check(lib().pea_unet_ip_create(self._h, ad.n_tokens))
+        many = isinstance(adapter_or_sd, (list, tuple))
+        ads = [a if isinstance(a, _LayerMap) else IPAdapter(a, self.cfg) for a in (adapter_or_sd if many else [adapter_or_sd])]
+        for ad in ads:
+            if ad.cfg.cross_attention_dim != self.cfg.cross_attention_dim:
+                raise PeaError(f"load_ip_adapter: adapter built for cross_attention_dim {ad.cfg.cross_attention_dim}, UNet has "
+                               f"{self.cfg.cross_attention_dim}")
+        if many:
+            n = (ctypes.c_int * max(len(ads), 1))(*[ad.n_tokens for ad in ads])
+            check(lib().pea_unet_ip_create_sets(self._h, len(ads), n))
+        else:
+            check(lib().pea_unet_ip_create(self._h, ads[0].n_tokens))
         try:
-            for k, t in ad.layers.items():
-                t = t.to(self.device, torch.float32).contiguous()
-                check(lib().pea_unet_ip_load_weight(self._h, k.encode(), ptr(t), t.numel(), stream_ptr()))
+            for j, ad in enumerate(ads):
+                for k, t in ad.layers.items():
+                    t = t.to(self.device, torch.float32).contiguous()
+                    if many:
+                        check(lib().pea_unet_ip_load_weight_set(self._h, j, k.encode(), ptr(t), t.numel(), stream_ptr()))
+                    else:
+                        check(lib().pea_unet_ip_load_weight(self._h, k.encode(), ptr(t), t.numel(), stream_ptr()))
             torch.cuda.current_stream().synchronize()      # staging tensors above are freed after this call
         except PeaError:
             self.unload_ip_adapter()
             raise
-        self._ip = ad
-        return ad
+        self._ips, self._ip_tokens = list(ads), [None] * len(ads)
+        self._ip = list(ads) if many else ads[0]
+        return self._ip
+
+    def _per_adapter(self, what, value):
+        """`value` as one entry per loaded adapter: a list is taken as it is, anything else is the entry of every adapter"""
+        if not self._ips:
+            raise PeaError(f"{what}: call load_ip_adapter first")
+        if isinstance(value, (list, tuple)):
+            if len(value) != len(self._ips):
+                raise PeaError(f"{what}: {len(value)} entries for {len(self._ips)} adapters")
+            return list(value)
+        return [value] * len(self._ips)
 
     def set_ip_tokens(self, tokens):
         """tokens [B, N, cross_dim] (`IPAdapter.tokens(image_embeds, do_cfg=...)`, or `IPAdapterPlus.tokens / encode`):
-        projected to every layer's image keys / values once; every call reads them until `clear_ip_tokens()`."""
-        if self._ip is None:
+        projected to every layer's image keys / values once; every call reads them until `clear_ip_tokens()`.  With several
+        adapters: a list with one such tensor per adapter; `None` leaves that adapter's tokens as they are."""
+        if not self._ips:
             raise PeaError("set_ip_tokens: call load_ip_adapter first")
-        want = (self.B, self._ip.n_tokens, self.cfg.cross_attention_dim)
-        if tuple(tokens.shape) != want:
-            raise PeaError(f"set_ip_tokens: tokens {tuple(tokens.shape)} != {want}")
-        t = tokens.detach().to(self.device, torch.float32).contiguous()
-        check(lib().pea_unet_ip_set_tokens(self._h, ptr(t), stream_ptr()))
-        self._ip_tokens = t
+        if not isinstance(tokens, (list, tuple)):
+            if len(self._ips) != 1:
+                raise PeaError(f"set_ip_tokens: one tensor for {len(self._ips)} adapters; pass a list with one entry per adapter")
+            tokens = [tokens]
+        for j, (ad, tok) in enumerate(zip(self._ips, self._per_adapter("set_ip_tokens", list(tokens)))):
+            if tok is None:
+                continue
+            want = (self.B, ad.n_tokens, self.cfg.cross_attention_dim)
+            if tuple(tok.shape) != want:
+                raise PeaError(f"set_ip_tokens: tokens {tuple(tok.shape)} != {want}" + (f" (adapter {j})" if len(self._ips) > 1 else ""))
+            t = tok.detach().to(self.device, torch.float32).contiguous()
+            if len(self._ips) == 1:
+                check(lib().pea_unet_ip_set_tokens(self._h, ptr(t), stream_ptr()))
+            else:
+                check(lib().pea_unet_ip_set_tokens_set(self._h, j, ptr(t), stream_ptr()))
+            self._ip_tokens[j] = t
 
-    def set_ip_adapter_scale(self, scale: float):
-        """the weight of the image branch (default 1; 0 runs the plain attention)"""
-        check(lib().pea_unet_ip_set_scale(self._h, float(scale)))
+    def set_ip_adapter_scale(self, scale):
+        """the weight of the image branch (default 1; 0 runs the plain attention).  A number, or a dict of per-block scales
+        (`ip_adapter.resolve_layer_scales`: keys `down` / `up` / `mid`, `up_blocks.0`, `up_blocks.0.attentions.1`, ..., `default`;
+        layers a dict does not name get 0), or a list with one such entry per adapter.  One entry for several adapters goes to
+        each of them."""
+        from .ip_adapter import resolve_layer_scales
+        for j, sc in enumerate(self._per_adapter("set_ip_adapter_scale", scale)):
+            if isinstance(sc, dict):
+                vec = resolve_layer_scales(self.cfg, sc)
+                arr = (ctypes.c_float * len(vec))(*vec)
+                check(lib().pea_unet_ip_set_layer_scales(self._h, j, arr, len(vec)))
+                check(lib().pea_unet_ip_set_scale_set(self._h, j, 1.0))
+            else:
+                check(lib().pea_unet_ip_set_layer_scales(self._h, j, None, 0))
+                check(lib().pea_unet_ip_set_scale_set(self._h, j, float(sc)))
 
-    def clear_ip_tokens(self):
-        """back to plain cross-attention launches; the adapter's weights stay loaded"""
-        check(lib().pea_unet_ip_clear(self._h))
-        self._ip_tokens = None
+    def ip_query_counts(self):
+        """the distinct query counts of this context's cross-attention layers (host only), e.g. [4096, 1024] for SDXL at 1024^2"""
+        n = ctypes.c_int()
+        check(lib().pea_unet_ip_query_counts(self._h, None, 0, ctypes.byref(n)))
+        out = (ctypes.c_int * max(n.value, 1))()
+        check(lib().pea_unet_ip_query_counts(self._h, out, n.value, ctypes.byref(n)))
+        return list(out[:n.value])
 
-    def unload_ip_adapter(self):
+    def _grid_of(self, count: int):
+        """(h, w) of the layers with `count` queries: the latent grid halved (n -> ceil(n / 2), a stride-2 convolution)"""
+        h, w = self.H, self.W
+        while h * w > count and (h > 1 or w > 1):
+            h, w = (h + 1) // 2, (w + 1) // 2
+        if h * w != count:
+            raise PeaError(f"no level of a {self.H} x {self.W} latent has {count} positions")
+        return h, w
+
+    def set_ip_adapter_masks(self, masks):
+        """Confine adapters to regions of the picture: a list with, per adapter, `None` (everywhere) or a mask `[h, w]` /
+        `[1|B, h, w]` at any resolution, 1 inside the region.  Every cross-attention layer multiplies that adapter's output by the
+        mask reduced to its own grid with `ip_adapter.downsample_mask` (bicubic, the values are used as they come out)."""
+        from .ip_adapter import downsample_mask
+        counts = None
+        for j, m in enumerate(self._per_adapter("set_ip_adapter_masks", list(masks) if isinstance(masks, (list, tuple)) else masks)):
+            if m is None:
+                check(lib().pea_unet_ip_set_mask(self._h, j, 0, None, 0, stream_ptr()))
+                continue
+            m = torch.as_tensor(m)
+            m = m[None] if m.dim() == 2 else m
+            if m.dim() != 3 or m.shape[0] not in (1, self.B):
+                raise PeaError(f"set_ip_adapter_masks: mask {tuple(m.shape)} of adapter {j}, expected [h, w] or [1|{self.B}, h, w]")
+            counts = self.ip_query_counts() if counts is None else counts
+            for c in counts:
+                d = downsample_mask(m.to(self.device), *self._grid_of(c))
+                check(lib().pea_unet_ip_set_mask(self._h, j, c, ptr(d), d.shape[0], stream_ptr()))
+            torch.cuda.current_stream().synchronize()      # the library copies on the stream; `d` is freed after this call
+
+    def clear_ip_tokens(self, index=None):
+        """back to plain cross-attention launches (index: for that adapter alone); the adapters' weights stay loaded"""
+        if index is None:
+            check(lib().pea_unet_ip_clear(self._h))
+            self._ip_tokens = [None] * len(self._ips)
+        else:
+            check(lib().pea_unet_ip_clear_set(self._h, int(index)))
+            self._ip_tokens[index] = None
+
+    def unload_ip_adapter(self, index=None):
+        """drop every adapter, or (index) that one: the others are loaded again into a new state, WITHOUT their tokens, scales
+        and masks -- set them again"""
+        rest = [] if index is None else [ad for j, ad in enumerate(self._ips) if j != int(index)]
+        if index is not None and not 0 <= int(index) < len(self._ips):
+            raise PeaError(f"unload_ip_adapter: adapter {index} of {len(self._ips)}")
         check(lib().pea_unet_ip_destroy(self._h))
-        self._ip = self._ip_tokens = None
+        self._ip, self._ips, self._ip_tokens = None, (), None
+        if rest:
+            self.load_ip_adapter(rest)
 
     def ip_kv(self):
-        """parity instrumentation: the image K|V of every layer, fp32 [B * N, cols] (columns: pea_unet_stacked_layout(which=0))"""
+        """parity instrumentation: the packed image K|V of every layer, fp32 [B * N, cols] with N the image tokens of all adapters
+        together, adapter j in rows off_j .. off_j + N_j of every sample (columns: pea_unet_stacked_layout(which=0))"""
         rows, cols = ctypes.c_longlong(), ctypes.c_int()
         check(lib().pea_unet_ip_export_kv(self._h, None, ctypes.byref(rows), ctypes.byref(cols), None))
         out = torch.empty(rows.value, cols.value, device=self.device, dtype=torch.float32)
