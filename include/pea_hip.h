@@ -155,6 +155,15 @@ int pea_op_attention_fwd_prescaled(const void* Q, int ldq, const void* K, int ld
 int pea_op_attention_fwd_masked(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
                                 float* lse, int B, int H, int Sq, int Skv, float scale, int causal, const int* kv_len,
                                 void* stream);
+/* Everything launch_attention_fwd takes at head_dim 64 (what the text-encoder and merged-pass tapes ask of it), forward only:
+ * q_prescaled as for pea_op_attention_fwd_prescaled, causal and kv_len as for pea_op_attention_fwd_masked (kv_len values in
+ * 1 .. Skv), and `bias`: NULL, or an additive score bias (T5 relative positions) as the kernel reads it -- device fp32
+ * [H][Sq][pitch] with pitch = 64 * ceil(Skv / 64), shared by the batch, 16-byte aligned, in the log2 domain (the natural-log
+ * bias times log2(e)), added to the scaled score.  Columns Skv .. pitch of a row are read but never used: they must be
+ * addressable, their values do not matter.  lse (may be NULL) fp32 [B][H][Sq], natural log, over the keys a row keeps. */
+int pea_op_attention_fwd_text(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
+                              float* lse, int B, int H, int Sq, int Skv, float scale, int q_prescaled, int causal,
+                              const int* kv_len, const float* bias, void* stream);
 /* Decoupled cross-attention of an image prompt (IP-Adapter), forward only, head_dim 64:
  *   O = softmax(scale Q K^T) V + ip_scale * softmax(scale Q K2^T) V2
  * two separate softmaxes over the same Q, in ONE launch that writes O once.  1 <= Skv <= 128 text keys, 1 <= Skv2 <= 32 image
@@ -213,6 +222,17 @@ int pea_op_attention_bwd_prescaled(const void* Q, int ldq, const void* K, int ld
                                    int ldo, const void* dO, int lddo, const float* lse, float* delta, void* dQ, int lddq,
                                    void* dK, int lddk, void* dV, int lddv, int B, int H, int Sq, int Skv, float scale,
                                    int accum_dq, int accum_dkv, int nd, void* scratch, void* stream);
+
+/* pea_op_attention_bwd with the Q convention as an argument and per-sample key counts: kv_len = device int[B] or NULL, the
+ * counts the forward ran with (O and lse are that forward's).  Keys >= kv_len[b] of sample b are padding: they take no part
+ * in dQ, and their rows of dK / dV are written as zeros (left as they are by the accumulating form).  Values lie in
+ * 1 .. Skv; a count of 0 (a sample without any key) is outside the contract.  head_dim 64 only with kv_len (nd = 1;
+ * anything else is PEA_E_SHAPE before any launch).  There is no causal or biased backward: the text encoders are frozen. */
+int pea_op_attention_bwd_masked(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O,
+                                int ldo, const void* dO, int lddo, const float* lse, float* delta, void* dQ, int lddq,
+                                void* dK, int lddk, void* dV, int lddv, int B, int H, int Sq, int Skv, float scale,
+                                int accum_dq, int accum_dkv, int nd, void* scratch, int q_prescaled, const int* kv_len,
+                                void* stream);
 
 int pea_op_geglu_fwd(const void* hg, void* y, long long rows, int inner, void* stream);
 int pea_op_geglu_bwd(const void* hg, const void* dy, void* dhg, long long rows, int inner, void* stream);

@@ -37,7 +37,8 @@ static int attention_fwd_impl(const void* Q, int ldq, const void* K, int ldk, co
 static int attention_bwd_impl(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O,
                               int ldo, const void* dO, int lddo, const float* lse, float* delta, void* dQ, int lddq,
                               void* dK, int lddk, void* dV, int lddv, int B, int H, int Sq, int Skv, float scale,
-                              int accum_dq, int accum_dkv, int nd, void* scratch, int q_prescaled, void* stream) {
+                              int accum_dq, int accum_dkv, int nd, void* scratch, int q_prescaled, const int* kv_len,
+                              void* stream) {
   AttnP p;
   memset(&p, 0, sizeof(p));
   p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
@@ -45,7 +46,7 @@ static int attention_bwd_impl(const void* Q, int ldq, const void* K, int ldk, co
   p.dO = (const bf16*)dO; p.lddo = lddo; p.delta = delta;
   p.dQ = (bf16*)dQ; p.lddq = lddq; p.dK = (bf16*)dK; p.lddk = lddk; p.dV = (bf16*)dV; p.lddv = lddv;
   p.accum_dq = accum_dq; p.accum_dkv = accum_dkv; p.dkv_part = (float*)scratch; p.nd = nd;
-  p.q_prescaled = q_prescaled;
+  p.q_prescaled = q_prescaled; p.kv_len = kv_len;
   return launch_attention_bwd(p, (hipStream_t)stream);
 }
 
@@ -260,6 +261,16 @@ int pea_op_attention_fwd_masked(const void* Q, int ldq, const void* K, int ldk, 
   p.causal = causal; p.kv_len = kv_len;
   return launch_attention_fwd(p, (hipStream_t)stream);
 }
+int pea_op_attention_fwd_text(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
+                              float* lse, int B, int H, int Sq, int Skv, float scale, int q_prescaled, int causal,
+                              const int* kv_len, const float* bias, void* stream) {
+  AttnP p;
+  memset(&p, 0, sizeof(p));
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
+  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = 1;
+  p.q_prescaled = q_prescaled; p.causal = causal; p.kv_len = kv_len; p.bias = bias;
+  return launch_attention_fwd(p, (hipStream_t)stream);
+}
 int pea_op_attention_fwd_ip(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                             const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                             float scale, float ip_scale, int q_prescaled, int causal, const int* kv_len, void* stream) {
@@ -310,14 +321,22 @@ int pea_op_attention_bwd(const void* Q, int ldq, const void* K, int ldk, const v
                          void* dK, int lddk, void* dV, int lddv, int B, int H, int Sq, int Skv, float scale,
                          int accum_dq, int accum_dkv, int nd, void* scratch, void* stream) {
   return attention_bwd_impl(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, delta, dQ, lddq, dK, lddk, dV, lddv, B, H, Sq, Skv,
-                            scale, accum_dq, accum_dkv, nd, scratch, 0, stream);
+                            scale, accum_dq, accum_dkv, nd, scratch, 0, nullptr, stream);
 }
 int pea_op_attention_bwd_prescaled(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O,
                                    int ldo, const void* dO, int lddo, const float* lse, float* delta, void* dQ, int lddq,
                                    void* dK, int lddk, void* dV, int lddv, int B, int H, int Sq, int Skv, float scale,
                                    int accum_dq, int accum_dkv, int nd, void* scratch, void* stream) {
   return attention_bwd_impl(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, delta, dQ, lddq, dK, lddk, dV, lddv, B, H, Sq, Skv,
-                            scale, accum_dq, accum_dkv, nd, scratch, 1, stream);
+                            scale, accum_dq, accum_dkv, nd, scratch, 1, nullptr, stream);
+}
+int pea_op_attention_bwd_masked(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O,
+                                int ldo, const void* dO, int lddo, const float* lse, float* delta, void* dQ, int lddq,
+                                void* dK, int lddk, void* dV, int lddv, int B, int H, int Sq, int Skv, float scale,
+                                int accum_dq, int accum_dkv, int nd, void* scratch, int q_prescaled, const int* kv_len,
+                                void* stream) {
+  return attention_bwd_impl(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, delta, dQ, lddq, dK, lddk, dV, lddv, B, H, Sq, Skv,
+                            scale, accum_dq, accum_dkv, nd, scratch, q_prescaled, kv_len, stream);
 }
 
 int pea_op_geglu_fwd(const void* hg, void* y, long long rows, int inner, void* stream) {

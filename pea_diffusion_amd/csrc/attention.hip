@@ -256,8 +256,14 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       qf[nd][s] = *(const bf16x8*)(Qb + (long long)qrow * p.ldq + nd * 64 + 16 * s + 8 * fh);
-      if (!p.q_prescaled) qf[nd][s] = scale_frag(qf[nd][s], c);
+      if (!p.q_prescaled && !TXT) qf[nd][s] = scale_frag(qf[nd][s], c);
     }
+  // TXT with a plain Q: the factor is applied to the fp32 scores (qs), not rounded into the Q fragment.  A causal row 0, or a
+  // sample with one valid key, has lse = that one logit, and the 2^-9 of a bf16 Q * scale * log2(e) on it is all of the error
+  // (measured 2.4e-3 .. 4.6e-3 on unit inputs, against 1e-6 this way); with many keys it averages out.  The C operand then
+  // carries -m_run / qs.  A prescaled Q has qs = 1: the same bits as before.
+  [[maybe_unused]] const float qs = (TXT && !p.q_prescaled) ? c : 1.f;
+  [[maybe_unused]] const float inv_qs = (TXT && !p.q_prescaled) ? 1.f / c : 1.f;
   float lse2 = 0.f, dlt = 0.f;
   if (MODE == 1) {
     const bf16* dOb = p.dO + (long long)b * p.Sq * p.lddo + head * 64 * ND;
@@ -404,6 +410,10 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
       int skv_b = p.Skv;
       if constexpr (TXT) skv_b = skv_all;
       if constexpr (TXT) {
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sacc[kb][r] *= qs;              // (K . Q^T - m_run / qs) qs: the log2 domain
         if (p.bias) {
           // additive score bias (T5 relative positions), given in the log2 domain with a row pitch of 64 * ceil(Skv / 64)
           const int pitch = ((p.Skv + 63) >> 6) << 6;
@@ -459,7 +469,7 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
           for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
         m_run += mrel;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) rowc[r] = -m_run;
+        for (int r = 0; r < 16; ++r) rowc[r] = TXT ? -m_run * inv_qs : -m_run;
       }
       float ls = 0.f;
 #pragma unroll
@@ -2728,6 +2738,9 @@ int launch_attention_bwd(const AttnP& p0, hipStream_t s) {
   p.nsplit = p.dkv_part ? attention_bwd_nsplit(p.B, p.H, p.Sq, p.Skv) : 1;
   int rc = attn_check(p);
   if (rc) return rc;
+  // no backward kernel knows a causal mask or a score bias (the text encoders are frozen): unmasked gradients would be wrong
+  SHAPECHK(!p.causal && !p.bias, "attention bwd: no backward with a causal mask or a score bias");
+  SHAPECHK(!p.kv_len || p.nd == 1, "attention bwd: key-length masks need head_dim 64 (nd=%d)", p.nd);
   SHAPECHK(p.lse && p.delta && p.dO && p.O, "attention bwd: lse/delta/dO/O required");
   SHAPECHK(p.Sq % 4 == 0, "attention bwd: Sq=%d must be a multiple of 4", p.Sq);
   const long long total = (long long)p.B * p.Sq * p.H * 8;

@@ -345,15 +345,40 @@ def attention_fwd_fewq(q, k, v, k2=None, v2=None, heads=1, scale=None, q_prescal
     return (o, lse) if want_lse else o
 
 
-def attention_fwd_masked(q, k, v, heads, causal=False, kv_len=None, scale=None):
-    """text-encoder attention: head_dim 64, optional causal mask and per-sample key counts (int32 [B])"""
+def attention_fwd_masked(q, k, v, heads, causal=False, kv_len=None, scale=None, want_lse=False):
+    """text-encoder attention: head_dim 64, optional causal mask and per-sample key counts (int32 [B])
+    -> o, or (o, lse [B,H,Sq]) with want_lse"""
     B, Sq, C = q.shape
     Skv = k.shape[1]
     scale = scale if scale is not None else (C // heads) ** -0.5
     o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
-    check(lib().pea_op_attention_fwd_masked(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, None,
+    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    check(lib().pea_op_attention_fwd_masked(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, ptr(lse),
                                             B, heads, Sq, Skv, scale, int(causal), ptr(kv_len), stream_ptr()))
-    return o
+    return (o, lse) if want_lse else o
+
+
+def attention_bias_pitch(Skv):
+    """row pitch (elements) of the score bias of attention_fwd_text: whole 64-key tiles"""
+    return (Skv + 63) // 64 * 64
+
+
+def attention_fwd_text(q, k, v, heads, scale=None, q_prescaled=False, causal=False, kv_len=None, bias=None, want_lse=True):
+    """pea_op_attention_fwd_text: everything the forward launcher takes at head_dim 64.  kv_len int32 [B] (values 1..Skv);
+    bias fp32 [H, Sq, attention_bias_pitch(Skv)], contiguous, in the log2 domain (natural-log bias x log2 e), shared by the
+    batch -- the columns past Skv are read but never used.  -> (o, lse [B,H,Sq]), or o alone without want_lse."""
+    B, Sq, C = q.shape
+    Skv = k.shape[1]
+    scale = scale if scale is not None else (C // heads) ** -0.5
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (heads, Sq, attention_bias_pitch(Skv))
+                             or not bias.is_contiguous()):
+        raise PeaError(f"attention_fwd_text: bias must be contiguous fp32 [{heads}, {Sq}, {attention_bias_pitch(Skv)}]")
+    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
+    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    check(lib().pea_op_attention_fwd_text(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, ptr(lse),
+                                          B, heads, Sq, Skv, scale, int(q_prescaled), int(causal), ptr(kv_len), ptr(bias),
+                                          stream_ptr()))
+    return (o, lse) if want_lse else o
 
 
 def attention_bwd(q, k, v, o, do, lse, heads, scale=None, q_prescaled=False):
@@ -370,6 +395,24 @@ def attention_bwd(q, k, v, o, do, lse, heads, scale=None, q_prescaled=False):
     check(fn(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, ptr(do),
                                      C, ptr(lse), ptr(delta), ptr(dq), C, ptr(dk), C, ptr(dv), C, B, heads, Sq, Skv,
                                      scale, 0, 0, nd, ptr(scratch), stream_ptr()))
+    return dq, dk, dv
+
+
+def attention_bwd_masked(q, k, v, o, do, lse, heads, scale=None, q_prescaled=False, kv_len=None, use_scratch=True):
+    """pea_op_attention_bwd_masked -> (dq, dk, dv): attention_bwd with per-sample key counts (int32 [B], values 1..Skv, those
+    of the forward that made o and lse); rows >= kv_len[b] of dk / dv come back as zeros.  use_scratch=False: without the
+    query-split scratch."""
+    B, Sq, C = q.shape
+    Skv = k.shape[1]
+    nd = C // heads // 64
+    scale = scale if scale is not None else (C // heads) ** -0.5
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty(2, B, heads, Sq, device=q.device, dtype=torch.float32)
+    nb = lib().pea_op_attention_bwd_scratch_bytes(B, heads, Sq, Skv, nd) if use_scratch else 0
+    scratch = torch.empty(nb, device=q.device, dtype=torch.uint8) if nb else None
+    check(lib().pea_op_attention_bwd_masked(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, ptr(do),
+                                            C, ptr(lse), ptr(delta), ptr(dq), C, ptr(dk), C, ptr(dv), C, B, heads, Sq, Skv,
+                                            scale, 0, 0, nd, ptr(scratch), int(q_prescaled), ptr(kv_len), stream_ptr()))
     return dq, dk, dv
 
 

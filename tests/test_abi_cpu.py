@@ -44,6 +44,36 @@ def test_shape_errors_are_reported_without_gpu():
     assert rc == -3 and b"K=10" in L.pea_last_error()
 
 
+def test_attention_mask_refusals_without_gpu():
+    """The attention launchers refuse what no kernel implements before any launch (null operands, no device): a key-length mask
+    at a head width other than 64 in the backward, like the forward's own refusal.  A causal mask or a score bias in the
+    backward is refused by launch_attention_bwd as well, but no exported entry point can ask for one (pea_op_attention_bwd_masked
+    has no such argument), and pea_op_attention_fwd_masked / _text fix nd = 1, so those two refusals are not reachable from
+    here; what is reachable is that the masked entries get as far as the launcher's checks and answer PEA_E_SHAPE."""
+    import ctypes as C
+    L = _lib.lib()
+    kv = C.cast((C.c_int * 2)(1, 1), C.c_void_p)                     # never read: the call is refused on the host
+    for nd in (2, 3):
+        rc = L.pea_op_attention_bwd_masked(None, 64 * nd, None, 64 * nd, None, 64 * nd, None, 64 * nd, None, 64 * nd, None, None,
+                                           None, 64 * nd, None, 64 * nd, None, 64 * nd, 2, 1, 8, 8, 0.125, 0, 0, nd, None, 0, kv, None)
+        assert rc == -3 and b"key-length masks need head_dim 64" in L.pea_last_error(), L.pea_last_error()
+    # without kv_len the same call gets past that check (and is stopped by the next one: no operands)
+    rc = L.pea_op_attention_bwd_masked(None, 128, None, 128, None, 128, None, 128, None, 128, None, None,
+                                       None, 128, None, 128, None, 128, 2, 1, 8, 8, 0.125, 0, 0, 2, None, 0, None, None)
+    assert rc == -3 and b"lse/delta/dO/O required" in L.pea_last_error(), L.pea_last_error()
+    # nd = 1 with kv_len: not refused for the mask
+    rc = L.pea_op_attention_bwd_masked(None, 64, None, 64, None, 64, None, 64, None, 64, None, None,
+                                       None, 64, None, 64, None, 64, 2, 1, 8, 8, 0.125, 0, 0, 1, None, 0, kv, None)
+    assert rc == -3 and b"lse/delta/dO/O required" in L.pea_last_error(), L.pea_last_error()
+    # the forward entries: an empty problem is refused by the launcher's first check, masks or not
+    rc = L.pea_op_attention_fwd_masked(None, 64, None, 64, None, 64, None, 64, None, 2, 1, 0, 8, 0.125, 1, kv, None)
+    assert rc == -3 and b"empty problem" in L.pea_last_error()
+    rc = L.pea_op_attention_fwd_text(None, 64, None, 64, None, 64, None, 64, None, 2, 1, 8, 0, 0.125, 0, 1, kv, None, None)
+    assert rc == -3 and b"empty problem" in L.pea_last_error()
+    rc = L.pea_op_attention_fwd_text(None, 60, None, 64, None, 64, None, 64, None, 2, 1, 8, 8, 0.125, 0, 1, kv, None, None)
+    assert rc == -3 and b"multiples of 8" in L.pea_last_error()
+
+
 def test_unet_plan_runs_without_a_device():
     """pea_unet_plan: the host-side tape builder + memory planner needs no GPU (known answer: SDXL parameter total)"""
     import ctypes as C

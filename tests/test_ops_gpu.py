@@ -710,10 +710,12 @@ def test_attention_text_masks(ops, B, H, S, causal, padded):
         mask[b, :, :, int(lens[b]):] = float("-inf")
     sp = lambda t: t.float().view(B, S, H, 64).transpose(1, 2)
     ref = F.scaled_dot_product_attention(sp(q), sp(k), sp(v), attn_mask=mask).transpose(1, 2).reshape(B, S, C)
-    o = ops.attention_fwd_masked(q.cuda(), k.cuda(), v.cuda(), H, causal=causal,
-                                 kv_len=lens.to(torch.int32).cuda() if padded else None)
+    lref = torch.logsumexp(sp(q) @ sp(k).transpose(-1, -2) * 0.125 + mask, -1)
+    o, lse = ops.attention_fwd_masked(q.cuda(), k.cuda(), v.cuda(), H, causal=causal,
+                                      kv_len=lens.to(torch.int32).cuda() if padded else None, want_lse=True)
     # with causal + padding a query row can lie beyond the valid keys only through padding; every row keeps key 0
     close_bf16(f"attn text B{B} H{H} S{S} causal={causal} padded={padded}", o, ref, ulps=2.0)   # as the other attention outputs
+    close_f32(f"attn text B{B} H{H} S{S} causal={causal} padded={padded} lse", lse, lref, rtol=1e-3, atol=2e-3)
 
 
 def test_gemm_tile_rules_on_a_smaller_device(ops):
