@@ -103,6 +103,20 @@ int pea_op_pack_conv_subpixel(const float* w, void* out, int Co, int Ci, int dgr
 int pea_op_concat2(const void* a, int C1, const void* b, int C2, void* y, long long rows, int aH, int aW, void* stream);
 int pea_op_split2(const void* dy, int C1, int C2, void* da, int accum_a, void* db, int accum_b, long long rows, int aH,
                   int aW, void* stream);
+/* FreeU (diffusers 0.23 `apply_freeu`, `fourier_filter` with threshold 1) on the two operands of that concat, in two launches.
+ * pea_op_freeu_coef: skip bf16 [B][H][W][C2] -> coef fp32 [B][7][C2], per channel map the sums S00 = sum v, C10 / S10 = sum v cos /
+ * sin(2 pi y / H), C01 / S01 = sum v cos / sin(2 pi x / W), C11 / S11 = sum v cos / sin(2 pi y / H + 2 pi x / W), in that order.
+ * Where one workgroup per (sample, 128 channels) would leave the chip empty the rows are split into slabs whose partial sums go
+ * to `scratch` (pea_op_freeu_scratch_bytes device bytes; 0 = one slab, scratch may be NULL) and are added in slab order: no
+ * atomics, the same bits on every run.
+ * pea_op_concat2_freeu: y [B*H*W][C1 + C2] = ( bscale * a[:, :C1/2] | a[:, C1/2:] | skip filtered with scale s ), the filter
+ * evaluated in fp32 from coef.  s == 1 and bscale == 1 are plain copies of their columns (s == 1 never reads coef; both: the bits
+ * of pea_op_concat2).  aH, aW != 0: `a` is stored depth-to-space (aH == H, aW == W).  a may be b.
+ * C1 / 2, C1 and C2 must be multiples of 8, H and W at least 2, s and bscale finite and positive (PEA_E_SHAPE otherwise). */
+long long pea_op_freeu_scratch_bytes(int B, int H, int W, int C2);
+int pea_op_freeu_coef(const void* skip, int B, int H, int W, int C2, float* coef, void* scratch, void* stream);
+int pea_op_concat2_freeu(const void* a, int C1, const void* b, int C2, const float* coef, void* y, int B, int H, int W, float s,
+                         float bscale, int aH, int aW, void* stream);
 int pea_op_upconv_subpixel(const void* x, const void* w, void* y, int B, int Hs, int Ws, int Cin, int Cout,
                            const float* bias, void* stream);
 int pea_op_upconv_subpixel_dgrad(const void* dy, const void* wt, void* dx, int B, int Hs, int Ws, int Cin, int Cout,
@@ -407,6 +421,16 @@ int pea_unet_set_residuals(void* unet, int n, const void* const* ptrs, int dtype
 int pea_unet_set_inpaint_cond(void* unet, const float* mask, const float* masked_latents, int cond_batch, int latent_batch,
                               void* stream);
 int pea_unet_clear_inpaint_cond(void* unet);
+/* FreeU (diffusers 0.23 `pipe.enable_freeu(s1, s2, b1, b2)`; training-free, no weights).  In front of every skip concatenation of
+ * up block 0 (factors s1, b1) and up block 1 (s2, b2) the first half of the hidden state's channels is multiplied by b and the
+ * skip tensor goes through `fourier_filter(skip, threshold=1, scale=s)`: pea_op_freeu_coef + pea_op_concat2_freeu instead of the
+ * plain concat, everything else unchanged.  ControlNet residuals are in the skips by then, as in diffusers.  The feature taps
+ * u0 / u1 keep their unscaled values.  A runtime switch of a UNet context (graph 0): PEA_E_STATE on a PEA_UNET_GRAD context
+ * (an inference feature, no backward through it), PEA_E_INVALID for a factor that is not finite and positive, PEA_E_SHAPE where
+ * up block 0 or 1 works on a map with H < 2 or W < 2.  The coefficient buffer is allocated by the first call and survives
+ * pea_unet_release_activations.  pea_unet_clear_freeu: the plain concat launches again, bit for bit. */
+int pea_unet_set_freeu(void* unet, float s1, float s2, float b1, float b2, void* stream);
+int pea_unet_clear_freeu(void* unet);
 /* Image prompt (IP-Adapter, `ip-adapter_sdxl_vit-h` and its kin): every cross-attention layer gets a second, independent
  * key / value projection `to_k_ip` / `to_v_ip` over n_tokens image tokens (1..32) and runs the decoupled attention of
  * pea_op_attention_fwd_ip.  The UNet's own weights do not change.

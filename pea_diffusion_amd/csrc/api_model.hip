@@ -450,6 +450,15 @@ int pea_unet_clear_inpaint_cond(void* h) {
   u->inp_cond_b = u->inp_lat_b = 0;
   return PEA_OK;
 }
+int pea_unet_set_freeu(void* h, float s1, float s2, float b1, float b2, void* stream) {
+  NOTNULL(h, "pea_unet_set_freeu");
+  return ((Tape*)h)->set_freeu(s1, s2, b1, b2, (hipStream_t)stream);
+}
+int pea_unet_clear_freeu(void* h) {
+  NOTNULL(h, "pea_unet_clear_freeu");
+  ((Tape*)h)->fu_on = false;
+  return PEA_OK;
+}
 // ------------------------------------------------------------------------------ image prompt (IP-Adapter)
 // what a graph must be to take one; on success *kv_op is the stacked text K|V projection
 static int ip_check(const Tape& u, int n_tokens, const Op** kv_op) {

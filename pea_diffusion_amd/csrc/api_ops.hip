@@ -184,6 +184,15 @@ int pea_op_split2(const void* dy, int C1, int C2, void* da, int accum_a, void* d
                   int aW, void* stream) {
   return launch_split2((const bf16*)dy, C1, C2, (bf16*)da, accum_a, (bf16*)db, accum_b, rows, (hipStream_t)stream, aH, aW);
 }
+// FreeU on the operands of an up-path concat (elementwise.hip: freeu_coef_kernel, concat2_freeu_kernel)
+long long pea_op_freeu_scratch_bytes(int B, int H, int W, int C2) { return (long long)freeu_scratch_bytes(B, H, W, C2); }
+int pea_op_freeu_coef(const void* skip, int B, int H, int W, int C2, float* coef, void* scratch, void* stream) {
+  return launch_freeu_coef((const bf16*)skip, B, H, W, C2, coef, (float*)scratch, (hipStream_t)stream);
+}
+int pea_op_concat2_freeu(const void* a, int C1, const void* b, int C2, const float* coef, void* y, int B, int H, int W, float s,
+                         float bscale, int aH, int aW, void* stream) {
+  return launch_concat2_freeu((const bf16*)a, C1, (const bf16*)b, C2, coef, (bf16*)y, B, H, W, s, bscale, (hipStream_t)stream, aH, aW);
+}
 int pea_op_pack_conv_subpixel(const float* w, void* out, int Co, int Ci, int dgrad, void* stream) {
   return launch_pack_conv_subpix(w, (bf16*)out, Co, Ci, dgrad, (hipStream_t)stream);
 }

@@ -6,6 +6,8 @@
 // (train_sdxl_zh.py:397,415); add_noise train_sdxl_zh.py:322; `torch.where` CFG dropout
 // train_sdxl_zh.py:395,413; `torch.mean(x,1)` train_sdxl_zh.py:66; FusedAdam
 // utils/model_utils.py:64-67.
+#include <algorithm>
+
 #include "pea_kernels.h"
 
 #define EW_GRID(n8) ((int)(cdivl((n8), 256) < 8192 ? cdivl((n8), 256) : 8192))
@@ -162,6 +164,209 @@ int launch_split2(const bf16* dy, int C1, int C2, bf16* da, int accum_a, bf16* d
   PROF_BEGIN(6, 0.0, 4.0 * rows * (C1 + C2), s);
   hipLaunchKernelGGL(split2_kernel, dim3(EW_GRID(rows * ((C1 + C2) / 8))), dim3(256), 0, s, dy, C1, C2, da, accum_a,
                      db, accum_b, rows, aH, aW);
+  PROF_END(s);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
+// ---- FreeU (diffusers 0.23 `apply_freeu` / `fourier_filter`, threshold 1) on the two operands of an up-path concat
+// The filter multiplies the four frequencies (ky, kx) in {-1, 0} x {-1, 0} of a channel map by s and takes the real part.  With
+// ty = 2 pi y / H, tx = 2 pi x / W and the seven sums over one map
+//   S00 = sum v,  C10 / S10 = sum v cos / sin ty,  C01 / S01 = sum v cos / sin tx,  C11 / S11 = sum v cos / sin (ty + tx)
+// that is  y = v + (s - 1) / (H W) * (S00 + C10 cos ty + S10 sin ty + C01 cos tx + S01 sin tx + C11 cos(ty + tx) + S11 sin(ty + tx)).
+// freeu_coef_kernel computes the sums (fp32 [B][7][C2], order S00 C10 S10 C01 S01 C11 S11), concat2_freeu_kernel applies them
+// while it copies.  Both take every phase from freeu_phase, so the two agree on each cos / sin bit for bit.
+__device__ __forceinline__ void freeu_phase(int k, int n, float* c, float* s) {
+  sincospif(2.f * (float)k / (float)n, s, c);          // argument in half turns: no 2 pi k / n is ever rounded or range-reduced
+}
+#define FU_CG 16             // lanes along channels, 8 channels (16 bytes) each: a workgroup covers 128 channels
+#define FU_PL 16             // lanes along the pixels of a row
+// One workgroup per (128 channels, slab of rows_per_slab rows, sample).  A lane sums its pixels of one row into the three row sums
+// (1, cos tx, sin tx) -- three FMAs per element -- and folds each finished row into the seven sums with (1, cos ty, sin ty).  The
+// pixel lanes are then added in lane order through LDS.  out = part [B][nslab][7][C2] (nslab == 1: the coefficients themselves).
+__global__ __launch_bounds__(256) void freeu_coef_kernel(const bf16* __restrict__ x, float* __restrict__ out, int H, int W, int C2,
+                                                         int rows_per_slab, int nslab) {
+  extern __shared__ float fu_sm[];
+  float* tcy = fu_sm;                  // [rows_per_slab] cos / sin ty of this slab's rows
+  float* tsy = tcy + rows_per_slab;
+  float* tcx = tsy + rows_per_slab;    // [W]
+  float* tsx = tcx + W;
+  float* red = tsx + W;                // [FU_PL][FU_CG * 8]
+  const int tid = threadIdx.x, cg = tid & (FU_CG - 1), pl = tid / FU_CG;
+  const int slab = blockIdx.y, b = blockIdx.z;
+  const int y0 = slab * rows_per_slab, y1 = min(H, y0 + rows_per_slab);
+  for (int i = tid; i < y1 - y0; i += 256) freeu_phase(y0 + i, H, tcy + i, tsy + i);
+  for (int i = tid; i < W; i += 256) freeu_phase(i, W, tcx + i, tsx + i);
+  __syncthreads();
+  const int chunk = blockIdx.x * FU_CG + cg;
+  const bool live = chunk < C2 / 8;
+  float acc[7][8];
+#pragma unroll
+  for (int k = 0; k < 7; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
+  if (live)
+    for (int yy = y0; yy < y1; ++yy) {
+      float r0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      const bf16* row = x + ((long long)b * H + yy) * W * C2 + chunk * 8;
+      for (int xx = pl; xx < W; xx += FU_PL) {
+        const bf16x8 v = *(const bf16x8*)(row + (long long)xx * C2);
+        const float cx = tcx[xx], sx = tsx[xx];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float f = (float)v[j];
+          r0[j] += f;
+          rc[j] = fmaf(f, cx, rc[j]);
+          rs[j] = fmaf(f, sx, rs[j]);
+        }
+      }
+      const float cy = tcy[yy - y0], sy = tsy[yy - y0];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        acc[0][j] += r0[j];
+        acc[1][j] = fmaf(cy, r0[j], acc[1][j]);
+        acc[2][j] = fmaf(sy, r0[j], acc[2][j]);
+        acc[3][j] += rc[j];
+        acc[4][j] += rs[j];
+        acc[5][j] = fmaf(-sy, rs[j], fmaf(cy, rc[j], acc[5][j]));      // cos(ty + tx) = cos ty cos tx - sin ty sin tx
+        acc[6][j] = fmaf(cy, rs[j], fmaf(sy, rc[j], acc[6][j]));       // sin(ty + tx) = sin ty cos tx + cos ty sin tx
+      }
+    }
+  const int col = blockIdx.x * FU_CG * 8 + tid;          // tid < 128: the channel this lane sums and writes
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[pl * (FU_CG * 8) + cg * 8 + j] = acc[k][j];
+    __syncthreads();
+    if (tid < FU_CG * 8 && col < C2) {
+      float t = 0.f;
+      for (int p = 0; p < FU_PL; ++p) t += red[p * (FU_CG * 8) + tid];
+      out[(((long long)b * nslab + slab) * 7 + k) * C2 + col] = t;
+    }
+  }
+}
+// coef [B][7][C2] = the slabs of part [B][nslab][7][C2] added in slab order
+__global__ void freeu_finalize_kernel(const float* __restrict__ part, float* __restrict__ coef, int nslab, int per, long long n4) {
+  EW_LOOP(i, n4) {                                        // per = 7 * C2 / 4 float4s per sample
+    const long long b = i / per;
+    const f32x4* src = (const f32x4*)part + b * nslab * per + (i - b * per);
+    f32x4 t = src[0];
+    for (int sl = 1; sl < nslab; ++sl) t += src[(long long)sl * per];
+    ((f32x4*)coef)[i] = t;
+  }
+}
+// The split of the H rows into slabs: one workgroup per compute unit of the 256 where the shape has that many, a slab of at least
+// 64 pixels (four per pixel lane), whole rows.  Production maps: 32 x 32 x 1280 at batch 2 -> 11 slabs of 3 rows (220 workgroups),
+// 64 x 64 x 320 at batch 1 -> 64 slabs of one row (192).
+static int freeu_rows_per_slab(int B, int H, int W, int C2) {
+  const int wg = B * cdiv(C2 / 8, FU_CG);
+  const int want = std::min(H, cdiv(256, wg));
+  return std::min(H, std::max(cdiv(H, want), cdiv(64, W)));
+}
+static int freeu_shapechk(int B, int H, int W, int C2) {
+  SHAPECHK(B >= 1 && C2 >= 8 && C2 % 8 == 0, "freeu: B=%d C2=%d (C2 %% 8)", B, C2);
+  SHAPECHK(H >= 2 && W >= 2, "freeu: a %d x %d map (the filter's 2 x 2 window needs H >= 2 and W >= 2)", H, W);
+  SHAPECHK(H <= 2048 && W <= 2048 && B <= 65535, "freeu: B=%d, map %d x %d (at most 65535 samples of 2048 x 2048)", B, H, W);
+  return PEA_OK;
+}
+size_t freeu_scratch_bytes(int B, int H, int W, int C2) {
+  if (freeu_shapechk(B, H, W, C2) != PEA_OK) return 0;
+  const int nslab = cdiv(H, freeu_rows_per_slab(B, H, W, C2));
+  return nslab > 1 ? sizeof(float) * (size_t)B * nslab * 7 * C2 : 0;
+}
+int launch_freeu_coef(const bf16* skip, int B, int H, int W, int C2, float* coef, float* scratch, hipStream_t s) {
+  if (int rc = freeu_shapechk(B, H, W, C2)) return rc;
+  const int rps = freeu_rows_per_slab(B, H, W, C2), nslab = cdiv(H, rps);
+  SHAPECHK(nslab == 1 || scratch != nullptr, "freeu: %d slabs need the scratch buffer of freeu_scratch_bytes", nslab);
+  const size_t lds = sizeof(float) * (2 * (size_t)rps + 2 * (size_t)W + FU_PL * FU_CG * 8);
+  PROF_BEGIN(6, 6.0 * B * H * W * C2, 2.0 * B * H * W * C2 + 4.0 * 7 * B * C2 * (nslab > 1 ? 2 * nslab + 1 : 1), s);
+  hipLaunchKernelGGL(freeu_coef_kernel, dim3(cdiv(C2 / 8, FU_CG), nslab, B), dim3(256), lds, s, skip, nslab > 1 ? scratch : coef,
+                     H, W, C2, rps, nslab);
+  if (nslab > 1) {
+    const long long n4 = (long long)B * 7 * C2 / 4;
+    hipLaunchKernelGGL(freeu_finalize_kernel, dim3(EW_GRID(n4)), dim3(256), 0, s, scratch, coef, nslab, 7 * C2 / 4, n4);
+  }
+  PROF_END(s);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+// concat2 with FreeU riding on the copy: y[r] = ( bscale * a[r][0 : C1/2] | a[r][C1/2 : C1] | filter(b)[r] ), g = (s - 1) / (H W).
+// One workgroup per (rows_per_wg pixels of one sample): a lane keeps its 8 channels' seven coefficients in registers over those
+// pixels.  bscale == 1 and g == 0 are the plain copies of their columns (no arithmetic: the output is concat2's bit for bit,
+// whatever coef holds).  a may be stored depth-to-space (aW != 0) and may be b.
+__global__ __launch_bounds__(256) void concat2_freeu_kernel(const bf16* a, int C1, const bf16* b, int C2, const float* __restrict__ coef,
+                                                            bf16* __restrict__ y, int H, int W, float g, float bscale, int rows_per_wg,
+                                                            int aH, int aW) {
+  __shared__ float ph[8][4];                             // (cos ty, sin ty, cos tx, sin tx) of this workgroup's pixels
+  const int HW = H * W, smp = blockIdx.y;
+  const int p0 = blockIdx.x * rows_per_wg, p1 = min(HW, p0 + rows_per_wg);
+  if ((int)threadIdx.x < 2 * (p1 - p0)) {
+    const int i = threadIdx.x >> 1, p = p0 + i, yy = p / W;
+    if (threadIdx.x & 1) freeu_phase(p - yy * W, W, &ph[i][2], &ph[i][3]);
+    else freeu_phase(yy, H, &ph[i][0], &ph[i][1]);
+  }
+  __syncthreads();
+  const int ck = (C1 + C2) / 8, k1 = C1 / 8, kh = C1 / 16;
+  const bool scale_a = bscale != 1.f, filt = g != 0.f;
+  for (int c = threadIdx.x; c < ck; c += 256) {
+    if (c < k1) {
+      for (int p = p0; p < p1; ++p) {
+        const long long r = (long long)smp * HW + p;
+        bf16x8 v = *(const bf16x8*)(a + (aW ? d2s_row(r, aH, aW) : r) * C1 + c * 8);
+        if (scale_a && c < kh) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = (bf16)((float)v[j] * bscale);
+        }
+        *(bf16x8*)(y + r * (C1 + C2) + c * 8) = v;
+      }
+      continue;
+    }
+    const int cb = (c - k1) * 8;
+    float q[7][8];
+    if (filt) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) {
+        const f32x4* src = (const f32x4*)(coef + ((long long)smp * 7 + k) * C2 + cb);
+        const f32x4 lo = src[0], hi = src[1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { q[k][j] = lo[j]; q[k][4 + j] = hi[j]; }
+      }
+    }
+    for (int p = p0; p < p1; ++p) {
+      const long long r = (long long)smp * HW + p;
+      bf16x8 v = *(const bf16x8*)(b + r * C2 + cb);
+      if (filt) {
+        const float cy = ph[p - p0][0], sy = ph[p - p0][1], cx = ph[p - p0][2], sx = ph[p - p0][3];
+        const float c11 = fmaf(-sy, sx, cy * cx), s11 = fmaf(cy, sx, sy * cx);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float t = fmaf(q[1][j], cy, q[0][j]);
+          t = fmaf(q[2][j], sy, t);
+          t = fmaf(q[3][j], cx, t);
+          t = fmaf(q[4][j], sx, t);
+          t = fmaf(q[5][j], c11, t);
+          t = fmaf(q[6][j], s11, t);
+          v[j] = (bf16)fmaf(g, t, (float)v[j]);
+        }
+      }
+      *(bf16x8*)(y + r * (C1 + C2) + cb + C1) = v;
+    }
+  }
+}
+int launch_concat2_freeu(const bf16* a, int C1, const bf16* b, int C2, const float* coef, bf16* y, int B, int H, int W, float s_scale,
+                         float bscale, hipStream_t s, int aH, int aW) {
+  if (int rc = freeu_shapechk(B, H, W, C2)) return rc;
+  SHAPECHK(C1 >= 16 && C1 % 16 == 0, "freeu concat: C1=%d (C1 / 2 %% 8)", C1);
+  SHAPECHK(!aW || (aH == H && aW == W && H % 2 == 0 && W % 2 == 0), "freeu concat: depth-to-space operand %d x %d on a %d x %d map", aH, aW, H, W);
+  SHAPECHK(s_scale > 0.f && bscale > 0.f && s_scale <= 3.0e38f && bscale <= 3.0e38f, "freeu concat: s=%g b=%g (finite and positive)",
+           (double)s_scale, (double)bscale);
+  SHAPECHK(s_scale == 1.f || coef != nullptr, "freeu concat: no coefficients");
+  const long long rows = (long long)B * H * W;
+  const int rpw = (int)std::max(1LL, std::min(8LL, rows / 512));       // >= 512 workgroups before a lane keeps its coefficients longer
+  const float g = s_scale == 1.f ? 0.f : (s_scale - 1.f) / ((float)H * (float)W);
+  PROF_BEGIN(6, 0.0, 4.0 * rows * (C1 + C2) + (s_scale == 1.f ? 0.0 : 4.0 * 7 * C2 * (double)cdivl(rows, rpw)), s);
+  hipLaunchKernelGGL(concat2_freeu_kernel, dim3(cdiv(H * W, rpw), B), dim3(256), 0, s, a, C1, b, C2, coef, y, H, W, g, bscale, rpw, aH, aW);
   PROF_END(s);
   HIPCHK(hipGetLastError());
   return PEA_OK;

@@ -809,6 +809,7 @@ int Tape::build() {
       const int sk = skips.back();
       skips.pop_back();
       x = bd.concat(x, sk);
+      ops.back().p0 = i + 1;                       // FreeU's tag (Tape::set_freeu): the up block of this concat, plus one
       x = bd.resnet(x, p + ".resnets." + std::to_string(j), c.block_out[lvl]);
       if (c.up_cross[i]) x = bd.transformer(x, p + ".attentions." + std::to_string(j), c.heads[lvl], c.depth_up[i][j]);
     }

@@ -192,6 +192,16 @@ struct Tape {
   int time_cond_dim = 0;
   int t_tcond = -1;
   int set_timestep_cond(const float* cond, hipStream_t s);
+  // FreeU (diffusers 0.23 `enable_freeu`; graph 0, inference only; api_model.hip: pea_unet_set_freeu).  Tape::build tags every
+  // up-path concat with its up-block index + 1 in Op::p0 (0: any other concat).  While fu_on, the concats tagged 1 and 2 run
+  // launch_freeu_coef + launch_concat2_freeu with (fu_s[0], fu_b[0]) and (fu_s[1], fu_b[1]) instead of launch_concat2.  fu_buf:
+  // the coefficients [B][7][C2] (fu_coef_bytes) and behind them the split reduction's partials, sized for the largest tagged
+  // concat at the first set.  Outside the arenas: release_acts keeps it.
+  bool fu_on = false;
+  float fu_s[2] = {1.f, 1.f}, fu_b[2] = {1.f, 1.f};
+  float* fu_buf = nullptr;
+  size_t fu_coef_bytes = 0;
+  int set_freeu(float s1, float s2, float b1, float b2, hipStream_t s);
   // Image prompts (IP-Adapter, graph 0, inference only; api_model.hip: pea_unet_ip_*): up to four adapters ("sets"), each a
   // second K|V stack over its own n image tokens, columns laid out as the text stack's (t_kvall), so a cross-attention op finds
   // its image keys / values at its own bcol / ccol.  All sets share ONE packed image K|V buffer [B][total][cols], set j in rows

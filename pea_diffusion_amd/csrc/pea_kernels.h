@@ -156,6 +156,13 @@ int launch_concat2(const bf16* a, int C1, const bf16* b, int C2, bf16* y, long l
 // split-add (backward of concat): da[r] (+)= dy[r][0:C1]; db[r] (+)= dy[r][C1:]
 int launch_split2(const bf16* dy, int C1, int C2, bf16* da, int accum_a, bf16* db, int accum_b, long long rows,
                   hipStream_t s, int aH = 0, int aW = 0);
+// FreeU on an up-path concat (elementwise.hip): the seven low-frequency sums of every channel map of skip [B][H][W][C2] -> coef fp32
+// [B][7][C2] (scratch: freeu_scratch_bytes, the per-slab partials of a split reduction; 0 bytes = one slab, no scratch), then
+// y = ( bscale * a[:, :C1/2] | a[:, C1/2:] | fourier_filter(skip, threshold 1, scale s) ).  s == 1 never reads coef.
+size_t freeu_scratch_bytes(int B, int H, int W, int C2);
+int launch_freeu_coef(const bf16* skip, int B, int H, int W, int C2, float* coef, float* scratch, hipStream_t s);
+int launch_concat2_freeu(const bf16* a, int C1, const bf16* b, int C2, const float* coef, bf16* y, int B, int H, int W, float s_scale,
+                         float bscale, hipStream_t s, int aH = 0, int aW = 0);
 // 2x2 sum pooling NHWC (backward of nearest 2x upsample): x [B][2H][2W][C] -> y [B][H][W][C]
 int launch_sumpool2(const bf16* x, bf16* y, int B, int H, int W, int C, int accum, hipStream_t s);
 int launch_cast_f32_bf16(const float* x, bf16* y, long long n, hipStream_t s);

@@ -266,6 +266,7 @@ Tape::~Tape() {
   if (rel_bucket) (void)hipFree(rel_bucket);
   if (cross_kvlen) (void)hipFree(cross_kvlen);
   if (inp_buf) (void)hipFree(inp_buf);
+  if (fu_buf) (void)hipFree(fu_buf);
   delete ip;
 }
 
@@ -288,6 +289,36 @@ int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, i
   inp_set = true;
   inp_cond_b = cond_b;
   inp_lat_b = lat_b;
+  return PEA_OK;
+}
+
+int Tape::set_freeu(float s1, float s2, float b1, float b2, hipStream_t s) {
+  if (graph != 0) { pea_set_error("pea_unet_set_freeu: not a UNet handle (graph %d)", graph); return PEA_E_INVALID; }
+  if (needs_grad) {
+    pea_set_error("pea_unet_set_freeu: FreeU is an inference feature (no backward through it); this context was created with PEA_UNET_GRAD");
+    return PEA_E_STATE;
+  }
+  for (float f : {s1, s2, b1, b2})
+    if (!(f > 0.f && f <= 3.0e38f)) {
+      pea_set_error("pea_unet_set_freeu: s1=%g s2=%g b1=%g b2=%g (every factor finite and positive)", (double)s1, (double)s2, (double)b1, (double)b2);
+      return PEA_E_INVALID;
+    }
+  size_t coef = 0, part = 0;
+  for (const Op& o : ops) {
+    if (o.kind != OP_CONCAT || (o.p0 != 1 && o.p0 != 2)) continue;
+    const Tn &a = tn[o.a], &b = tn[o.b];
+    SHAPECHK(a.H >= 2 && a.W >= 2, "pea_unet_set_freeu: up block %d works on a %d x %d map (the filter needs H >= 2 and W >= 2)", o.p0 - 1, a.H, a.W);
+    SHAPECHK(a.cols % 16 == 0 && b.cols % 8 == 0, "pea_unet_set_freeu: up block %d concatenates %d | %d channels (C1 / 2 and C2 %% 8)", o.p0 - 1, a.cols, b.cols);
+    coef = std::max(coef, al256(sizeof(float) * (size_t)a.B * 7 * b.cols));
+    part = std::max(part, freeu_scratch_bytes(a.B, a.H, a.W, b.cols));
+  }
+  if (!fu_buf) {
+    HIPCHK(hipMalloc((void**)&fu_buf, coef + part + 256));
+    HIPCHK(hipMemsetAsync(fu_buf, 0, coef + part + 256, s));
+    fu_coef_bytes = coef;
+  }
+  fu_s[0] = s1; fu_s[1] = s2; fu_b[0] = b1; fu_b[1] = b2;
+  fu_on = true;
   return PEA_OK;
 }
 
@@ -655,6 +686,14 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
         RC(launch_silu_fwd(tn[o.a].d, tn[o.out].d, tn[o.a].rows * tn[o.a].cols, s));
         break;
       case OP_CONCAT:
+        if (fu_on && (o.p0 == 1 || o.p0 == 2)) {   // FreeU: the skip's low-frequency sums, then the concat that scales and filters
+          const Tn &a = tn[o.a], &b = tn[o.b];
+          const float fs = fu_s[o.p0 - 1], fb = fu_b[o.p0 - 1];
+          if (fs != 1.f) RC(launch_freeu_coef(b.d, a.B, a.H, a.W, b.cols, fu_buf, (float*)((char*)fu_buf + fu_coef_bytes), s));
+          RC(launch_concat2_freeu(a.d, a.cols, b.d, b.cols, fu_buf, tn[o.out].d, a.B, a.H, a.W, fs, fb, s, a.d2s ? a.H : 0,
+                                  a.d2s ? a.W : 0));
+          break;
+        }
         RC(launch_concat2(tn[o.a].d, tn[o.a].cols, tn[o.b].d, tn[o.b].cols, tn[o.out].d, tn[o.a].rows, s,
                           tn[o.a].d2s ? tn[o.a].H : 0, tn[o.a].d2s ? tn[o.a].W : 0));
         break;

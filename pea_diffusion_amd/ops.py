@@ -143,6 +143,34 @@ def concat2(a, b, d2s_hw=None):
     return y
 
 
+def freeu_scratch_bytes(B, H, W, C2):
+    """device bytes of the split reduction's partials behind `freeu_concat` (host only); 0: one slab per map, no scratch"""
+    return int(lib().pea_op_freeu_scratch_bytes(B, H, W, C2))
+
+
+def freeu_concat(a, b, s, bscale, d2s=False, y=None, coef=None, scratch=None):
+    """FreeU on the operands of an up-path concat (diffusers 0.23 `apply_freeu`): b [B,H,W,C2] is the skip tensor, a [B,H,W,C1]
+    the hidden state (d2s: stored depth-to-space, [B,H/2,W/2,4,C1]).  -> (y [B*H*W, C1+C2] = (bscale * a[..., :C1/2] |
+    a[..., C1/2:] | fourier_filter(b, threshold 1, scale s)), coef fp32 [B,7,C2]: the filter's seven sums per channel map, or
+    None with s == 1, which needs none).  y / coef / scratch: buffers to use instead of fresh ones."""
+    B, H, W, C2 = b.shape
+    C1 = a.shape[-1]
+    if y is None:
+        y = torch.empty(B * H * W, C1 + C2, device=b.device, dtype=BF)
+    if s != 1.0:
+        if coef is None:
+            coef = torch.empty(B, 7, C2, device=b.device, dtype=torch.float32)
+        nbytes = freeu_scratch_bytes(B, H, W, C2)
+        if scratch is None and nbytes:
+            scratch = torch.empty(nbytes // 4, device=b.device, dtype=torch.float32)
+        check(lib().pea_op_freeu_coef(ptr(b), B, H, W, C2, ptr(coef), ptr(scratch), stream_ptr()))
+    else:
+        coef = None
+    check(lib().pea_op_concat2_freeu(ptr(a), C1, ptr(b), C2, ptr(coef), ptr(y), B, H, W, float(s), float(bscale),
+                                     H if d2s else 0, W if d2s else 0, stream_ptr()))
+    return y, coef
+
+
 def split2(dy, C1, C2, da=None, db=None, accum_a=False, accum_b=False, d2s_hw=None):
     rows = dy.numel() // (C1 + C2)
     H, W = d2s_hw if d2s_hw else (0, 0)

@@ -197,6 +197,23 @@ class HipUNet(HipTape):
         check(lib().pea_unet_set_timestep_cond(self._h, ptr(c), stream_ptr()))
         self._tcond = c
 
+    # ---------------------------------------------------------------- FreeU
+    freeu = None           # (s1, s2, b1, b2) while the switch is on
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """diffusers' `pipe.enable_freeu(s1, s2, b1, b2)` (0.23; training-free, no weights): in front of every skip concatenation
+        of `up_blocks[0]` (s1, b1) and `up_blocks[1]` (s2, b2) the first half of the hidden channels is multiplied by b and the
+        skip tensor's four lowest frequencies by s (`fourier_filter`, threshold 1), inside the concat's own launch plus one
+        reduction.  A switch of THIS context (one sharing its weights carries its own); every later call runs with it until
+        `disable_freeu()`; calling again replaces the factors.  Inference contexts only."""
+        check(lib().pea_unet_set_freeu(self._h, float(s1), float(s2), float(b1), float(b2), stream_ptr()))
+        self.freeu = (float(s1), float(s2), float(b1), float(b2))
+
+    def disable_freeu(self):
+        """diffusers' `pipe.disable_freeu()`: the plain concat launches again, bit for bit"""
+        check(lib().pea_unet_clear_freeu(self._h))
+        self.freeu = None
+
     # ---------------------------------------------------------------- inpainting condition
     _inp = None            # (mask, masked_latents) fp32 on the device, as last handed to the context
     _inp_lat_b = 0
