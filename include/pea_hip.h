@@ -802,6 +802,19 @@ void pea_debug_set_gemm_variant(int v);
  * 256 column scale, 512 split-K, 1024 pointers 16-byte aligned and row strides multiples of 8 (else 4-byte / multiples of 4).
  * M <= 0: the N-th entry of the enumerator list instead (-1 past its end). */
 int pea_debug_gemm_dispatch(int M, int N, int K, int mode, int rows_per_batch, int features, int cus, int forced);
+/* Test aid, needs no device: what launch_attention_fwd / _bwd / _fwd_fewq launch for a problem (shape checks included).
+ * q[14] = { direction (0 forward, 1 backward, 2 few-query forward), B, H, Sq, Skv, nd, features, Skv2, image key sets, bit j: set j
+ * has a mask, then the four switches or -1 for the process's own: pea_debug_set_xattn_bwd_v2, _attn_tr, _attn_xattn,
+ * _attn_fused_bwd }.  features: 1 causal, 2 per-sample key counts, 4 score bias, 8 prescaled Q, 16 a second key set (K2 / V2 with
+ * Skv2 keys, shared evenly among the sets), 32 every set weight 0, 64 / 128 / 256 dQ / dK / dV wanted, 512 split scratch passed,
+ * 1024 gradients accumulate.  Returns PEA_OK and out[0] = launches (<= 3), out[1] = query-range splits, then per launch 7 ints at
+ * out[2 + 7 i]: enumerator, grid x / y / z, dynamic LDS bytes, two scalar arguments (units per workgroup; or dQ and dK/dV blocks
+ * per head of the fused backward); or the error code of a refused problem (pea_last_error has the text).  out holds 23 ints.
+ * Enumerators: 0 + 4 f + (KB - 1) xattn_fwd_kernel<KB> (f: 0 plain, 1 one image key set, 2 several); 12 + 6 MODE + 3 TR + (ND - 1)
+ * attn_q_kernel (MODE 1: dQ); 24 its masked instance; 25 + 3 TR + (ND - 1) attn_dkv_kernel; 31 + 3 TR + (ND - 1)
+ * attn_bwd_fused_kernel; 37 + (KB - 1) xattn_bwd_kernel; 41 / 45 + 2 (KB - 2) + PRE xattn_bwd2_kernel / xattn_bwd3_kernel;
+ * 49 attn_fewq_kernel; 50 attn_delta_kernel; 51 attn_dkv_reduce_kernel.  direction outside 0..2: the q[1]-th enumerator (-1 past the end). */
+int pea_debug_attn_dispatch(const int* q, int* out);
 /* timing-only probes of the loader/consumer GEMM (results are wrong while set): 1 no DMA, 2 no barriers, 4 no ds_reads */
 void pea_debug_set_gemm_debug(int v);
 /* experiment aid (scripts/chain_probe.py): arms the NEXT GEMM / conv launch with a prefetch target -- its DMA waves touch

@@ -23,14 +23,20 @@ int pea_zero_page(const bf16** out) {
   return PEA_OK;
 }
 
+// what every attention entry point starts from: a zeroed AttnP with Q / K / V / O, lse, the shape, the scale and nd set
+static AttnP attn_operands(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O, int ldo,
+                           const float* lse, int B, int H, int Sq, int Skv, float scale, int nd) {
+  AttnP p;
+  memset(&p, 0, sizeof(p));
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
+  p.O = (bf16*)O; p.ldo = ldo; p.lse = (float*)lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = nd;
+  return p;
+}
 // bodies of the attention operators with the Q convention as a PARAMETER (the entry points below pass 0 or 1): nothing
 // process-wide is written around a call, so concurrent callers (ctypes releases the GIL) cannot see each other's mode
 static int attention_fwd_impl(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
                               float* lse, int B, int H, int Sq, int Skv, float scale, int nd, int q_prescaled, void* stream) {
-  AttnP p;
-  memset(&p, 0, sizeof(p));
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = nd;
+  AttnP p = attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, nd);
   p.q_prescaled = q_prescaled;
   return launch_attention_fwd(p, (hipStream_t)stream);
 }
@@ -39,13 +45,10 @@ static int attention_bwd_impl(const void* Q, int ldq, const void* K, int ldk, co
                               void* dK, int lddk, void* dV, int lddv, int B, int H, int Sq, int Skv, float scale,
                               int accum_dq, int accum_dkv, int nd, void* scratch, int q_prescaled, const int* kv_len,
                               void* stream) {
-  AttnP p;
-  memset(&p, 0, sizeof(p));
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-  p.O = (bf16*)O; p.ldo = ldo; p.lse = (float*)lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale;
+  AttnP p = attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, nd);
   p.dO = (const bf16*)dO; p.lddo = lddo; p.delta = delta;
   p.dQ = (bf16*)dQ; p.lddq = lddq; p.dK = (bf16*)dK; p.lddk = lddk; p.dV = (bf16*)dV; p.lddv = lddv;
-  p.accum_dq = accum_dq; p.accum_dkv = accum_dkv; p.dkv_part = (float*)scratch; p.nd = nd;
+  p.accum_dq = accum_dq; p.accum_dkv = accum_dkv; p.dkv_part = (float*)scratch;
   p.q_prescaled = q_prescaled; p.kv_len = kv_len;
   return launch_attention_bwd(p, (hipStream_t)stream);
 }
@@ -263,20 +266,14 @@ int pea_op_attention_fwd_prescaled(const void* Q, int ldq, const void* K, int ld
 int pea_op_attention_fwd_masked(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
                                 float* lse, int B, int H, int Sq, int Skv, float scale, int causal, const int* kv_len,
                                 void* stream) {
-  AttnP p;
-  memset(&p, 0, sizeof(p));
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = 1;
+  AttnP p = attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, 1);
   p.causal = causal; p.kv_len = kv_len;
   return launch_attention_fwd(p, (hipStream_t)stream);
 }
 int pea_op_attention_fwd_text(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
                               float* lse, int B, int H, int Sq, int Skv, float scale, int q_prescaled, int causal,
                               const int* kv_len, const float* bias, void* stream) {
-  AttnP p;
-  memset(&p, 0, sizeof(p));
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = 1;
+  AttnP p = attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, 1);
   p.q_prescaled = q_prescaled; p.causal = causal; p.kv_len = kv_len; p.bias = bias;
   return launch_attention_fwd(p, (hipStream_t)stream);
 }
@@ -284,10 +281,7 @@ int pea_op_attention_fwd_ip(const void* Q, int ldq, const void* K, int ldk, cons
                             const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                             float scale, float ip_scale, int q_prescaled, int causal, const int* kv_len, void* stream) {
   SHAPECHK(K2 && V2 && Skv2 >= 1, "pea_op_attention_fwd_ip: no image keys (Skv2=%d)", Skv2);
-  AttnP p;
-  memset(&p, 0, sizeof(p));
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = 1;
+  AttnP p = attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, 1);
   p.q_prescaled = q_prescaled; p.causal = causal; p.kv_len = kv_len;
   p.K2 = (const bf16*)K2; p.V2 = (const bf16*)V2; p.ldk2 = ldk2; p.ldv2 = ldv2; p.Skv2 = Skv2; p.scale2 = ip_scale;
   return launch_attention_fwd(p, (hipStream_t)stream);
@@ -297,10 +291,7 @@ int pea_op_attention_fwd_ipn(const void* Q, int ldq, const void* K, int ldk, con
                              const pea_attn_ip_sets* sets, float scale, int q_prescaled, int causal, const int* kv_len, void* stream) {
   SHAPECHK(sets && K2 && V2, "pea_op_attention_fwd_ipn: no image keys");
   SHAPECHK(sets->n_sets >= 1 && sets->n_sets <= 4, "pea_op_attention_fwd_ipn: 1..4 image key sets (n_sets=%d)", sets->n_sets);
-  AttnP p;
-  memset(&p, 0, sizeof(p));
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = 1;
+  AttnP p = attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, 1);
   p.q_prescaled = q_prescaled; p.causal = causal; p.kv_len = kv_len;
   p.K2 = (const bf16*)K2; p.V2 = (const bf16*)V2; p.ldk2 = ldk2; p.ldv2 = ldv2;
   p.nset = sets->n_sets;
@@ -317,10 +308,7 @@ int pea_op_attention_fwd_ipn(const void* Q, int ldq, const void* K, int ldk, con
 int pea_op_attention_fwd_fewq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                               const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                               float scale, int nd, int q_prescaled, void* stream) {
-  AttnP p;
-  memset(&p, 0, sizeof(p));
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-  p.O = (bf16*)O; p.ldo = ldo; p.lse = lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = nd;
+  AttnP p = attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, nd);
   p.q_prescaled = q_prescaled;
   p.K2 = (const bf16*)K2; p.V2 = (const bf16*)V2; p.ldk2 = ldk2; p.ldv2 = ldv2; p.Skv2 = Skv2;
   return launch_attention_fwd_fewq(p, (hipStream_t)stream);

@@ -29,26 +29,14 @@
 // one copy has to be carried to the others by hand.  Each of these was tried as a shared __forceinline__ helper; the table
 // in profiles/EXPERIMENTS.md ("Cross-attention backward: one launcher, one context helper") says per piece whether it
 // moved register counts (not wanted) or only the instruction order (open: needs a bit-identity and timing A/B on a GPU).
-// Host side (bottom of the file): launch_lds raises a kernel's dynamic-LDS limit once and launches it; launch_xattn_fwd /
-// launch_xattn_bwd1 / launch_xattn_bwd23 map the run-time (key blocks, prescaled Q) to the instantiation;
-// launch_dkv_reduce is the ordered split reduce behind any backward that wrote partials.
+// Host side (bottom of the file): attn_decide_fwd / attn_decide_bwd turn a problem into an AttnPlan (which instantiations, grids,
+// LDS bytes, in which order); attn_launch maps a plan's enumerator to its instantiation; launch_lds raises a kernel's dynamic-LDS
+// limit once and launches it.
 #include <stdlib.h>
 
 #include "pea_kernels.h"
 
 #define TILE_BYTES 8192   // 64 rows x 128 bytes
-#ifndef PEA_ATTN_WT
-#define PEA_ATTN_WT 0     // experiment: O / dQ rows leave as write-through (sc1) stores (see norm.hip: PEA_LN_WT)
-#endif
-#ifndef PEA_ATTN_DQ_READS_DELTA
-#define PEA_ATTN_DQ_READS_DELTA 1   // fused backward: the dQ role reads (-delta, -lse log2 e) from attn_delta_kernel's output instead of recomputing delta from O
-#endif
-#ifndef PEA_ATTN_DKV_LDS_EPI
-#define PEA_ATTN_DKV_LDS_EPI 1      // dK / dV leave through a per-wave LDS image as whole 128-byte rows (16 bytes per lane) instead of 8-byte pieces over 32 lines
-#endif
-#ifndef PEA_ATTN_BWD_PREFETCH
-#define PEA_ATTN_BWD_PREFETCH 0   // 1: backward roles request each batch of LDS fragments one phase ahead of its MFMAs (A/B: 1 % slower, +40 registers)
-#endif
 // raw v_exp_f32: exp2f() expands to a denormal-safe 5-instruction sequence; every argument here is <= 0 (scores
 // minus a running max / the log-sum-exp), so a flushed denormal result is an exact zero after bf16 rounding anyway
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -273,7 +261,7 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
       for (int s = 0; s < 4; ++s)
         dof[nd][s] = *(const bf16x8*)(dOb + (long long)qrow * p.lddo + nd * 64 + 16 * s + 8 * fh);
     const long long li = ((long long)b * p.H + head) * p.Sq + qrow;
-    if (!WRITE_DELTA && PEA_ATTN_DQ_READS_DELTA) {
+    if (!WRITE_DELTA) {
       // fused launch: attn_delta_kernel ran in front of this grid and left -delta[q] and -lse[q] * log2(e) for the dK/dV role;
       // the dQ role takes the same two floats instead of re-reading its O row (4 x 16 bytes per lane over 32 lines per
       // instruction) and redoing the 64 multiply-adds -- bit-identical inputs for both roles
@@ -376,10 +364,6 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
     // before the first MFMA: read-wait-MFMA per fragment (what the compiler emits for the fused loop under a 128-register
     // budget) exposes one LDS latency per MFMA, i.e. the matrix pipe runs at a quarter of its rate in this phase.
     f32x16 sacc[2];
-    // dQ role: the V fragments of the dP product are requested BEFORE the S MFMAs and the transposed K fragments of the dQ
-    // product before the exponentials, so each batch of LDS reads lands under the work in front of it (two waves per SIMD
-    // do not cover an LDS round trip per batch; the forward's three do, and it has no registers to spare)
-    bf16x8 vfr0[2][4];
 #pragma unroll
     for (int nd = 0; nd < ND; ++nd) {
       bf16x8 kfr[2][4];
@@ -387,12 +371,6 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int s = 0; s < 4; ++s) kfr[kb][s] = *(const bf16x8*)(smem + rfc[s] + (nd * TILE_BYTES + kb * 4096));
-      if (MODE == 1 && nd == ND - 1 && PEA_ATTN_BWD_PREFETCH) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int s = 0; s < 4; ++s) vfr0[kb][s] = *(const bf16x8*)(smem + rfc[s] + (ND * TILE_BYTES + kb * 4096));
-      }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < 4; ++s)
@@ -402,7 +380,6 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
     }
     const int kv0 = t * 64;
     bf16x8 pf[4];   // P^T (fwd) or dS^T (dQ) as B-operand fragments, k-permuted
-    bf16x8 tfr1[MODE == 1 ? 4 : 1][2];   // dQ role: transposed K fragments, requested early
     if (MODE == 0) {
       // keys beyond Skv are masked only in the tile that contains them.
       // TXT (text encoders, inference): causal mask and / or a per-sample key count (padding) -- a separate instance
@@ -491,20 +468,7 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            if (nd == 0 && PEA_ATTN_BWD_PREFETCH) vfr[kb][s] = vfr0[kb][s];            // requested before the S products
-            else vfr[kb][s] = *(const bf16x8*)(smem + rfc[s] + ((ND + nd) * TILE_BYTES + kb * 4096));
-          }
-        if (nd == ND - 1 && PEA_ATTN_BWD_PREFETCH) {           // the dQ product's transposed K fragments: under dP and the exponentials
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-              if constexpr (USE_TR)
-                tfr1[ks][db] = read_transposed_frag_at(smem + trc[db][0] + ks * 2048, smem + trc[db][1] + ks * 2048);
-              else tfr1[ks][db] = read_transposed_frag<false>(Ks + chunk * TILE_BYTES, ks * 16, db * 32, lane);
-            }
-        }
+          for (int s = 0; s < 4; ++s) vfr[kb][s] = *(const bf16x8*)(smem + rfc[s] + ((ND + nd) * TILE_BYTES + kb * 4096));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 4; ++s)
@@ -545,7 +509,6 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
       for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
         for (int db = 0; db < 2; ++db) {
-          if constexpr (MODE == 1 && PEA_ATTN_BWD_PREFETCH) { tfr[ks][db] = tfr1[ks][db]; continue; }
           if constexpr (USE_TR)
             tfr[ks][db] = read_transposed_frag_at(smem + trc[db][0] + (no * TILE_BYTES + ks * 2048),
                                                   smem + trc[db][1] + (no * TILE_BYTES + ks * 2048));
@@ -604,7 +567,7 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = (bf16)((float)v[j] + (float)old[j]);
         }
-        store16<PEA_ATTN_WT != 0>(dst, v);
+        *(bf16x8*)dst = v;
       }
     }
   }
@@ -759,12 +722,7 @@ __device__ __forceinline__ void attn_dkv_body(const AttnP& p, char* smem, int bl
       load_rows(0, 0);
 #pragma unroll
       for (int qb = 0; qb < 2; ++qb) {
-        if (PEA_ATTN_BWD_PREFETCH) {
-          if (qb == 0) load_rows(1, 1);
-          else load_tr(0);                        // lands under the second block's MFMAs and the exponentials
-        } else if (qb == 1) {
-          load_rows(1, 1);
-        }
+        if (qb == 1) load_rows(1, 1);
         __builtin_amdgcn_sched_barrier(0);
         if (!all_valid) {
 #pragma unroll
@@ -798,7 +756,7 @@ __device__ __forceinline__ void attn_dkv_body(const AttnP& p, char* smem, int bl
       // two k-slices (8 transposed fragments = 32 registers) per batch of 8 MFMAs; the second batch's fragments are read
       // while the first batch's MFMAs run
       __builtin_amdgcn_sched_barrier(0);
-      if (!PEA_ATTN_BWD_PREFETCH) load_tr(0);
+      load_tr(0);
       load_tr(1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -817,7 +775,7 @@ __device__ __forceinline__ void attn_dkv_body(const AttnP& p, char* smem, int bl
     __syncthreads();
   }
   // (whole waves store rows there: ragged lanes stay; an accumulating store keeps the direct form -- fp32 sum, ONE rounding)
-  const bool lds_epi = PEA_ATTN_DKV_LDS_EPI && p.nsplit <= 1 && !p.accum_dkv;
+  const bool lds_epi = p.nsplit <= 1 && !p.accum_dkv;
   if (lds_epi ? !wave_active : !kstored) return;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -1256,7 +1214,7 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
       for (int i = 0; i < 4; ++i) {
         const int row = i * 8 + r8;
         const bf16x8 v = *(const bf16x8*)(ost + row * 144 + ch * 16);
-        if (q0w + row < p.Sq) store16<PEA_ATTN_WT != 0>(Ob + (long long)(q0w + row) * p.ldo, v);
+        if (q0w + row < p.Sq) *(bf16x8*)(Ob + (long long)(q0w + row) * p.ldo) = v;
       }
     }
   }
@@ -2369,12 +2327,11 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd3_kernel(const AttnP p, int u
 
 // row constants of the backward kernels: delta[0][b][h][q] = -sum_d dO[q][h*D+d] * O[q][h*D+d], delta[1][b][h][q] = -lse * log2(e);
 // 8 lanes per (row, head), each sums D/8 elements
-#ifndef PEA_ATTN_DELTA_ROWS
-#define PEA_ATTN_DELTA_ROWS 4      // (row, head) slots per thread, all requested before the first use: a thread with ONE pair of 16-byte loads in
-                                   // flight left the kernel latency-bound (9.6 us for 21 MB); 1 restores that form
-#endif
+// (row, head) slots per thread, all requested before the first use: a thread with ONE pair of 16-byte loads in flight left the
+// kernel latency-bound (9.6 us for 21 MB)
+constexpr int ATTN_DELTA_ROWS = 4;
 __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnP p) {
-  constexpr int NR = PEA_ATTN_DELTA_ROWS;
+  constexpr int NR = ATTN_DELTA_ROWS;
   const long long total = (long long)p.B * p.Sq * p.H * 8;            // one lane per (b, q, head, 8-lane slot)
   const long long stride = (long long)gridDim.x * 256;                // slot r of a thread: idx + r * stride (coalesced per r)
   const long long idx0 = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -2469,22 +2426,40 @@ __global__ void attn_dkv_reduce_kernel(const AttnP p) {
   *(bf16x4*)dst = o;
 }
 
-// Which one-pass cross-attention backward kernel (PEA_XATTN_BWD_VER=n in the environment, pea_debug_set_xattn_bwd_v2(n) at
-// run time: A/B, parity tests):
-//   0              v1, xattn_bwd_kernel (round 3), for every key count
-//   2              v2, xattn_bwd2_kernel, where it applies (33..96 keys); v1 elsewhere
-//   1, 3 (default) the newest that applies: v3, xattn_bwd3_kernel, for 33..80 keys, v2 for 81..96, v1 elsewhere
-static int g_xattn_v2 = getenv("PEA_XATTN_BWD_VER") ? atoi(getenv("PEA_XATTN_BWD_VER")) : 3;
-extern "C" void pea_debug_set_xattn_bwd_v2(int v) { g_xattn_v2 = v; }
-static bool xattn_v2_keys(int Skv) { return g_xattn_v2 && Skv > 32 && Skv <= 96; }     // v2 OR v3: 64-query units
-static bool xattn_v3_keys(int Skv) { return g_xattn_v2 != 0 && g_xattn_v2 != 2 && Skv > 32 && Skv <= 80; }
+// ============================================================================= host: what a call launches
+// attn_decide_fwd / attn_decide_bwd: pure functions of the problem (AttnP) and the four switches (AttnEnv) that fill an AttnPlan
+// -- up to three launches in order, each a kernel enumerator, its grid, its dynamic LDS bytes and its scalar arguments.  A launcher
+// is the shape checks, that call and a walk over the plan through attn_launch, the one switch that names the instantiations.
+// pea_debug_attn_dispatch exports the plan without a device (tests/test_attn_dispatch_cpu.py, tests/golden/attn_dispatch.json).
+enum AttnKernel : int {   // a family's enumerators are arithmetic in its template arguments (include/pea_hip.h has the formulas)
+  AK_XFWD = 0, AK_Q = 12, AK_Q_TXT = 24, AK_DKV = 25, AK_FUSED = 31, AK_XBWD1 = 37, AK_XBWD2 = 41, AK_XBWD3 = 45, AK_FEWQ = 49,
+  AK_DELTA = 50, AK_REDUCE = 51, AK_COUNT = 52
+};
+struct AttnLaunch { int kernel; dim3 grid; int lds, a0, a1; };   // a0: upw (cross-attention) or n_dq (fused backward); a1: n_dkv
+struct AttnPlan {
+  AttnLaunch l[3]; int n = 0, nsplit = 1;                         // nsplit: query-range splits of the backward (attn_nsplit)
+  void add(int kernel, dim3 grid, int lds, int a0 = 0, int a1 = 0) { l[n++] = AttnLaunch{kernel, grid, lds, a0, a1}; }
+};
+// The switches, read once from the environment (A/B runs) and written by the pea_debug_set_* calls (parity tests).  xattn_ver
+// (PEA_XATTN_BWD_VER=n), which one-pass cross-attention backward kernel: 0 = v1, xattn_bwd_kernel (round 3), for every key count;
+// 2 = v2, xattn_bwd2_kernel, where it applies (33..96 keys), v1 elsewhere; 1, 3 (default) = the newest that applies: v3,
+// xattn_bwd3_kernel, for 33..80 keys, v2 for 81..96, v1 elsewhere.  use_tr 0: the general kernels gather their fragments;  xattn 0
+// (PEA_XATTN_OFF=1): cross-attention on the general kernels;  fused_bwd 0 (PEA_ATTN_BWD_SPLIT=1): dQ and dK / dV as two launches
+struct AttnEnv { int xattn_ver, use_tr, xattn, fused_bwd; };
+static AttnEnv g_attn_env = {getenv("PEA_XATTN_BWD_VER") ? atoi(getenv("PEA_XATTN_BWD_VER")) : 3, 1, getenv("PEA_XATTN_OFF") ? 0 : 1,
+                             getenv("PEA_ATTN_BWD_SPLIT") ? 0 : 1};
+extern "C" void pea_debug_set_xattn_bwd_v2(int v) { g_attn_env.xattn_ver = v; }
+extern "C" void pea_debug_set_attn_tr(int v) { g_attn_env.use_tr = v; }
+extern "C" void pea_debug_set_attn_xattn(int v) { g_attn_env.xattn = v; }
+extern "C" void pea_debug_set_attn_fused_bwd(int v) { g_attn_env.fused_bwd = v; }
+static bool xattn_v2_keys(int Skv, const AttnEnv& e) { return e.xattn_ver && Skv > 32 && Skv <= 96; }     // v2 OR v3: 64-query units
 // query-range splitting of the cross-attention backward (few keys, many queries): a workgroup owns `u` consecutive
 // 128-query units of one (batch, head); pick the u that minimises (rounds of 512 workgroups: two per CU) x u, then the
 // split count (fp32 partials per split).  1024 tokens, B*H = 80: u = 2 -> 320 workgroups, 4 splits; 4096 tokens, 40:
 // u = 3 -> 440 workgroups, 11 splits.
-int attention_bwd_nsplit(int B, int H, int Sq, int Skv) {
+static int attn_nsplit(int B, int H, int Sq, int Skv, const AttnEnv& e) {
   if (Skv > 128 || Sq < 512) return 1;
-  const bool v2 = xattn_v2_keys(Skv);
+  const bool v2 = xattn_v2_keys(Skv, e);
   const int uq = v2 ? 64 : 128;                                          // queries per unit
   // v2: a workgroup's fixed part (K / V staging, the first unit's flight, the hand-over and the partial stores) is worth
   // about two of its 64-query units; without it the rule cut B * H = 160 (per-GPU batch 8) into 2560 one-unit workgroups:
@@ -2502,16 +2477,60 @@ int attention_bwd_nsplit(int B, int H, int Sq, int Skv) {
   }
   return best_ns;
 }
+int attention_bwd_nsplit(int B, int H, int Sq, int Skv) { return attn_nsplit(B, H, Sq, Skv, g_attn_env); }
 size_t attention_bwd_scratch_bytes(int B, int H, int Sq, int Skv, int nd) {
   const int ns = attention_bwd_nsplit(B, H, Sq, Skv);
   return ns > 1 ? (size_t)ns * B * H * Skv * 128 * nd * sizeof(float) : 0;
 }
-
-static int g_attn_use_tr = 1;
-static int g_attn_xattn = getenv("PEA_XATTN_OFF") ? 0 : 1;               // PEA_XATTN_OFF=1: cross-attention on the general kernels (A/B)
-extern "C" void pea_debug_set_attn_xattn(int v) { g_attn_xattn = v; }
-extern "C" void pea_debug_set_attn_tr(int v) { g_attn_use_tr = v; }
-
+// the kernels with K / V resident in LDS exist for head_dim 64 and at most 128 keys, and read through the transpose path
+static bool attn_resident_kv(const AttnP& p, const AttnEnv& e) { return e.xattn && e.use_tr && p.nd == 1 && p.Skv <= 128; }
+static int attn_decide_fwd(const AttnP& p, const AttnEnv& e, AttnPlan& plan) {
+  const int nu = cdiv(p.Sq, 128);
+  // cross-attention: K / V resident.  With a second key set (attn_check_ip has passed: head_dim 64, <= 128 keys) always, at any
+  // query count: there is no other kernel for it
+  if (p.K2 || (attn_resident_kv(p, e) && !p.causal && !p.bias && p.Sq >= 128)) {
+    const int kb = cdiv(p.Skv, 32), kt = (kb + 1) / 2;
+    const int lds = 2 * kt * TILE_BYTES + 4 * 32 * 144 + 4 * 4096 + (p.K2 ? 2 * 4096 : 0);
+    int upw = (int)(((long long)p.B * p.H * nu + 511) / 512);   // one round of two workgroups per CU (66 KB of LDS each, 74 KB with image keys)
+    upw = upw < 1 ? 1 : (upw > nu ? nu : upw);
+    plan.add(AK_XFWD + 4 * (!p.K2 ? 0 : p.nset ? 2 : 1) + (kb - 1), dim3(cdiv(nu, upw), p.H, p.B), lds, upw);
+    return PEA_OK;
+  }
+  const bool txt = p.causal || p.kv_len || p.bias;              // text-encoder masks / score bias: separate instance (head_dim 64 only)
+  SHAPECHK(!txt || p.nd == 1, "attention: causal / key-length masks need head_dim 64");
+  plan.add(txt ? AK_Q_TXT : AK_Q + 3 * (e.use_tr != 0) + (p.nd - 1), dim3(nu, p.H, p.B), 2 * 2 * p.nd * TILE_BYTES);
+  return PEA_OK;
+}
+static int attn_decide_bwd(const AttnP& p, const AttnEnv& e, AttnPlan& plan) {
+  const int ns = plan.nsplit = p.dkv_part ? attn_nsplit(p.B, p.H, p.Sq, p.Skv, e) : 1;
+  const int nd = p.nd, tr = e.use_tr != 0;
+  bool all = p.dQ && p.dK && p.dV, partials = true;                // partials: some launch writes dK / dV (fp32 partials where ns > 1)
+  if (attn_resident_kv(p, e) && all) {                             // the one-pass cross-attention backward
+    const int kb = cdiv(p.Skv, 32);
+    const dim3 grid(ns, p.H, p.B);
+    if (xattn_v2_keys(p.Skv, e)) {                                 // v2 or v3 (2 or 3 key blocks): 64-query units
+      const bool v3 = e.xattn_ver != 2 && p.Skv <= 80;
+      const int lds = v3 ? 2 * (TILE_BYTES + TILE_BYTES / 2) + 2 * (2 * TILE_BYTES + 512) + 2 * (TILE_BYTES + 2048)
+                         : 4 * TILE_BYTES + 2 * (2 * TILE_BYTES + 512) + 2 * 32 * 144;
+      plan.add((v3 ? AK_XBWD3 : AK_XBWD2) + 2 * (kb - 2) + (p.q_prescaled != 0), grid, lds, cdiv(cdiv(p.Sq, 64), ns));
+    } else {                                                       // v1: 128-query units
+      plan.add(AK_XBWD1 + (kb - 1), grid, 4 * TILE_BYTES + (4 * TILE_BYTES + 1024), cdiv(cdiv(p.Sq, 128), ns));
+    }
+  } else {
+    const int lq = 2 * 2 * nd * TILE_BYTES, lk = 2 * (2 * nd * TILE_BYTES + 512);
+    const int n_dq = cdiv(p.Sq, 128) * nd, n_dkv = cdiv(p.Skv, 128) * ns * nd;
+    const bool fused = all && e.fused_bwd;
+    // delta: its own (memory-bound) kernel for the fused launch and for dK/dV-only calls; the two-launch form computes it in the dQ pass
+    if (fused || !p.dQ) plan.add(AK_DELTA, dim3((unsigned)cdivl((long long)p.B * p.Sq * p.H * 8, 256 * ATTN_DELTA_ROWS)), 0);
+    partials = fused || (p.dK && p.dV);
+    if (fused) plan.add(AK_FUSED + 3 * tr + (nd - 1), dim3((unsigned)((n_dq + n_dkv) * p.H * p.B)), lk, n_dq, n_dkv);
+    if (!fused && p.dQ) plan.add(AK_Q + 6 + 3 * tr + (nd - 1), dim3(n_dq, p.H, p.B), lq);
+    if (!fused && partials) plan.add(AK_DKV + 3 * tr + (nd - 1), dim3(n_dkv, p.H, p.B), lk);
+  }
+  // the ordered sum of the query-range splits' fp32 dK / dV partials, behind whichever kernel wrote them
+  if (ns > 1 && partials) plan.add(AK_REDUCE, dim3((unsigned)cdivl((long long)p.B * p.H * p.Skv * 2 * 16 * nd, 256)), 0);
+  return PEA_OK;
+}
 // a second key set (AttnP::K2, the image prompt's): forward only, served by xattn_fwd_kernel<KB, true> alone
 static int attn_check_ip(const AttnP& p) {
   SHAPECHK(p.K2 != nullptr && p.V2 != nullptr, "attention: a second key set needs both K2 and V2");
@@ -2546,165 +2565,9 @@ static void attn_resolve_sets(AttnP& p) {
     for (int j = p.nset; j < 4; ++j) { p.set_end[j] = p.Skv2; p.set_w[j] = 0.f; p.set_mask[j] = nullptr; }
   }
 }
-static int attn_check(const AttnP& p) {
-  SHAPECHK(p.B > 0 && p.H > 0 && p.Sq > 0 && p.Skv > 0, "attention: empty problem");
-  SHAPECHK(p.nd >= 1 && p.nd <= 3, "attention: padded head_dim must be 64, 128 or 192 (nd=%d)", p.nd);
-  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0, "attention: leading dims must be multiples of 8");
-  return PEA_OK;
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize of kernel K raised to `bytes`, once per process, then the launch: every
-// kernel of this file that takes dynamic LDS goes through here, so no list of instantiations has to be kept by hand.
-// The attribute call belongs to an instantiation's FIRST launch: if that launch is inside a stream capture, the call
-// happens during the capture (it is not a stream operation and is not recorded).
-template <auto K, typename... Args>
-static int launch_lds(dim3 grid, int bytes, hipStream_t s, const Args&... args) {
-  static bool raised = false;
-  if (!raised) {
-    HIPCHK(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    raised = true;
-  }
-  hipLaunchKernelGGL(K, grid, dim3(256), bytes, s, args...);
-  return PEA_OK;
-}
-// the general kernels: the transpose-read instance, or (pea_debug_set_attn_tr(0)) the one that gathers its fragments
-#define ATTN_DISPATCH(KERNEL_TR, KERNEL_NOTR, grid, lds, ...)                           \
-  (g_attn_use_tr ? launch_lds<KERNEL_TR>(grid, lds, s, p, ##__VA_ARGS__)                \
-                 : launch_lds<KERNEL_NOTR>(grid, lds, s, p, ##__VA_ARGS__))
-
-// run-time (key blocks of 32, prescaled Q) -> instantiation, one dispatch per cross-attention kernel family
-template <bool IP = false, bool MS = false>                        // IP: with a second key set (AttnP::K2); MS: that set is several
-static int launch_xattn_fwd(int kb, dim3 grid, int lds, hipStream_t s, const AttnP& p, int upw) {
-  switch (kb) {
-    case 1: return launch_lds<xattn_fwd_kernel<1, IP, MS>>(grid, lds, s, p, upw);
-    case 2: return launch_lds<xattn_fwd_kernel<2, IP, MS>>(grid, lds, s, p, upw);
-    case 3: return launch_lds<xattn_fwd_kernel<3, IP, MS>>(grid, lds, s, p, upw);
-    default: return launch_lds<xattn_fwd_kernel<4, IP, MS>>(grid, lds, s, p, upw);
-  }
-}
-static int launch_xattn_bwd1(int kb, dim3 grid, hipStream_t s, const AttnP& p, int upw) {
-  constexpr int lds = 4 * TILE_BYTES + (4 * TILE_BYTES + 1024);
-  switch (kb) {
-    case 1: return launch_lds<xattn_bwd_kernel<1>>(grid, lds, s, p, upw);
-    case 2: return launch_lds<xattn_bwd_kernel<2>>(grid, lds, s, p, upw);
-    case 3: return launch_lds<xattn_bwd_kernel<3>>(grid, lds, s, p, upw);
-    default: return launch_lds<xattn_bwd_kernel<4>>(grid, lds, s, p, upw);
-  }
-}
-template <int KB>                                                  // v2 / v3 exist for 2 and 3 key blocks (33..96 keys)
-static int launch_xattn_bwd23(bool v3, dim3 grid, hipStream_t s, const AttnP& p, int upw) {
-  constexpr int lds2 = 4 * TILE_BYTES + 2 * (2 * TILE_BYTES + 512) + 2 * 32 * 144;
-  constexpr int lds3 = 2 * (TILE_BYTES + TILE_BYTES / 2) + 2 * (2 * TILE_BYTES + 512) + 2 * (TILE_BYTES + 2048);
-  if (v3) return p.q_prescaled ? launch_lds<xattn_bwd3_kernel<KB, true>>(grid, lds3, s, p, upw)
-                               : launch_lds<xattn_bwd3_kernel<KB, false>>(grid, lds3, s, p, upw);
-  return p.q_prescaled ? launch_lds<xattn_bwd2_kernel<KB, true>>(grid, lds2, s, p, upw)
-                       : launch_lds<xattn_bwd2_kernel<KB, false>>(grid, lds2, s, p, upw);
-}
-// the ordered sum of the query-range splits' fp32 dK / dV partials, behind whichever kernel wrote them
-static void launch_dkv_reduce(const AttnP& p, int nd, hipStream_t s) {
-  const long long total = (long long)p.B * p.H * p.Skv * 2 * 16 * nd;
-  hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, p);
-}
-
-template <int ND>
-static int attn_fwd_nd(const AttnP& p, hipStream_t s) {
-  const dim3 grid(cdiv(p.Sq, 128), p.H, p.B);
-  constexpr int lq = 2 * 2 * ND * TILE_BYTES;
-  if constexpr (ND == 1) {
-    // cross-attention: K / V resident.  With a second key set (attn_check_ip has passed) always, at any query count: there
-    // is no other kernel for it
-    if (p.K2 || (g_attn_xattn && g_attn_use_tr && p.Skv <= 128 && !p.causal && !p.bias && p.Sq >= 128)) {
-      const int kb = cdiv(p.Skv, 32), kt = (kb + 1) / 2;
-      const int lds = 2 * kt * TILE_BYTES + 4 * 32 * 144 + 4 * 4096 + (p.K2 ? 2 * 4096 : 0);
-      const int nu = cdiv(p.Sq, 128);
-      const long long units = (long long)p.B * p.H * nu;
-      int upw = (int)((units + 511) / 512);                       // one round of two workgroups per CU (66 KB of LDS each, 74 KB with image keys)
-      upw = upw < 1 ? 1 : (upw > nu ? nu : upw);
-      const dim3 xgrid(cdiv(nu, upw), p.H, p.B);
-      if (p.K2 && p.nset) return launch_xattn_fwd<true, true>(kb, xgrid, lds, s, p, upw);
-      return p.K2 ? launch_xattn_fwd<true>(kb, xgrid, lds, s, p, upw) : launch_xattn_fwd(kb, xgrid, lds, s, p, upw);
-    }
-  }
-  if (p.causal || p.kv_len || p.bias) {       // text-encoder masks / score bias: separate instance (head_dim 64 only)
-    SHAPECHK(ND == 1, "attention: causal / key-length masks need head_dim 64");
-    if constexpr (ND == 1) return launch_lds<attn_q_kernel<0, true, 1, true>>(grid, lq, s, p);
-    return PEA_OK;
-  }
-  return ATTN_DISPATCH((attn_q_kernel<0, true, ND>), (attn_q_kernel<0, false, ND>), grid, lq);
-}
-static int g_attn_fused_bwd = getenv("PEA_ATTN_BWD_SPLIT") ? 0 : 1;      // PEA_ATTN_BWD_SPLIT=1: the two-launch form (A/B)
-// the one-pass cross-attention backward: head_dim 64, at most 128 keys, all three gradients wanted
-static bool attn_use_xattn(const AttnP& p) {
-  return g_attn_xattn && g_attn_use_tr && p.nd == 1 && p.Skv <= 128 && p.dQ && p.dK && p.dV && (p.nsplit <= 1 || p.dkv_part);
-}
-extern "C" void pea_debug_set_attn_fused_bwd(int v) { g_attn_fused_bwd = v; }
-template <int ND>
-static int attn_bwd_nd(const AttnP& p, hipStream_t s) {
-  const int ns = p.nsplit > 1 ? p.nsplit : 1;
-  constexpr int lq = 2 * 2 * ND * TILE_BYTES, lk = 2 * (2 * ND * TILE_BYTES + 512);
-  int rc = PEA_OK;
-  if constexpr (ND == 1) {
-    if (attn_use_xattn(p)) {
-      const dim3 grid(ns, p.H, p.B);
-      const int kb = cdiv(p.Skv, 32);
-      if (xattn_v2_keys(p.Skv)) {                                  // v2 or v3: 64-query units
-        const int upw = cdiv(cdiv(p.Sq, 64), ns);
-        rc = kb == 2 ? launch_xattn_bwd23<2>(xattn_v3_keys(p.Skv), grid, s, p, upw)
-                     : launch_xattn_bwd23<3>(xattn_v3_keys(p.Skv), grid, s, p, upw);
-      } else {                                                     // v1: 128-query units
-        rc = launch_xattn_bwd1(kb, grid, s, p, cdiv(cdiv(p.Sq, 128), ns));
-      }
-      if (rc) return rc;
-      if (p.nsplit > 1) launch_dkv_reduce(p, 1, s);
-      return PEA_OK;
-    }
-  }
-  if (p.dQ && p.dK && p.dV && g_attn_fused_bwd) {
-    const int n_dq = cdiv(p.Sq, 128) * ND, n_dkv = cdiv(p.Skv, 128) * ns * ND;
-    const dim3 grid((unsigned)((n_dq + n_dkv) * p.H * p.B));
-    rc = ATTN_DISPATCH((attn_bwd_fused_kernel<true, ND>), (attn_bwd_fused_kernel<false, ND>), grid, lk, n_dq, n_dkv);
-    if (rc) return rc;
-    if (p.nsplit > 1) launch_dkv_reduce(p, ND, s);
-    return PEA_OK;
-  }
-  if (p.dQ) {
-    rc = ATTN_DISPATCH((attn_q_kernel<1, true, ND>), (attn_q_kernel<1, false, ND>), dim3(cdiv(p.Sq, 128) * ND, p.H, p.B), lq);
-    if (rc) return rc;
-  }
-  if (p.dK && p.dV) {
-    rc = ATTN_DISPATCH((attn_dkv_kernel<true, ND>), (attn_dkv_kernel<false, ND>), dim3(cdiv(p.Skv, 128) * ns * ND, p.H, p.B), lk);
-    if (rc) return rc;
-    if (p.nsplit > 1) launch_dkv_reduce(p, ND, s);
-  }
-  return PEA_OK;
-}
-
-int launch_attention_fwd(const AttnP& p0, hipStream_t s) {
-  AttnP p = p0;
-  if (p.nd == 0) p.nd = 1;
-  int rc = attn_check(p);
-  if (rc) return rc;
-  SHAPECHK(p.ldo % 4 == 0, "attention: ldo %% 4");
-  if (p.K2 || p.V2) {
-    rc = attn_check_ip(p);
-    if (rc) return rc;
-    SHAPECHK(p.k2_brows == 0 || p.k2_brows >= p.Skv2, "attention: %d image key rows per sample hold no %d keys", p.k2_brows, p.Skv2);
-    if (!p.k2_brows) p.k2_brows = p.Skv2;
-    attn_resolve_sets(p);
-  }
-  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = p.nd; }
-  const int keys = p.Skv + (p.K2 ? p.Skv2 : 0);                    // both key sets: one more score / value product each
-  PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * keys * 64 * p.nd, 2.0 * p.B * p.H * 64 * p.nd * (2.0 * p.Sq + 2.0 * keys), s);
-  rc = p.nd == 1 ? attn_fwd_nd<1>(p, s) : p.nd == 2 ? attn_fwd_nd<2>(p, s) : attn_fwd_nd<3>(p, s);
-  PROF_END(s);
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  return PEA_OK;
-}
-
 // at most 32 queries over one softmax of two key sets (attn_fewq_kernel); AttnP::K2 / V2 / Skv2 are the second SET here, not
 // a second softmax.  Everything outside the kernel's shape is refused before any launch.
-int launch_attention_fwd_fewq(const AttnP& p, hipStream_t s) {
+static int attn_plan_fewq(const AttnP& p, AttnPlan& plan) {
   SHAPECHK(p.B > 0 && p.B <= 65535 && p.H > 0 && p.Sq >= 1 && p.Skv >= 1, "attention_fewq: empty problem (B=%d H=%d Sq=%d Skv=%d)", p.B, p.H, p.Sq, p.Skv);
   SHAPECHK(p.Sq <= 32, "attention_fewq: at most 32 queries (Sq=%d); larger counts belong to pea_op_attention_fwd", p.Sq);
   SHAPECHK(p.nd == 1, "attention_fewq: head_dim 64 only (nd=%d)", p.nd);
@@ -2722,38 +2585,132 @@ int launch_attention_fwd_fewq(const AttnP& p, hipStream_t s) {
   const unsigned long long in_bits = (unsigned long long)p.Q | (unsigned long long)p.K | (unsigned long long)p.V |
                                      (unsigned long long)p.K2 | (unsigned long long)p.V2;
   SHAPECHK(in_bits % 16 == 0 && (unsigned long long)p.O % 8 == 0, "attention_fewq: Q / K / V 16-byte, O 8-byte aligned");
-  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv + p.Skv2; g_prof_tag[3] = 1; }
-  const int keys = p.Skv + p.Skv2;
-  PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * keys * 64, 2.0 * p.B * p.H * 64 * (2.0 * p.Sq + 2.0 * keys), s);
-  const int rc = launch_lds<attn_fewq_kernel>(dim3(p.H, p.B), 4 * FEWQ_WAVE_BYTES + 4096, s, p);
+  plan.add(AK_FEWQ, dim3(p.H, p.B), 4 * FEWQ_WAVE_BYTES + 4096);   // the one kernel there is: nothing to decide
+  return PEA_OK;
+}
+// all of a call that needs no device: the shape checks, attn_resolve_sets, the decision.  dir: 0 forward, 1 backward, 2 few-query
+static int attn_plan(int dir, AttnP& p, const AttnEnv& e, AttnPlan& plan) {
+  if (dir == 2) return attn_plan_fewq(p, plan);
+  if (p.nd == 0) p.nd = 1;
+  SHAPECHK(p.B > 0 && p.H > 0 && p.Sq > 0 && p.Skv > 0, "attention: empty problem");
+  SHAPECHK(p.nd >= 1 && p.nd <= 3, "attention: padded head_dim must be 64, 128 or 192 (nd=%d)", p.nd);
+  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0, "attention: leading dims must be multiples of 8");
+  if (dir == 1) {
+    // no backward kernel knows a causal mask or a score bias (the text encoders are frozen): unmasked gradients would be wrong
+    SHAPECHK(!p.causal && !p.bias, "attention bwd: no backward with a causal mask or a score bias");
+    SHAPECHK(!p.kv_len || p.nd == 1, "attention bwd: key-length masks need head_dim 64 (nd=%d)", p.nd);
+    SHAPECHK(p.lse && p.delta && p.dO && p.O, "attention bwd: lse/delta/dO/O required");
+    SHAPECHK(p.Sq % 4 == 0, "attention bwd: Sq=%d must be a multiple of 4", p.Sq);
+    const int rc = attn_decide_bwd(p, e, plan);
+    p.nsplit = plan.nsplit;
+    return rc;
+  }
+  SHAPECHK(p.ldo % 4 == 0, "attention: ldo %% 4");
+  if (p.K2 || p.V2) {
+    const int rc = attn_check_ip(p);
+    if (rc) return rc;
+    SHAPECHK(p.k2_brows == 0 || p.k2_brows >= p.Skv2, "attention: %d image key rows per sample hold no %d keys", p.k2_brows, p.Skv2);
+    if (!p.k2_brows) p.k2_brows = p.Skv2;
+    attn_resolve_sets(p);
+  }
+  return attn_decide_fwd(p, e, plan);
+}
+// hipFuncAttributeMaxDynamicSharedMemorySize of kernel K raised to `bytes`, once per process, then the launch: every
+// kernel of this file that takes dynamic LDS goes through here, so no list of instantiations has to be kept by hand.
+// The attribute call belongs to an instantiation's FIRST launch: if that launch is inside a stream capture, the call
+// happens during the capture (it is not a stream operation and is not recorded).
+template <auto K, typename... Args>
+static int launch_lds(dim3 grid, int bytes, hipStream_t s, const Args&... args) {
+  static bool raised = false;
+  if (!raised) {
+    HIPCHK(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    raised = true;
+  }
+  hipLaunchKernelGGL(K, grid, dim3(256), bytes, s, args...);
+  return PEA_OK;
+}
+// enumerator -> instantiation: the one place that names them
+static int attn_launch(const AttnLaunch& l, const AttnP& p, hipStream_t s) {
+#define ATTN_CASE(e, K, ...) case e: return launch_lds<K>(l.grid, l.lds, s, p, ##__VA_ARGS__);
+  switch (l.kernel) {
+    ATTN_CASE(AK_XFWD + 0, (xattn_fwd_kernel<1, false, false>), l.a0) ATTN_CASE(AK_XFWD + 1, (xattn_fwd_kernel<2, false, false>), l.a0)
+    ATTN_CASE(AK_XFWD + 2, (xattn_fwd_kernel<3, false, false>), l.a0) ATTN_CASE(AK_XFWD + 3, (xattn_fwd_kernel<4, false, false>), l.a0)
+    ATTN_CASE(AK_XFWD + 4, (xattn_fwd_kernel<1, true, false>), l.a0) ATTN_CASE(AK_XFWD + 5, (xattn_fwd_kernel<2, true, false>), l.a0)
+    ATTN_CASE(AK_XFWD + 6, (xattn_fwd_kernel<3, true, false>), l.a0) ATTN_CASE(AK_XFWD + 7, (xattn_fwd_kernel<4, true, false>), l.a0)
+    ATTN_CASE(AK_XFWD + 8, (xattn_fwd_kernel<1, true, true>), l.a0) ATTN_CASE(AK_XFWD + 9, (xattn_fwd_kernel<2, true, true>), l.a0)
+    ATTN_CASE(AK_XFWD + 10, (xattn_fwd_kernel<3, true, true>), l.a0) ATTN_CASE(AK_XFWD + 11, (xattn_fwd_kernel<4, true, true>), l.a0)
+    ATTN_CASE(AK_Q + 0, (attn_q_kernel<0, false, 1>)) ATTN_CASE(AK_Q + 1, (attn_q_kernel<0, false, 2>)) ATTN_CASE(AK_Q + 2, (attn_q_kernel<0, false, 3>))
+    ATTN_CASE(AK_Q + 3, (attn_q_kernel<0, true, 1>)) ATTN_CASE(AK_Q + 4, (attn_q_kernel<0, true, 2>)) ATTN_CASE(AK_Q + 5, (attn_q_kernel<0, true, 3>))
+    ATTN_CASE(AK_Q + 6, (attn_q_kernel<1, false, 1>)) ATTN_CASE(AK_Q + 7, (attn_q_kernel<1, false, 2>)) ATTN_CASE(AK_Q + 8, (attn_q_kernel<1, false, 3>))
+    ATTN_CASE(AK_Q + 9, (attn_q_kernel<1, true, 1>)) ATTN_CASE(AK_Q + 10, (attn_q_kernel<1, true, 2>)) ATTN_CASE(AK_Q + 11, (attn_q_kernel<1, true, 3>))
+    ATTN_CASE(AK_Q_TXT, (attn_q_kernel<0, true, 1, true>)) ATTN_CASE(AK_FEWQ, attn_fewq_kernel)
+    ATTN_CASE(AK_DKV + 0, (attn_dkv_kernel<false, 1>)) ATTN_CASE(AK_DKV + 1, (attn_dkv_kernel<false, 2>)) ATTN_CASE(AK_DKV + 2, (attn_dkv_kernel<false, 3>))
+    ATTN_CASE(AK_DKV + 3, (attn_dkv_kernel<true, 1>)) ATTN_CASE(AK_DKV + 4, (attn_dkv_kernel<true, 2>)) ATTN_CASE(AK_DKV + 5, (attn_dkv_kernel<true, 3>))
+    ATTN_CASE(AK_FUSED + 0, (attn_bwd_fused_kernel<false, 1>), l.a0, l.a1) ATTN_CASE(AK_FUSED + 1, (attn_bwd_fused_kernel<false, 2>), l.a0, l.a1)
+    ATTN_CASE(AK_FUSED + 2, (attn_bwd_fused_kernel<false, 3>), l.a0, l.a1) ATTN_CASE(AK_FUSED + 3, (attn_bwd_fused_kernel<true, 1>), l.a0, l.a1)
+    ATTN_CASE(AK_FUSED + 4, (attn_bwd_fused_kernel<true, 2>), l.a0, l.a1) ATTN_CASE(AK_FUSED + 5, (attn_bwd_fused_kernel<true, 3>), l.a0, l.a1)
+    ATTN_CASE(AK_XBWD1 + 0, xattn_bwd_kernel<1>, l.a0) ATTN_CASE(AK_XBWD1 + 1, xattn_bwd_kernel<2>, l.a0)
+    ATTN_CASE(AK_XBWD1 + 2, xattn_bwd_kernel<3>, l.a0) ATTN_CASE(AK_XBWD1 + 3, xattn_bwd_kernel<4>, l.a0)
+    ATTN_CASE(AK_XBWD2 + 0, (xattn_bwd2_kernel<2, false>), l.a0) ATTN_CASE(AK_XBWD2 + 1, (xattn_bwd2_kernel<2, true>), l.a0)
+    ATTN_CASE(AK_XBWD2 + 2, (xattn_bwd2_kernel<3, false>), l.a0) ATTN_CASE(AK_XBWD2 + 3, (xattn_bwd2_kernel<3, true>), l.a0)
+    ATTN_CASE(AK_XBWD3 + 0, (xattn_bwd3_kernel<2, false>), l.a0) ATTN_CASE(AK_XBWD3 + 1, (xattn_bwd3_kernel<2, true>), l.a0)
+    ATTN_CASE(AK_XBWD3 + 2, (xattn_bwd3_kernel<3, false>), l.a0) ATTN_CASE(AK_XBWD3 + 3, (xattn_bwd3_kernel<3, true>), l.a0)
+    case AK_DELTA: hipLaunchKernelGGL(attn_delta_kernel, l.grid, dim3(256), 0, s, p); return PEA_OK;       // (no dynamic LDS)
+    case AK_REDUCE: hipLaunchKernelGGL(attn_dkv_reduce_kernel, l.grid, dim3(256), 0, s, p); return PEA_OK;
+  }
+#undef ATTN_CASE
+  pea_set_error("attention: no kernel for enumerator %d", l.kernel);
+  return PEA_E_SHAPE;
+}
+static int attn_go(int dir, const AttnP& p0, hipStream_t s) {
+  AttnP p = p0;
+  AttnPlan plan;
+  int rc = attn_plan(dir, p, g_attn_env, plan);
+  if (rc) return rc;
+  const int keys = p.Skv + (dir != 1 && p.K2 ? p.Skv2 : 0);        // both key sets: one more score / value product each
+  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = dir == 2 ? keys : p.Skv; g_prof_tag[3] = p.nd; }
+  // algorithmic: 2 products forward, 5 backward (S, dP, dV, dK, dQ) = 10*B*H*Sq*Skv*D flops (the two-kernel form recomputes S and dP)
+  const double w = dir == 1 ? 4.0 : 2.0;
+  PROF_BEGIN(dir == 1 ? 3 : 2, (dir == 1 ? 10.0 : 4.0) * p.B * p.H * (double)p.Sq * keys * 64 * p.nd,
+             2.0 * p.B * p.H * 64 * p.nd * (w * p.Sq + w * keys), s);
+  for (int i = 0; i < plan.n && !rc; ++i) rc = attn_launch(plan.l[i], p, s);
   PROF_END(s);
   if (rc) return rc;
   HIPCHK(hipGetLastError());
   return PEA_OK;
 }
-
-int launch_attention_bwd(const AttnP& p0, hipStream_t s) {
-  AttnP p = p0;
-  if (p.nd == 0) p.nd = 1;
-  p.nsplit = p.dkv_part ? attention_bwd_nsplit(p.B, p.H, p.Sq, p.Skv) : 1;
-  int rc = attn_check(p);
+int launch_attention_fwd(const AttnP& p, hipStream_t s) { return attn_go(0, p, s); }
+int launch_attention_bwd(const AttnP& p, hipStream_t s) { return attn_go(1, p, s); }
+int launch_attention_fwd_fewq(const AttnP& p, hipStream_t s) { return attn_go(2, p, s); }
+// include/pea_hip.h.  Every operand of the problem is a non-null, aligned stand-in; nothing is launched
+extern "C" int pea_debug_attn_dispatch(const int* q, int* out) {
+  const int dir = q[0], feat = q[6];
+  if (dir < 0 || dir > 2) return q[1] >= 0 && q[1] < AK_COUNT ? q[1] : -1;
+  const AttnEnv e = {q[10] < 0 ? g_attn_env.xattn_ver : q[10], q[11] < 0 ? g_attn_env.use_tr : q[11],
+                     q[12] < 0 ? g_attn_env.xattn : q[12], q[13] < 0 ? g_attn_env.fused_bwd : q[13]};
+  static float page[64];
+  bf16* const any = (bf16*)page;
+  AttnP p = AttnP();
+  p.Q = p.K = p.V = p.dO = any; p.O = any; p.lse = p.delta = page; p.scale = 0.125f;
+  p.B = q[1]; p.H = q[2]; p.Sq = q[3]; p.Skv = q[4]; p.nd = q[5];
+  p.ldq = p.ldk = p.ldv = p.ldo = p.lddo = p.lddq = p.lddk = p.lddv = p.ldk2 = p.ldv2 = 64 * p.H * (p.nd > 0 ? p.nd : 1);
+  p.causal = feat & 1; p.kv_len = feat & 2 ? (const int*)page : nullptr; p.bias = feat & 4 ? page : nullptr; p.q_prescaled = feat >> 3 & 1;
+  if (feat & 16) { p.K2 = p.V2 = any; p.Skv2 = q[7]; p.scale2 = 1.f; p.nset = dir == 2 ? 0 : q[8]; }
+  for (int j = 0; j < p.nset && j < 4; ++j) {                       // the sets share the Skv2 keys evenly; bit j of q[9]: set j has a mask
+    p.set_end[j] = (int)((long long)(j + 1) * p.Skv2 / p.nset);
+    p.set_w[j] = feat & 32 ? 0.f : 1.f;
+    p.set_mask[j] = q[9] >> j & 1 ? page : nullptr;
+  }
+  p.dQ = feat & 64 ? any : nullptr; p.dK = feat & 128 ? any : nullptr; p.dV = feat & 256 ? any : nullptr;
+  p.dkv_part = feat & 512 ? page : nullptr; p.accum_dq = p.accum_dkv = feat >> 10 & 1;
+  AttnPlan plan;
+  const int rc = attn_plan(dir, p, e, plan);
   if (rc) return rc;
-  // no backward kernel knows a causal mask or a score bias (the text encoders are frozen): unmasked gradients would be wrong
-  SHAPECHK(!p.causal && !p.bias, "attention bwd: no backward with a causal mask or a score bias");
-  SHAPECHK(!p.kv_len || p.nd == 1, "attention bwd: key-length masks need head_dim 64 (nd=%d)", p.nd);
-  SHAPECHK(p.lse && p.delta && p.dO && p.O, "attention bwd: lse/delta/dO/O required");
-  SHAPECHK(p.Sq % 4 == 0, "attention bwd: Sq=%d must be a multiple of 4", p.Sq);
-  const long long total = (long long)p.B * p.Sq * p.H * 8;
-  // algorithmic: 5 products (S, dP, dV, dK, dQ) = 10*B*H*Sq*Skv*D flops (the two-kernel form recomputes S and dP)
-  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = p.nd; }
-  PROF_BEGIN(3, 10.0 * p.B * p.H * (double)p.Sq * p.Skv * 64 * p.nd, 2.0 * p.B * p.H * 64 * p.nd * (4.0 * p.Sq + 4.0 * p.Skv), s);
-  // delta: its own (memory-bound) kernel for the fused launch and for dK/dV-only calls; the two-launch form computes it
-  // inside the dQ pass
-  if (!attn_use_xattn(p) && (!p.dQ || (p.dK && p.dV && g_attn_fused_bwd)))
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)cdivl(total, 256 * PEA_ATTN_DELTA_ROWS)), dim3(256), 0, s, p);
-  rc = p.nd == 1 ? attn_bwd_nd<1>(p, s) : p.nd == 2 ? attn_bwd_nd<2>(p, s) : attn_bwd_nd<3>(p, s);
-  PROF_END(s);
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
+  out[0] = plan.n; out[1] = plan.nsplit;
+  for (int i = 0; i < plan.n; ++i) {
+    const AttnLaunch& l = plan.l[i];
+    int* const o = out + 2 + 7 * i;
+    o[0] = l.kernel; o[1] = (int)l.grid.x; o[2] = (int)l.grid.y; o[3] = (int)l.grid.z; o[4] = l.lds; o[5] = l.a0; o[6] = l.a1;
+  }
   return PEA_OK;
 }

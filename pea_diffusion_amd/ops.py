@@ -281,15 +281,20 @@ def gemm_qscale(a, w, bias=None, qscale_cols=0, qscale=1.0):
     return out
 
 
+def _attn_fwd_out(q, heads, scale, want_lse=True):
+    """what every attention forward wrapper starts from -> B, Sq, C, the scale (default head_dim^-0.5), o, lse (or None)"""
+    B, Sq, C = q.shape
+    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
+    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    return B, Sq, C, (scale if scale is not None else (C // heads) ** -0.5), o, lse
+
+
 def attention_fwd(q, k, v, heads, scale=None, q_prescaled=False):
     """q [B,Sq,H*D], k/v [B,Skv,H*D] bf16 (D = 64, 128 or 192: zero-padded heads) -> (o, lse [B,H,Sq]).
     q_prescaled: q already holds (unscaled q) * scale * log2(e)."""
-    B, Sq, C = q.shape
+    B, Sq, C, scale, o, lse = _attn_fwd_out(q, heads, scale)
     Skv = k.shape[1]
     nd = C // heads // 64
-    scale = scale if scale is not None else (C // heads) ** -0.5
-    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
-    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32)
     fn = lib().pea_op_attention_fwd_prescaled if q_prescaled else lib().pea_op_attention_fwd
     check(fn(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, ptr(lse),
                                      B, heads, Sq, Skv, scale, nd, stream_ptr()))
@@ -302,10 +307,7 @@ def attention_fwd_ip(q, k, v, k_ip, v_ip, heads, ip_scale, scale=None, q_prescal
     softmax(scale q k^T) v + ip_scale * softmax(scale q k_ip^T) v_ip, head_dim 64.  q [B,Sq,H*64], k/v [B,Skv<=128,H*64],
     k_ip/v_ip [B,N<=32,>=H*64] bf16; kv_len (int32 [B]) masks text keys only; the lse is the text softmax's.
     -> o, or (o, lse [B,H,Sq]) with want_lse.  causal=True exists to be refused."""
-    B, Sq, C = q.shape
-    scale = scale if scale is not None else (C // heads) ** -0.5
-    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
-    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    B, Sq, C, scale, o, lse = _attn_fwd_out(q, heads, scale, want_lse)
     check(lib().pea_op_attention_fwd_ip(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(k_ip), k_ip.stride(1),
                                         ptr(v_ip), v_ip.stride(1), ptr(o), C, ptr(lse), B, heads, Sq, k.shape[1], k_ip.shape[1],
                                         scale, float(ip_scale), int(q_prescaled), int(causal), ptr(kv_len), stream_ptr()))
@@ -344,11 +346,8 @@ def attention_fwd_ipn(q, k, v, k2, v2, heads, n_keys, scales, masks=None, scale=
     sum(n_keys[:j]) .. + n_keys[j].  masks: None, or per set None / fp32 [1,Sq] (shared by the batch) / [B,Sq], any finite
     values.  kv_len (int32 [B]) masks text keys only; the lse is the text softmax's.  -> o, or (o, lse [B,H,Sq]) with want_lse.
     causal=True and mask_strides (the batch stride handed over instead of the tensor's) exist to be refused."""
-    B, Sq, C = q.shape
-    scale = scale if scale is not None else (C // heads) ** -0.5
     sets = ip_sets(n_keys, scales, masks, mask_strides)
-    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
-    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    B, Sq, C, scale, o, lse = _attn_fwd_out(q, heads, scale, want_lse)
     check(lib().pea_op_attention_fwd_ipn(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(k2), k2.stride(1),
                                          ptr(v2), v2.stride(1), ptr(o), C, ptr(lse), B, heads, Sq, k.shape[1], ctypes.byref(sets),
                                          scale, int(q_prescaled), int(causal), ptr(kv_len), stream_ptr()))
@@ -361,12 +360,9 @@ def attention_fwd_fewq(q, k, v, k2=None, v2=None, heads=1, scale=None, q_prescal
     softmax(scale [q k^T | q k2^T]) [v ; v2], ONE softmax, head_dim 64.  q [B,Sq<=32,H*64], k/v [B,Skv,>=H*64], k2/v2
     [B,N<=32,>=H*64] bf16 or both None.  kv_rows / kv2_rows: use only the first so many rows of each sample of k, v / k2, v2
     (buffers with rows to spare: the batch stride stays that of the tensor only for B == 1).  -> o, or (o, lse [B,H,Sq])."""
-    B, Sq, C = q.shape
-    scale = scale if scale is not None else 0.125
+    B, Sq, C, scale, o, lse = _attn_fwd_out(q, heads, scale if scale is not None else 0.125, want_lse)
     Skv = k.shape[1] if kv_rows is None else kv_rows
     Skv2 = 0 if k2 is None else (k2.shape[1] if kv2_rows is None else kv2_rows)
-    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
-    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
     check(lib().pea_op_attention_fwd_fewq(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(k2),
                                           0 if k2 is None else k2.stride(1), ptr(v2), 0 if v2 is None else v2.stride(1), ptr(o), C,
                                           ptr(lse), B, heads, Sq, Skv, Skv2, scale, C // heads // 64, int(q_prescaled), stream_ptr()))
@@ -376,11 +372,8 @@ def attention_fwd_fewq(q, k, v, k2=None, v2=None, heads=1, scale=None, q_prescal
 def attention_fwd_masked(q, k, v, heads, causal=False, kv_len=None, scale=None, want_lse=False):
     """text-encoder attention: head_dim 64, optional causal mask and per-sample key counts (int32 [B])
     -> o, or (o, lse [B,H,Sq]) with want_lse"""
-    B, Sq, C = q.shape
+    B, Sq, C, scale, o, lse = _attn_fwd_out(q, heads, scale, want_lse)
     Skv = k.shape[1]
-    scale = scale if scale is not None else (C // heads) ** -0.5
-    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
-    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
     check(lib().pea_op_attention_fwd_masked(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, ptr(lse),
                                             B, heads, Sq, Skv, scale, int(causal), ptr(kv_len), stream_ptr()))
     return (o, lse) if want_lse else o
@@ -397,12 +390,10 @@ def attention_fwd_text(q, k, v, heads, scale=None, q_prescaled=False, causal=Fal
     batch -- the columns past Skv are read but never used.  -> (o, lse [B,H,Sq]), or o alone without want_lse."""
     B, Sq, C = q.shape
     Skv = k.shape[1]
-    scale = scale if scale is not None else (C // heads) ** -0.5
     if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (heads, Sq, attention_bias_pitch(Skv))
                              or not bias.is_contiguous()):
         raise PeaError(f"attention_fwd_text: bias must be contiguous fp32 [{heads}, {Sq}, {attention_bias_pitch(Skv)}]")
-    o = torch.empty(B, Sq, C, device=q.device, dtype=BF)
-    lse = torch.empty(B, heads, Sq, device=q.device, dtype=torch.float32) if want_lse else None
+    B, Sq, C, scale, o, lse = _attn_fwd_out(q, heads, scale, want_lse)
     check(lib().pea_op_attention_fwd_text(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, ptr(lse),
                                           B, heads, Sq, Skv, scale, int(q_prescaled), int(causal), ptr(kv_len), ptr(bias),
                                           stream_ptr()))

@@ -60,7 +60,7 @@ def softmax_peak(q, k, H, scale, kv_len=None):
 
 
 # ---------------------------------------------------------------------------------------------- forward cases
-# kernel: which forward launch_attention_fwd picks (attention.hip, attn_fwd_nd): the resident-key kernel xattn_fwd_kernel needs no
+# kernel: which forward launch_attention_fwd picks (attention.hip, attn_decide_fwd): the resident-key kernel xattn_fwd_kernel needs no
 # causal mask, no bias, Sq >= 128 and Skv <= 128; everything else that is masked or biased runs attn_q_kernel<0, true, 1, true>
 FWD_CASES = [
     dict(id="xattn-3blocks", kernel="xattn", B=4, H=2, Sq=200, Skv=77, kv_len=[77, 33, 32, 1]),
@@ -119,15 +119,16 @@ def padded_log2_bias(bias_nat):
 
 
 # ---------------------------------------------------------------------------------------------- backward cases
-# A form is (one-pass kernel selector for pea_debug_set_xattn_bwd_v2 or None, fused single launch, scratch passed, gradients).
-# kernel: what launch_attention_bwd picks for it (attention.hip, attn_bwd_nd / attention_bwd_nsplit):
+# A form is (one-pass kernel selector for pea_debug_set_xattn_bwd_v2 or None, fused single launch, scratch passed, gradients,
+# transpose reads or pea_debug_set_attn_tr(0)).
+# kernel: what launch_attention_bwd picks for it (attention.hip, attn_decide_bwd / attention_bwd_nsplit):
 #   <= 128 keys and all three gradients -> one-pass: selector 3 = xattn_bwd3_kernel for 33..80 keys, xattn_bwd2_kernel for 81..96,
 #   xattn_bwd_kernel otherwise; 2 = xattn_bwd2_kernel for 33..96; 0 = xattn_bwd_kernel.  With the scratch and Sq >= 512 they write
 #   fp32 partials per query split and attn_dkv_reduce_kernel sums them.
 #   > 128 keys -> attn_bwd_fused_kernel (attn_q_body + attn_dkv_body in one grid), or attn_q_kernel<1> then attn_dkv_kernel.
 #   dK/dV only -> attn_delta_kernel + attn_dkv_kernel (+ reduce with the scratch); dQ only -> attn_q_kernel<1>.
-def _form(id, kernel, ver=None, fused=1, scratch=False, grads="all"):
-    return dict(id=id, kernel=kernel, ver=ver, fused=fused, scratch=scratch, grads=grads)
+def _form(id, kernel, ver=None, fused=1, scratch=False, grads="all", tr=1):
+    return dict(id=id, kernel=kernel, ver=ver, fused=fused, scratch=scratch, grads=grads, tr=tr)
 
 
 _ONE_PASS_77 = [("v3", "xattn_bwd3", 3), ("v2", "xattn_bwd2", 2), ("v1", "xattn_bwd", 0)]
@@ -142,7 +143,8 @@ BWD_CASES = [
     dict(id="x128", B=4, H=2, Sq=260, Skv=128, kv_len=[128, 97, 96, 32], forms=[_form("v1", "xattn_bwd", ver=3)]),
     dict(id="x20", B=2, H=2, Sq=260, Skv=20, kv_len=[20, 3], forms=[_form("v1", "xattn_bwd", ver=3)]),
     dict(id="g200", B=4, H=2, Sq=260, Skv=200, kv_len=[200, 129, 128, 65],
-         forms=[_form("fused", "general-fused", fused=1), _form("two-launch", "general-split", fused=0)]),
+         forms=[_form("fused", "general-fused", fused=1), _form("two-launch", "general-split", fused=0),
+                _form("two-launch-gather", "general-split", fused=0, tr=0)]),      # (tr=0: pea_debug_set_attn_tr, the gathering instances)
     dict(id="first-layer", B=4, H=2, Sq=520, Skv=77, kv_len=[77, 64, 33, 1],
          forms=[_form("dkv-scratch", "dkv", scratch=True, grads="dkv"), _form("dkv-null", "dkv", grads="dkv"),
                 _form("dq", "dq", grads="dq")]),
@@ -151,7 +153,7 @@ BWD_PARAMS = [(c, f) for c in BWD_CASES for f in c["forms"]]
 
 
 def one_pass_kernel(ver, Skv):
-    """the one-pass kernel pea_debug_set_xattn_bwd_v2(ver) selects at Skv <= 128 keys (xattn_v2_keys / xattn_v3_keys)"""
+    """the one-pass kernel pea_debug_set_xattn_bwd_v2(ver) selects at Skv <= 128 keys (attn_decide_bwd)"""
     if ver not in (0, 2) and 32 < Skv <= 80:
         return "xattn_bwd3"
     if ver != 0 and 32 < Skv <= 96:

@@ -155,6 +155,7 @@ def test_attention_bwd_kv_len(ops, case, form, prescaled):
         if form["ver"] is not None:
             L.pea_debug_set_xattn_bwd_v2(form["ver"])
         L.pea_debug_set_attn_fused_bwd(form["fused"])
+        L.pea_debug_set_attn_tr(form["tr"])
         # ---- write form, twice
         cv = _run_bwd(L, case, form, prescaled, dev, o, lse, kv, accum=0)
         cv2 = _run_bwd(L, case, form, prescaled, dev, o, lse, kv, accum=0)
@@ -188,6 +189,7 @@ def test_attention_bwd_kv_len(ops, case, form, prescaled):
     finally:
         L.pea_debug_set_xattn_bwd_v2(3)
         L.pea_debug_set_attn_fused_bwd(1)
+        L.pea_debug_set_attn_tr(1)
 
 
 @pytest.mark.parametrize("prescaled", [False, True])

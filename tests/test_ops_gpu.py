@@ -668,9 +668,15 @@ def test_adamw(ops):
     close_f32("adamw", wd, p.detach(), rtol=1e-4, atol=1e-6)
 
 
-@pytest.mark.parametrize("d,H,Sq,Skv", [(40, 8, 256, 256), (80, 4, 128, 77), (160, 2, 64, 64), (128, 2, 192, 200), (16, 8, 64, 20)])
-def test_attention_padded_heads(ops, d, H, Sq, Skv):
+PADDED_HEADS = [(40, 8, 256, 256, 1), (80, 4, 128, 77, 1), (160, 2, 64, 64, 1), (128, 2, 192, 200, 1), (16, 8, 64, 20, 1),
+                # the gathering instances (pea_debug_set_attn_tr(0)) at 128 and 192 columns: forward, fused and two-launch backward
+                (80, 2, 192, 200, 0), (160, 1, 192, 200, 0)]
+
+
+@pytest.mark.parametrize("d,H,Sq,Skv,use_tr", PADDED_HEADS, ids=[f"{d}-{H}-{Sq}-{Skv}" + ("" if tr else "-gather") for d, H, Sq, Skv, tr in PADDED_HEADS])
+def test_attention_padded_heads(ops, d, H, Sq, Skv, use_tr):
     """SD1.5 head widths (40 / 80 / 160) are stored zero-padded to 64 / 128 / 192 columns; scale = d^-0.5"""
+    from pea_diffusion_amd._lib import lib
     B = 2
     dp = (d + 63) // 64 * 64
     def padded(x):                       # [B,S,H,d] -> [B,S,H*dp] with zero padding
@@ -681,18 +687,25 @@ def test_attention_padded_heads(ops, d, H, Sq, Skv):
     qr, kr, vr = [t_.float().requires_grad_(True) for t_ in (q, k, v)]
     s = torch.einsum("bqhd,bkhd->bhqk", qr, kr) * d ** -0.5
     oref = torch.einsum("bhqk,bkhd->bqhd", torch.softmax(s, -1), vr)
-    o, lse = ops.attention_fwd(padded(q).cuda(), padded(k).cuda(), padded(v).cuda(), H, scale=d ** -0.5)
-    og = o.float().cpu().view(B, Sq, H, dp)
-    close_bf16(f"attn d{d} O", og[..., :d], oref, ulps=2.0)
-    assert d == dp or og[..., d:].abs().max() == 0
-    close_f32(f"attn d{d} lse", lse, torch.logsumexp(s, -1), rtol=1e-3, atol=2e-3)
-    oref.backward(do.float())
-    dq, dk, dv = ops.attention_bwd(padded(q).cuda(), padded(k).cuda(), padded(v).cuda(), o, padded(do).cuda(), lse, H,
-                                   scale=d ** -0.5)
-    for name, g, r, S in (("dQ", dq, qr.grad, Sq), ("dK", dk, kr.grad, Skv), ("dV", dv, vr.grad, Skv)):
-        gg = g.float().cpu().view(B, S, H, dp)
-        close_bf16(f"attn d{d} {name}", gg[..., :d], r, ulps=4.0)
-        assert d == dp or gg[..., d:].abs().max() == 0
+    lib().pea_debug_set_attn_tr(use_tr)
+    try:
+        o, lse = ops.attention_fwd(padded(q).cuda(), padded(k).cuda(), padded(v).cuda(), H, scale=d ** -0.5)
+        og = o.float().cpu().view(B, Sq, H, dp)
+        close_bf16(f"attn d{d} O", og[..., :d], oref, ulps=2.0)
+        assert d == dp or og[..., d:].abs().max() == 0
+        close_f32(f"attn d{d} lse", lse, torch.logsumexp(s, -1), rtol=1e-3, atol=2e-3)
+        oref.backward(do.float())
+        for fused in ((1,) if use_tr else (1, 0)):
+            lib().pea_debug_set_attn_fused_bwd(fused)
+            dq, dk, dv = ops.attention_bwd(padded(q).cuda(), padded(k).cuda(), padded(v).cuda(), o, padded(do).cuda(), lse, H,
+                                           scale=d ** -0.5)
+            for name, g, r, S in (("dQ", dq, qr.grad, Sq), ("dK", dk, kr.grad, Skv), ("dV", dv, vr.grad, Skv)):
+                gg = g.float().cpu().view(B, S, H, dp)
+                close_bf16(f"attn d{d} fused{fused} {name}", gg[..., :d], r, ulps=4.0)
+                assert d == dp or gg[..., d:].abs().max() == 0
+    finally:
+        lib().pea_debug_set_attn_tr(1)
+        lib().pea_debug_set_attn_fused_bwd(1)
 
 
 @pytest.mark.parametrize("B,H,S,causal,padded", [(2, 2, 77, True, False), (3, 4, 52, False, True), (2, 3, 200, True, True),
