@@ -821,6 +821,34 @@ void pea_debug_set_gemm_debug(int v);
  * [p, p + bytes) behind their last K-step (the product's tapes set the next launch's weight matrix themselves: GemmP::pf_ptr) */
 void pea_debug_set_gemm_prefetch(const void* p, long long bytes);
 
+/* ---- regional text prompts ("regional prompter" / "attention couple"): every region of the picture its own text prompt.
+ * pea_op_attention_fwd_regions: O[b][q] = sum_r w[b][r][q] softmax(scale Q K_r^T) V_r, r < R, in ONE launch, forward only, head_dim
+ * 64.  K / V: bf16 [B][R * Lr][ldk / ldv], region r in rows r Lr .. (r + 1) Lr of every sample -- what a context of R prompts of Lr
+ * tokens leaves in a K|V projection.  1 <= R <= 4, 1 <= Lr <= 96, any Sq >= 1.  w: device fp32 [Bw][R][Sq], Bw 1 (shared by the
+ * batch) or B; any finite values, NOT normalised by the kernel (pea_diffusion_amd/regional.py: region_weights makes them sum to
+ * 1 per query).  Every region has a softmax of its own (own maximum, own sum).  A region whose weight is 0 on all 32 queries of
+ * a wave is skipped by that wave (contribution exactly zero); one-hot weights on region r give the bits of pea_op_attention_fwd
+ * on that region's rows; queries whose weights are all 0 come out as zeros.  No atomics: the same bits every run.  ld* and
+ * alignment as for pea_op_attention_fwd_ip (multiples of 8 holding every head, ldo a multiple of 4; Q / K / V 16-byte, O 8-byte
+ * aligned).  Every refusal is PEA_E_SHAPE before any launch. */
+int pea_op_attention_fwd_regions(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H,
+                                 int Sq, int R, int Lr, const float* w, int Bw, float scale, int q_prescaled, void* stream);
+/* The same in a UNet context (graph 0, inference) whose context length is L = R * Lr: while regions are set, every cross-attention
+ * layer runs ONE launch of pea_op_attention_fwd_regions over its columns of the stacked K|V projection, with the weights of its own
+ * query count.  pea_unet_set_prompt_regions sets the weights of ONE query count (device fp32 [Bw][R][Sq], copied into a buffer
+ * outside the arenas; Sq one of pea_unet_ip_query_counts); R must be the same in every call until pea_unet_clear_prompt_regions.
+ * A forward then needs weights for every count of pea_unet_ip_query_counts, L % R == 0 and L / R <= 96 (PEA_E_STATE / PEA_E_SHAPE
+ * before the first launch).  PEA_E_STATE: a PEA_UNET_GRAD context, live image prompts (pea_unet_ip_set_tokens), per-sample context
+ * lengths.  After pea_unet_clear_prompt_regions a forward gives the bits it gave before.  The tape, the plans and the arenas do
+ * not change; pooled embeds and time ids stay the caller's. */
+int pea_unet_set_prompt_regions(void* unet, int R, int Sq, const float* w, int Bw, void* stream);
+int pea_unet_clear_prompt_regions(void* unet);
+/* Test aid, needs no device: what pea_op_attention_fwd_regions launches (shape checks included).  q[8] = { B, H, Sq, R, Lr, nd,
+ * ldk (<= 0: 64 H, like every other leading dimension), Bw (<= 0: 1) }.  Returns PEA_OK and out[6] = { KB (the instantiation
+ * xattn_regions_fwd_kernel<KB>), grid x / y / z, dynamic LDS bytes, 128-query units per workgroup }, or the error code of a
+ * refused problem.  LDS = R KB 2 4096 + 4 4096 + 4 4096 bytes (keys and values, the O images, the Q images). */
+int pea_debug_attn_regions_dispatch(const int* q, int* out);
+
 #ifdef __cplusplus
 }
 #endif

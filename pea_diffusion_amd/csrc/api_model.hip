@@ -657,6 +657,48 @@ int pea_unet_ip_set_mask(void* h, int set, int Sq, const float* mask, int Bm, vo
   HIPCHK(hipMemcpyAsync(it->second.first, mask, (size_t)Bm * Sq * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return PEA_OK;
 }
+// ------------------------------------------------------------------------------ regional text prompts
+int pea_unet_set_prompt_regions(void* h, int R, int Sq, const float* w, int Bw, void* stream) {
+  NOTNULL(h, "pea_unet_set_prompt_regions");
+  Tape* u = (Tape*)h;
+  if (u->graph != 0 || u->t_kvall < 0) { pea_set_error("pea_unet_set_prompt_regions: not a UNet handle (ControlNet graphs keep one prompt)"); return PEA_E_INVALID; }
+  if (!w) { pea_set_error("pea_unet_set_prompt_regions: null weights"); return PEA_E_INVALID; }
+  RCX(u->regions_check(R, false));
+  SHAPECHK(!u->regions || u->regions->R == R, "pea_unet_set_prompt_regions: R=%d, but weights for %d regions are set (pea_unet_clear_prompt_regions)",
+           R, u->regions ? u->regions->R : 0);
+  std::vector<int> c;
+  ip_query_counts(*u, c);
+  if (std::find(c.begin(), c.end(), Sq) == c.end()) {
+    pea_set_error("pea_unet_set_prompt_regions: no cross-attention layer of this context has %d queries (pea_unet_ip_query_counts)", Sq);
+    return PEA_E_SHAPE;
+  }
+  SHAPECHK(Bw == 1 || Bw == u->B, "pea_unet_set_prompt_regions: Bw=%d (1, or the context's batch %d)", Bw, u->B);
+  if (!u->regions) { u->regions = new Tape::RegionState(); u->regions->R = R; }
+  auto& tab = u->regions->w;
+  auto it = tab.find(Sq);
+  if (it != tab.end() && it->second.second != Bw) {
+    HIPCHK(hipDeviceSynchronize());                  // a queued forward may still read it
+    (void)hipFree(it->second.first);
+    tab.erase(it);
+    it = tab.end();
+  }
+  const size_t bytes = (size_t)Bw * R * Sq * sizeof(float);
+  if (it == tab.end()) {
+    float* buf = nullptr;
+    HIPCHK(hipMalloc((void**)&buf, bytes));
+    it = tab.emplace(Sq, std::make_pair(buf, Bw)).first;
+  }
+  HIPCHK(hipMemcpyAsync(it->second.first, w, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return PEA_OK;
+}
+int pea_unet_clear_prompt_regions(void* h) {
+  NOTNULL(h, "pea_unet_clear_prompt_regions");
+  Tape* u = (Tape*)h;
+  if (u->regions) HIPCHK(hipDeviceSynchronize());    // a queued forward may still read the weights
+  delete u->regions;
+  u->regions = nullptr;
+  return PEA_OK;
+}
 int pea_unet_ip_clear_set(void* h, int set) {
   IP_SET(h, set, "pea_unet_ip_clear");
   e.live = false;

@@ -305,6 +305,14 @@ int pea_op_attention_fwd_ipn(const void* Q, int ldq, const void* K, int ldk, con
   p.Skv2 = total;
   return launch_attention_fwd(p, (hipStream_t)stream);
 }
+int pea_op_attention_fwd_regions(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H,
+                                 int Sq, int R, int Lr, const float* w, int Bw, float scale, int q_prescaled, void* stream) {
+  AttnRegionsP p = AttnRegionsP();
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+  p.B = B; p.H = H; p.Sq = Sq; p.R = R; p.Lr = Lr; p.w = w; p.Bw = Bw; p.scale = scale; p.q_prescaled = q_prescaled; p.nd = 1;
+  return launch_attention_fwd_regions(p, (hipStream_t)stream);
+}
 int pea_op_attention_fwd_fewq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                               const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                               float scale, int nd, int q_prescaled, void* stream) {

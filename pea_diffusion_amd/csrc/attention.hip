@@ -1220,6 +1220,165 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
   }
 }
 
+// ============================================================================= regional text prompts
+// O[b][q] = sum_r w[b][r][q] softmax(s Q K_r^T) V_r over R <= 4 key sets ("regions") of Lr <= 96 keys each that lie back to back
+// in ONE K / V buffer [B][R * Lr][ld]: what a UNet context of R * 77 rows leaves in its stacked K|V projection.  Unfused that is
+// R launches of xattn_fwd_kernel and R weighted adds: Q read R times, O written and re-read R times, in a kernel whose output
+// is most of its traffic.  Here a workgroup stages all R regions once, each padded to KB = ceil(Lr / 32) whole 32-key blocks
+// (half tiles of 4 096 bytes, region r at r * KB * 8 192: its K blocks, then its V blocks), and a wave walks the regions on
+// its resident Q fragments: S^T over the region's blocks, a one-shot softmax with the region's OWN maximum and sum (a spike in
+// one region cannot underflow another), P rounded to bf16 un-normalised exactly as xattn_fwd_kernel rounds it, O_r^T = V_r^T
+// P^T, and one fmaf per element by w / sum into a running fp32 total: 32 more VGPRs whatever R is.  O is rounded once.
+// LDS: R x KB x 8 192 bytes of keys and values, four O images and four Q images of 4 096 bytes each: 81 920 bytes for two regions
+// of 77 keys, which is exactly two workgroups per CU, 131 072 at the maximum of twelve blocks.  The O image is XOR-swizzled at a
+// 128-byte pitch for that reason: padded to 144 bytes per row as in xattn_fwd_kernel the two-region launch took 83 968 bytes and
+// ran one workgroup per CU (same bits; 9.11 -> 8.64 us at 10 heads x 4096 queries, 8.36 -> 7.21 us at 20 x 1024, the other
+// region counts unchanged: profiles/EXPERIMENTS.md section 9, f9).  Its 8-byte writes conflict two ways in either layout.
+// Every block goes through a descriptor that starts at the block's first row and ends with the region's last (as the blocks
+// of attn_fewq_kernel do), so no row of the next region, the next sample or anything behind the buffer is read: such slots
+// arrive as zeros and score -inf.
+// Skipping: a region whose weight is 0 on every valid query of a wave's 32 (a wave-uniform vote) costs that wave nothing -- both
+// products skipped, contribution exactly zero; with disjoint regions a wave's queries are a short run of one latent row and lie
+// in one or two regions.  A wave with nothing left writes zeros.  One-hot weights on region r therefore give the bits of
+// xattn_fwd_kernel on that region's rows (fmaf(o, 1 / sum, 0) is o * (1 / sum)).  The weights are not normalised here, any
+// finite value goes; rows at or past Sq are never read.  No atomics: the same bits every run.
+template <int KB>
+__global__ __launch_bounds__(256, 2) void xattn_regions_fwd_kernel(const AttnRegionsP p, int upw) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int RB = KB * 2 * 4096;                              // bytes of a region: KB key blocks, then KB value blocks
+  char* const Osm = smem + p.R * RB;                             // 4 waves x 32 rows x 128 bytes, then the 4 Q images
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int frow = lane & 31, fh = lane >> 5;
+  int split, head, b;
+  attn_block_coords(split, head, b);
+  const int nu = (p.Sq + 127) >> 7;
+  const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
+  const float c = p.q_prescaled ? 1.f : p.scale * LOG2E;
+  const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq + head * 64;
+  {                                                              // waves 0 / 1: the 32 rows of every K block, waves 2 / 3: of every V block
+    const bool isv = wave >= 2;
+    const int ld = isv ? p.ldv : p.ldk;
+    const bf16* base = (isv ? p.V : p.K) + (long long)b * p.R * p.Lr * ld + head * 64;
+    for (int r = 0; r < p.R; ++r)
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) {
+        const TileSrc src = tile_src(base + ((long long)r * p.Lr + kb * 32) * ld, ld, p.Lr - kb * 32, wave & 1, lane);
+        stage_tile(src, 0, smem + r * RB + (isv ? KB * 4096 : 0) + kb * 4096, wave & 1);
+      }
+  }
+  int rf_off[4], tr_off[2][2];
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
+  {
+    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
+  }
+  int qrow = u_begin * 128 + wave * 32 + frow;
+  bf16x8 qf[4];
+  char* const qst = Osm + 4 * 4096 + wave * 4096;                 // this wave's Q image, one unit ahead (as in xattn_fwd_kernel)
+  const TileSrc qsrc = tile_src(Qb, p.ldq, p.Sq, 0, lane);
+  auto stage_q = [&](int row0) {
+    stage_tile(qsrc, row0, qst, 0);
+    stage_tile(qsrc, row0 + 16, qst + 2048, 0);
+  };
+  if (u_begin < u_end) stage_q(u_begin * 128 + wave * 32);
+  WAIT_VM0();
+  __syncthreads();
+  const float* const wb = p.w + (p.Bw == 1 ? 0 : (long long)b * p.R * p.Sq);
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int u = u_begin; u < u_end; ++u, qrow += 128) {
+    const bool qvalid = qrow < p.Sq;
+    WAIT_VM0();                                                  // this wave's Q image (and its stores of the last unit)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qst + rf_off[s]);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (u + 1 < u_end) stage_q((u + 1) * 128 + wave * 32);
+    float wv[4];                                                 // w[b][r][this lane's query]; 0 for a region that is not there
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wv[r] = r < p.R && qvalid ? wb[(long long)r * p.Sq + qrow] : 0.f;
+    f32x16 tot[2] = {zero16, zero16};
+    for (int r = 0; r < p.R; ++r) {
+      const float wr = r == 0 ? wv[0] : r == 1 ? wv[1] : r == 2 ? wv[2] : wv[3];
+      if (__builtin_amdgcn_ballot_w64(wr != 0.f) == 0) continue; // nobody in this wave weighs region r: skip both products
+      const char* const Ksm = smem + r * RB;
+      const char* const Vsm = Ksm + KB * 4096;
+      f32x16 sacc[KB];
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) {
+        bf16x8 kfr[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) kfr[s] = *(const bf16x8*)(Ksm + rf_off[s] + kb * 4096);
+        sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[0], qf[0], zero16, 0, 0, 0);
+#pragma unroll
+        for (int s = 1; s < 4; ++s) sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[s], qf[s], sacc[kb], 0, 0, 0);
+      }
+      if (KB * 32 > p.Lr) {                                      // padding slots of the region's last block: -inf
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int key = (KB - 1) * 32 + (i & 3) + 8 * (i >> 2) + 4 * fh;
+          sacc[KB - 1][i] = key < p.Lr ? sacc[KB - 1][i] : -INFINITY;
+        }
+      }
+      float mx = sacc[0][0];
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+        for (int i = (kb == 0 ? 1 : 0); i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
+      mx = xhalf_max(mx);
+      const float mc = mx * c;
+      float ls = 0.f;
+      bf16x8 pf[2 * KB];
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float e = fast_exp2(fmaf(sacc[kb][i], c, -mc));
+          ls += e;
+          pf[2 * kb + (i >> 3)][i & 7] = (bf16)e;
+        }
+      const float f = wr / xhalf_sum(ls);
+      f32x16 oacc[2];
+#pragma unroll
+      for (int ks = 0; ks < 2 * KB; ++ks)
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+          const bf16x8 tf = read_transposed_frag_at(Vsm + tr_off[db][0] + ks * 2048, Vsm + tr_off[db][1] + ks * 2048);
+          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[ks], ks == 0 ? zero16 : oacc[db], 0, 0, 0);
+        }
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) tot[db][i] = fmaf(oacc[db][i], f, tot[db][i]);
+    }
+    char* const ost = Osm + wave * 4096;                         // O leaves through a per-wave LDS image, as in xattn_fwd_kernel;
+                                                                 // here XOR-swizzled at a 128-byte pitch instead of padded to 144
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        bf16x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (bf16)tot[db][4 * g + j];
+        *(bf16x4*)(ost + frow * 128 + (((db * 4 + g) ^ swz_x(frow)) << 4) + fh * 8) = o;
+      }
+    {
+      const int r8 = lane >> 3, ch = lane & 7;
+      const int q0w = u * 128 + wave * 32;
+      bf16* Ob = p.O + (long long)b * p.Sq * p.ldo + head * 64 + ch * 8;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = i * 8 + r8;
+        const bf16x8 v = *(const bf16x8*)(ost + row * 128 + ((ch ^ swz_x(row)) << 4));
+        if (q0w + row < p.Sq) *(bf16x8*)(Ob + (long long)(q0w + row) * p.ldo) = v;
+      }
+    }
+  }
+}
+
 // ============================================================================= few queries, keys split across the waves
 // O = softmax(scale [Q K1^T | Q K2^T]) [V1 ; V2]: at most 32 queries over ONE softmax of two key sets read in place (the
 // Perceiver Resampler of the IP-Adapter "plus" files: 16 latents over 257 image rows and the 16 latents themselves; K1 / V1 and
@@ -2712,5 +2871,83 @@ extern "C" int pea_debug_attn_dispatch(const int* q, int* out) {
     int* const o = out + 2 + 7 * i;
     o[0] = l.kernel; o[1] = (int)l.grid.x; o[2] = (int)l.grid.y; o[3] = (int)l.grid.z; o[4] = l.lds; o[5] = l.a0; o[6] = l.a1;
   }
+  return PEA_OK;
+}
+
+// ============================================================================= host: regional text prompts
+// A launcher of its own beside the decision table above (which, with AK_COUNT, attn_plan and pea_debug_attn_dispatch, does not
+// know it): the shape checks, the LDS and grid rule, the launch.  Units per workgroup are sized as attn_decide_fwd sizes them,
+// one round of the workgroups the LDS lets a CU hold: two up to 80 KiB (two regions of 77 keys: 81 920 bytes exactly), one above.
+struct AttnRegionsPlan { int kb, lds, upw; dim3 grid; };
+static int attn_plan_regions(AttnRegionsP& p, AttnRegionsPlan& plan) {
+  if (p.nd == 0) p.nd = 1;
+  SHAPECHK(p.B > 0 && p.B <= 65535 && p.H > 0 && p.H <= 65535 && p.Sq >= 1, "attention_regions: empty problem (B=%d H=%d Sq=%d)", p.B, p.H, p.Sq);
+  SHAPECHK(p.nd == 1, "attention_regions: head_dim 64 only (nd=%d)", p.nd);
+  SHAPECHK(p.R >= 1 && p.R <= 4, "attention_regions: 1..4 regions (R=%d)", p.R);
+  SHAPECHK(p.Lr >= 1 && p.Lr <= 96, "attention_regions: 1..96 keys per region (Lr=%d)", p.Lr);
+  SHAPECHK(p.Bw == 1 || p.Bw == p.B, "attention_regions: Bw=%d (1, or the batch %d)", p.Bw, p.B);
+  SHAPECHK(p.Q && p.K && p.V && p.O && p.w, "attention_regions: null operand");
+  SHAPECHK(p.scale > 0.f && p.scale <= 3.0e38f, "attention_regions: a finite positive scale (%g)", (double)p.scale);
+  const int C = 64 * p.H;
+  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldq >= C && p.ldk >= C && p.ldv >= C,
+           "attention_regions: ldq / ldk / ldv must be multiples of 8 and hold every head (%d %d %d)", p.ldq, p.ldk, p.ldv);
+  SHAPECHK(p.ldo % 4 == 0 && p.ldo >= C, "attention_regions: ldo %% 4, ldo >= 64 H (ldo=%d)", p.ldo);
+  const unsigned long long in_bits = (unsigned long long)p.Q | (unsigned long long)p.K | (unsigned long long)p.V;
+  SHAPECHK(in_bits % 16 == 0 && (unsigned long long)p.O % 8 == 0 && (unsigned long long)p.w % 4 == 0,
+           "attention_regions: Q / K / V 16-byte, O 8-byte, w 4-byte aligned");
+  SHAPECHK((long long)p.R * p.Sq * (p.Bw == 1 ? 1 : p.B) < (1ll << 40), "attention_regions: weight table too large");
+  plan.kb = cdiv(p.Lr, 32);
+  plan.lds = p.R * plan.kb * 2 * 4096 + 4 * 4096 + 4 * 4096;
+  const int nu = cdiv(p.Sq, 128), per_cu = 2 * plan.lds <= 160 * 1024 ? 2 : 1;
+  long long upw = ((long long)p.B * p.H * nu + 256 * per_cu - 1) / (256 * per_cu);
+  plan.upw = (int)(upw < 1 ? 1 : (upw > nu ? nu : upw));
+  plan.grid = dim3(cdiv(nu, plan.upw), p.H, p.B);
+  return PEA_OK;
+}
+// an instantiation's LDS grows with R: its limit is raised once, to what four regions take (launch_lds raises to the first launch's bytes)
+template <int KB>
+static int launch_regions(const AttnRegionsPlan& plan, const AttnRegionsP& p, hipStream_t s) {
+  static bool raised = false;
+  if (!raised) {
+    HIPCHK(hipFuncSetAttribute((const void*)xattn_regions_fwd_kernel<KB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               4 * KB * 2 * 4096 + 4 * 4096 + 4 * 4096));
+    raised = true;
+  }
+  hipLaunchKernelGGL(xattn_regions_fwd_kernel<KB>, plan.grid, dim3(256), plan.lds, s, p, plan.upw);
+  return PEA_OK;
+}
+int launch_attention_fwd_regions(const AttnRegionsP& p0, hipStream_t s) {
+  AttnRegionsP p = p0;
+  AttnRegionsPlan plan;
+  const int rc = attn_plan_regions(p, plan);
+  if (rc) return rc;
+  const double keys = (double)p.R * p.Lr;
+  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.R * p.Lr; g_prof_tag[3] = 1; }
+  PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * keys * 64, 2.0 * p.B * p.H * 64 * (2.0 * p.Sq + 2.0 * keys), s);
+  int lrc = PEA_OK;
+  switch (plan.kb) {
+    case 1: lrc = launch_regions<1>(plan, p, s); break;
+    case 2: lrc = launch_regions<2>(plan, p, s); break;
+    default: lrc = launch_regions<3>(plan, p, s); break;
+  }
+  PROF_END(s);
+  if (lrc) return lrc;
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+extern "C" int pea_debug_attn_regions_dispatch(const int* q, int* out) {
+  static float page[64];
+  bf16* const any = (bf16*)page;
+  AttnRegionsP p = AttnRegionsP();
+  p.Q = p.K = p.V = any; p.O = any; p.w = page; p.scale = 0.125f;
+  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.R = q[3]; p.Lr = q[4]; p.nd = q[5];
+  p.ldq = p.ldk = p.ldv = p.ldo = 64 * p.H;
+  if (q[6] > 0) p.ldk = q[6];
+  p.Bw = q[7] > 0 ? q[7] : 1;
+  AttnRegionsPlan plan;
+  const int rc = attn_plan_regions(p, plan);
+  if (rc) return rc;
+  out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
   return PEA_OK;
 }

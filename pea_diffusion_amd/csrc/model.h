@@ -231,6 +231,18 @@ struct Tape {
   };
   int ip_attach(const Op& o, AttnP& p);   // the image key sets of cross-attention op o, or none (tape.hip)
   IpState* ip = nullptr;
+  // Regional text prompts (graph 0, inference only; api_model.hip: pea_unet_set_prompt_regions): the context holds R prompts of
+  // L / R rows each, and while this is set every cross-attention on t_kvall is ONE launch_attention_fwd_regions with the weights
+  // of its query count.  The tape, the plans, the arenas and the attention census do not change.  Outside the arenas.
+  struct RegionState {
+    int R = 0;
+    std::map<int, std::pair<float*, int>> w;   // query count -> (device fp32 [Bw][R][Sq], Bw in {1, B})
+    ~RegionState() {
+      for (auto& m : w) (void)hipFree(m.second.first);
+    }
+  };
+  RegionState* regions = nullptr;
+  int regions_check(int R, bool need_weights) const;   // what a context must be to run R regions (tape.hip)
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

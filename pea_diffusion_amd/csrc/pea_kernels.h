@@ -141,6 +141,19 @@ int launch_attention_fwd(const AttnP& p, hipStream_t s);
 // Sq <= 32 over ONE softmax of K | K2 (Skv2 <= 32, or none): the keys, not the queries, are shared out (attn_fewq_kernel)
 int launch_attention_fwd_fewq(const AttnP& p, hipStream_t s);
 int launch_attention_bwd(const AttnP& p, hipStream_t s);
+// Regional text prompts, forward only, head_dim 64: R <= 4 key sets of Lr <= 96 keys back to back in one K / V buffer
+// [B][R * Lr][ld], each with a softmax of its own, O[b][q] = sum_r w[b][r][q] softmax(scale Q K_r^T) V_r (xattn_regions_fwd_kernel).
+// w: fp32 [Bw][R][Sq], Bw 1 (shared by the batch) or B, not normalised by the kernel.  Its own launcher, shape checks and grid
+// rule: the decision table of launch_attention_fwd / _bwd does not know it.
+struct AttnRegionsP {
+  const bf16 *Q, *K, *V; int ldq, ldk, ldv;
+  bf16* O; int ldo;
+  int B, H, Sq, R, Lr;
+  const float* w; int Bw;
+  float scale; int q_prescaled;
+  int nd;                          // padded head_dim / 64 (0 is read as 1); anything but 1 is refused
+};
+int launch_attention_fwd_regions(const AttnRegionsP& p, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise.hip
 int launch_geglu_fwd(const bf16* hg, bf16* y, long long rows, int inner, hipStream_t s);   // hg [rows][2*inner]

@@ -268,6 +268,7 @@ Tape::~Tape() {
   if (inp_buf) (void)hipFree(inp_buf);
   if (fu_buf) (void)hipFree(fu_buf);
   delete ip;
+  delete regions;
 }
 
 int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s) {
@@ -546,6 +547,36 @@ static int ip_masks_complete(const Tape& u) {
   return PEA_OK;
 }
 
+// Regional text prompts: what the context must be.  Checked when weights are set and again (need_weights) before the first
+// launch of a forward: image prompts or per-sample context lengths may have arrived in between, and a query count without
+// weights would otherwise run on another layer's table.
+int Tape::regions_check(int R, bool need_weights) const {
+  const char* const who = need_weights ? "pea_unet_forward" : "pea_unet_set_prompt_regions";
+  if (needs_grad) {
+    pea_set_error("%s: regional prompts are an inference feature (no backward through them); this context was created with PEA_UNET_GRAD", who);
+    return PEA_E_STATE;
+  }
+  if (cross_kvlen) { pea_set_error("%s: regional prompts cannot be combined with per-sample context lengths", who); return PEA_E_STATE; }
+  if (ip)
+    for (int j = 0; j < ip->nsets; ++j)
+      if (ip->set[j].live) {
+        pea_set_error("%s: regional prompts cannot be combined with live image prompts (set %d; pea_unet_ip_clear)", who, j);
+        return PEA_E_STATE;
+      }
+  SHAPECHK(R >= 1 && R <= 4, "%s: 1..4 regions (R=%d)", who, R);
+  SHAPECHK(L % R == 0 && L / R <= 96, "%s: a context of %d rows is no %d prompts of at most 96 rows", who, L, R);
+  for (const Op& o : ops) {
+    if (o.kind != OP_ATTN || o.b != t_kvall) continue;
+    SHAPECHK(o.p3 == 1 && o.p2 == L, "%s: regional prompts need head_dim 64 cross-attention over the whole context (nd=%d, %d keys)", who, o.p3, o.p2);
+    if (need_weights && !regions->w.count(o.p1)) {
+      pea_set_error("%s: regional prompts have no weights for the layers with %d queries; pea_unet_set_prompt_regions needs every "
+                    "count of pea_unet_ip_query_counts", who, o.p1);
+      return PEA_E_STATE;
+    }
+  }
+  return PEA_OK;
+}
+
 int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype, const void* text, int text_dtype,
                   const float* time_ids, float* eps, hipStream_t s) {
   std::string miss;
@@ -554,6 +585,7 @@ int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype
     return PEA_E_STATE;
   }
   RC(ip_masks_complete(*this));
+  if (regions) RC(regions_check(regions->R, true));
   RC(ensure_acts());
   RC(ensure_folded(s));
   x_in = x; t_in = t; tid_in = time_ids; eps_out = eps;
@@ -769,6 +801,15 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
         p.q_prescaled = o.pre;
         if (o.mask & 4) p.bias = rel_bias;
         if (cross_kvlen && o.b == t_kvall) p.kv_len = cross_kvlen;
+        if (regions && o.b == t_kvall) {                            // regional prompts: R softmaxes over the R runs of context rows
+          const auto& wt = regions->w.find(o.p1)->second;           // (regions_check has passed: the count is there)
+          AttnRegionsP r = AttnRegionsP();
+          r.Q = p.Q; r.ldq = p.ldq; r.K = p.K; r.ldk = p.ldk; r.V = p.V; r.ldv = p.ldv; r.O = p.O; r.ldo = p.ldo;
+          r.B = B; r.H = o.p0; r.Sq = o.p1; r.R = regions->R; r.Lr = o.p2 / regions->R; r.w = wt.first; r.Bw = wt.second;
+          r.scale = o.f0; r.q_prescaled = o.pre; r.nd = o.p3;
+          RC(launch_attention_fwd_regions(r, s));
+          break;
+        }
         if (ip && o.b == t_kvall) RC(ip_attach(o, p));               // image prompts: the layer's own columns of the image K|V
         RC(launch_attention_fwd(p, s));
         break;

@@ -354,6 +354,26 @@ def attention_fwd_ipn(q, k, v, k2, v2, heads, n_keys, scales, masks=None, scale=
     return (o, lse) if want_lse else o
 
 
+def attention_fwd_regions(q, k, v, heads, R, w, q_prescaled=False, scale=None):
+    """Regional text prompts in one launch (pea_op_attention_fwd_regions):
+    o[b, q] = sum_r w[b, r, q] * softmax(scale q k_r^T) v_r, head_dim 64, one softmax per region.  q [B,Sq,H*64] bf16; k/v
+    [B,R*Lr,>=H*64] bf16 hold the R <= 4 regions back to back, region r in rows r*Lr .. (r+1)*Lr, Lr <= 96; w fp32 [1|B,R,Sq],
+    any finite values, used as they are (`regional.region_weights` makes them sum to 1 per query).  -> o."""
+    B, Sq, C, scale, o, _ = _attn_fwd_out(q, heads, scale)
+    R = int(R)
+    if C != heads * 64:
+        raise PeaError(f"attention_fwd_regions: head_dim {C // heads} (the kernel is built for 64)")
+    if w.dtype != torch.float32 or w.dim() != 3 or w.shape[1] != R or w.shape[2] != Sq:
+        raise PeaError(f"attention_fwd_regions: w {tuple(w.shape)} {w.dtype}, expected fp32 [1|{B}, {R}, {Sq}]")
+    Lr = k.shape[1] // R if R > 0 and k.shape[1] % R == 0 else -1
+    if Lr < 0:
+        raise PeaError(f"attention_fwd_regions: {k.shape[1]} key rows are no {R} regions of equal length")
+    w = w.contiguous()
+    check(lib().pea_op_attention_fwd_regions(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, B, heads, Sq,
+                                             R, Lr, ptr(w), w.shape[0], scale, int(q_prescaled), stream_ptr()))
+    return o
+
+
 def attention_fwd_fewq(q, k, v, k2=None, v2=None, heads=1, scale=None, q_prescaled=False, want_lse=False, kv_rows=None,
                        kv2_rows=None):
     """Few-query attention over the union of two key sets in one launch (pea_op_attention_fwd_fewq):

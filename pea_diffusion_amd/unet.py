@@ -387,6 +387,39 @@ class HipUNet(HipTape):
                 check(lib().pea_unet_ip_set_mask(self._h, j, c, ptr(d), d.shape[0], stream_ptr()))
             torch.cuda.current_stream().synchronize()      # the library copies on the stream; `d` is freed after this call
 
+    def set_prompt_regions(self, masks, weights=None, do_cfg=False):
+        """Regional text prompts: the context of this UNet holds R prompts of L / R tokens (`regional.compose_prompt_embeds`), and
+        `masks` says where each of them applies: a list with, per prompt, `None` (everywhere) or a mask `[h, w]` / `[1|B, h, w]` at
+        any resolution, values >= 0.  Every cross-attention layer then runs R softmaxes in one launch and mixes their outputs with
+        `regional.region_weights(masks, weights, h_l, w_l)` of its own grid (area means, normalised per position; uncovered
+        positions go to prompt 0).  `weights`: one factor per prompt (default 1).  do_cfg: the first half of the batch (the
+        unconditional half) attends to prompt 0 alone.  Holds until `clear_prompt_regions()`."""
+        from .regional import region_weights
+        masks = list(masks)
+        R = len(masks)
+        self.clear_prompt_regions()
+        try:
+            for c in self.ip_query_counts():
+                w = region_weights(masks, weights, *self._grid_of(c), device=self.device)         # [Bm, R, c]
+                if w.shape[0] not in (1, self.B):
+                    raise PeaError(f"set_prompt_regions: masks with batch {w.shape[0]}, expected 1 or {self.B}")
+                if do_cfg:
+                    if self.B % 2:
+                        raise PeaError(f"set_prompt_regions: do_cfg needs an even batch (B={self.B})")
+                    w = w.expand(self.B, -1, -1).clone()
+                    w[: self.B // 2] = 0.0
+                    w[: self.B // 2, 0] = 1.0
+                w = w.contiguous()
+                check(lib().pea_unet_set_prompt_regions(self._h, R, c, ptr(w), w.shape[0], stream_ptr()))
+            torch.cuda.current_stream().synchronize()          # the library copies on the stream; `w` is freed after this call
+        except Exception:
+            self.clear_prompt_regions()
+            raise
+
+    def clear_prompt_regions(self):
+        """back to one softmax over the whole context"""
+        check(lib().pea_unet_clear_prompt_regions(self._h))
+
     def clear_ip_tokens(self, index=None):
         """back to plain cross-attention launches (index: for that adapter alone); the adapters' weights stay loaded"""
         if index is None:
