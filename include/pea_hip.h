@@ -849,6 +849,41 @@ int pea_unet_clear_prompt_regions(void* unet);
  * refused problem.  LDS = R KB 2 4096 + 4 4096 + 4 4096 bytes (keys and values, the O images, the Q images). */
 int pea_debug_attn_regions_dispatch(const int* q, int* out);
 
+/* ---- cross-attention heat maps ("DAAM", diffusion attentive attribution maps): where in the picture each prompt token acts.
+ * pea_op_attention_maps: maps[b][key][q] (op)= (1 / H) sum_h softmax_key(scale Q[b, q, h, :] . K[b, key, h, :]) in ONE launch, head_dim
+ * 64, no V / O / lse.  maps: device fp32 [B][Skv][Sq], so one key's map is one contiguous image of the layer's latent grid.
+ * 1 <= Skv <= 128, any Sq >= 1.  (op) is a store, or with accumulate != 0 a += done by the one thread that owns the element
+ * (load, one fp32 add, store; no atomics).  q_prescaled: Q arrives multiplied by scale * log2(e), as for pea_op_attention_fwd.
+ * kv_len: NULL or device int [B], 1 <= kv_len[b] <= Skv; the maps of keys at or past it are exact zeros (with accumulate: + 0).
+ * The probabilities are never rounded to bf16: exp2 and the normalisation are fp32.  Sum over heads in a fixed order (wave w of
+ * the workgroup's eight takes heads w, w + 8, ... in ascending order; the eight partial sums are added in wave order,
+ * (((w0 + w1) + w2) + ...) + w7, then x 1 / H): the same bits every run.  ldq / ldk multiples of 8 holding every head, Q / K 16-byte aligned.  Every refusal is PEA_E_SHAPE
+ * before any launch. */
+int pea_op_attention_maps(const void* Q, int ldq, const void* K, int ldk, float* maps, int B, int H, int Sq, int Skv, float scale,
+                          int q_prescaled, const int* kv_len, int accumulate, void* stream);
+/* The same in a UNet context (graph 0, inference): while enabled, every selected cross-attention layer is followed by ONE launch of
+ * pea_op_attention_maps (accumulate = 1) over its own Q and its columns of the stacked K|V projection, into the accumulator of its
+ * query count: fp32 [B][L][Sq], one per count of pea_unet_ip_query_counts, zeroed, outside the arenas
+ * (pea_unet_release_activations keeps them).  layer_on: NULL (every cross-attention layer) or n_layers floats in the order of the
+ * IP-Adapter files' layers (pea_unet_ip_set_layer_scales), non-zero = capture.  The ordinary attention launch, the tape, the plans
+ * and the arenas do not change: a forward gives the bits it gives without capture.  With image prompts the maps are those of the
+ * text softmax (the decoupled attention's text term does not depend on the image keys); per-sample context lengths mask as in
+ * the layer.  Refused: a PEA_UNET_GRAD context (PEA_E_STATE), any other graph than a UNet (PEA_E_INVALID), padded heads or a
+ * context longer than 128 rows (PEA_E_SHAPE); a forward with prompt regions set while capture is on (PEA_E_STATE).
+ * pea_unet_reset_attention_maps zeroes the accumulators (on `stream`) and their counters; pea_unet_disable_attention_maps
+ * synchronises the device and frees them.  pea_unet_attention_maps: the accumulator of one query count and how many
+ * layer-forwards have been added to it since the last reset -- a host counter of launches issued, so a forward replayed from a
+ * captured graph is not counted.  Enable before a denoising loop and read after it: the sums then run over layers and steps. */
+int pea_unet_enable_attention_maps(void* unet, const float* layer_on, int n_layers);
+int pea_unet_reset_attention_maps(void* unet, void* stream);
+int pea_unet_disable_attention_maps(void* unet);
+int pea_unet_attention_maps(void* unet, int Sq, float** maps, long long* n_accumulated);
+/* Test aid, needs no device: what pea_op_attention_maps launches (shape checks included).  q[8] = { B, H, Sq, Skv, nd, ldq (<= 0:
+ * 64 H), ldk (<= 0: 64 H), flags (1: kv_len, 2: accumulate, 4: q_prescaled) }.  Returns PEA_OK and out[6] = { KB (the instantiation
+ * xattn_maps_kernel<KB>, ceil(Skv / 32)), grid x / y / z, dynamic LDS bytes, 32-query units per workgroup }, or the error code of a
+ * refused problem.  grid = ceil(Sq / 32) x B x 1, workgroups of 512 threads; LDS = 8 waves x (KB + 1) x 4096 bytes. */
+int pea_debug_attn_maps_dispatch(const int* q, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -480,6 +480,19 @@ static int ip_check(const Tape& u, int n_tokens, const Op** kv_op) {
     }
   return PEA_OK;
 }
+// K column of every cross-attention layer in the stacked K|V projection `fused` -> the layer's index in the order of
+// ip_adapter.layer_keys: every down block, then every up block, then the mid block; inside a group the order of the modules,
+// which is the order of the slots
+static void xattn_layer_order(const Tape& u, int fused, std::map<int, int>& layer_of_col) {
+  for (int group = 0; group < 3; ++group)
+    for (const WSlot& s : u.slots) {
+      const std::string& n = s.name;
+      if (s.fused_parent != fused || s.kind != W_LINEAR || n.size() < 12 || n.compare(n.size() - 12, 12, ".to_k.weight")) continue;
+      if ((n.rfind("down_blocks.", 0) == 0 ? 0 : n.rfind("up_blocks.", 0) == 0 ? 1 : 2) != group) continue;
+      const int idx = (int)layer_of_col.size();
+      layer_of_col[s.row_off] = idx;
+    }
+}
 #define IP_HANDLE(h, what)                                                                     \
   NOTNULL(h, what);                                                                            \
   Tape* u = (Tape*)h;                                                                          \
@@ -525,14 +538,7 @@ int pea_unet_ip_create_sets(void* h, int n_sets, const int* n_tokens) {
   ip->nsets = n_sets; ip->total = total; ip->cols = u->kvall_total; ip->fused = kv->fused;
   // the file's layer order (ip_adapter.layer_keys): every down block, then every up block, then the mid block; inside a group
   // the order of the modules, which is the order of the slots
-  for (int group = 0; group < 3; ++group)
-    for (const WSlot& s : u->slots) {
-      const std::string& n = s.name;
-      if (s.fused_parent != kv->fused || s.kind != W_LINEAR || n.size() < 12 || n.compare(n.size() - 12, 12, ".to_k.weight")) continue;
-      if ((n.rfind("down_blocks.", 0) == 0 ? 0 : n.rfind("up_blocks.", 0) == 0 ? 1 : 2) != group) continue;
-      const int idx = (int)ip->layer_of_col.size();
-      ip->layer_of_col[s.row_off] = idx;
-    }
+  xattn_layer_order(*u, kv->fused, ip->layer_of_col);
   const size_t B = (size_t)u->B, K = (size_t)u->cfg.cross_dim;
   bool ok = hipMalloc((void**)&ip->kv, B * total * ip->cols * 2) == hipSuccess &&
             hipMemset(ip->kv, 0, B * total * ip->cols * 2) == hipSuccess;
@@ -697,6 +703,90 @@ int pea_unet_clear_prompt_regions(void* h) {
   if (u->regions) HIPCHK(hipDeviceSynchronize());    // a queued forward may still read the weights
   delete u->regions;
   u->regions = nullptr;
+  return PEA_OK;
+}
+// ------------------------------------------------------------------------------ cross-attention heat maps
+int pea_unet_enable_attention_maps(void* h, const float* layer_on, int n_layers) {
+  NOTNULL(h, "pea_unet_enable_attention_maps");
+  Tape* u = (Tape*)h;
+  if (u->graph != 0 || u->t_kvall < 0) {
+    pea_set_error("pea_unet_enable_attention_maps: not a UNet handle (graph %d has no text cross-attention to map)", u->graph);
+    return PEA_E_INVALID;
+  }
+  if (u->needs_grad) {
+    pea_set_error("pea_unet_enable_attention_maps: heat maps are an inference feature; this context was created with PEA_UNET_GRAD");
+    return PEA_E_STATE;
+  }
+  SHAPECHK(u->L >= 1 && u->L <= 128, "pea_unet_enable_attention_maps: context length %d (the maps kernel takes 1..128 keys)", u->L);
+  const Op* kv = nullptr;
+  for (const Op& o : u->ops)
+    if (o.out == u->t_kvall && o.fused >= 0) kv = &o;
+  if (!kv) { pea_set_error("pea_unet_enable_attention_maps: stacked K|V projection not found"); return PEA_E_STATE; }
+  for (const WSlot& s : u->slots)
+    SHAPECHK(!(s.fused_parent == kv->fused && s.pad_mode), "pea_unet_enable_attention_maps: '%s' has padded heads (head_dim %d); the maps "
+             "kernel is built for head_dim 64", s.name.c_str(), s.pad_d);
+  for (const Op& o : u->ops)
+    if (o.kind == OP_ATTN && o.b == u->t_kvall)
+      SHAPECHK(o.p3 == 1 && o.p2 == u->L, "pea_unet_enable_attention_maps: head_dim 64 cross-attention over the whole context (nd=%d, %d keys)", o.p3, o.p2);
+  Tape::MapState* m = new Tape::MapState();
+  xattn_layer_order(*u, kv->fused, m->layer_of_col);
+  const int want = (int)m->layer_of_col.size();
+  if (layer_on && n_layers != want) {
+    delete m;
+    pea_set_error("pea_unet_enable_attention_maps: %d layer switches, this UNet has %d cross-attention layers", n_layers, want);
+    return PEA_E_SHAPE;
+  }
+  m->on.assign(want, 1);
+  for (int i = 0; layer_on && i < want; ++i) m->on[i] = layer_on[i] != 0.f;
+  int rc = pea_unet_disable_attention_maps(h);        // accumulators already there: replaced, behind whatever still adds to them
+  std::vector<int> c;
+  ip_query_counts(*u, c);
+  for (size_t i = 0; i < c.size() && rc == PEA_OK; ++i) {
+    const size_t bytes = (size_t)u->B * u->L * c[i] * sizeof(float);
+    float* buf = nullptr;
+    if (hipMalloc((void**)&buf, bytes) != hipSuccess || (m->acc[c[i]] = buf, hipMemset(buf, 0, bytes)) != hipSuccess) {
+      pea_set_error("pea_unet_enable_attention_maps: out of device memory (%zu bytes for the %d-query level)", bytes, c[i]);
+      rc = PEA_E_HIP;
+    }
+    m->count[c[i]] = 0;
+  }
+  if (rc == PEA_OK && hipDeviceSynchronize() != hipSuccess) {  // the zeros are there before a forward on any stream adds to them
+    pea_set_error("pea_unet_enable_attention_maps: device synchronisation failed");
+    rc = PEA_E_HIP;
+  }
+  if (rc != PEA_OK) { delete m; return rc; }
+  u->maps = m;
+  return PEA_OK;
+}
+int pea_unet_reset_attention_maps(void* h, void* stream) {
+  NOTNULL(h, "pea_unet_reset_attention_maps");
+  Tape* u = (Tape*)h;
+  if (!u->maps) { pea_set_error("pea_unet_reset_attention_maps: call pea_unet_enable_attention_maps first"); return PEA_E_STATE; }
+  for (auto& a : u->maps->acc) {
+    HIPCHK(hipMemsetAsync(a.second, 0, (size_t)u->B * u->L * a.first * sizeof(float), (hipStream_t)stream));
+    u->maps->count[a.first] = 0;
+  }
+  return PEA_OK;
+}
+int pea_unet_disable_attention_maps(void* h) {
+  NOTNULL(h, "pea_unet_disable_attention_maps");
+  Tape* u = (Tape*)h;
+  if (u->maps) HIPCHK(hipDeviceSynchronize());       // a queued forward may still add to the accumulators
+  delete u->maps;
+  u->maps = nullptr;
+  return PEA_OK;
+}
+int pea_unet_attention_maps(void* h, int Sq, float** maps, long long* n_accumulated) {
+  NOTNULL(h, "pea_unet_attention_maps");
+  Tape* u = (Tape*)h;
+  if (!u->maps) { pea_set_error("pea_unet_attention_maps: call pea_unet_enable_attention_maps first"); return PEA_E_STATE; }
+  const auto it = u->maps->acc.find(Sq);
+  if (it == u->maps->acc.end()) {
+    pea_set_error("pea_unet_attention_maps: no cross-attention layer of this context has %d queries (pea_unet_ip_query_counts)", Sq);
+    return PEA_E_SHAPE;
+  }
+  if (maps) *maps = it->second;
+  if (n_accumulated) *n_accumulated = u->maps->count[Sq];
   return PEA_OK;
 }
 int pea_unet_ip_clear_set(void* h, int set) {

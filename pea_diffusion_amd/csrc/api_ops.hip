@@ -313,6 +313,14 @@ int pea_op_attention_fwd_regions(const void* Q, int ldq, const void* K, int ldk,
   p.B = B; p.H = H; p.Sq = Sq; p.R = R; p.Lr = Lr; p.w = w; p.Bw = Bw; p.scale = scale; p.q_prescaled = q_prescaled; p.nd = 1;
   return launch_attention_fwd_regions(p, (hipStream_t)stream);
 }
+int pea_op_attention_maps(const void* Q, int ldq, const void* K, int ldk, float* maps, int B, int H, int Sq, int Skv, float scale,
+                          int q_prescaled, const int* kv_len, int accumulate, void* stream) {
+  AttnMapsP p = AttnMapsP();
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.ldq = ldq; p.ldk = ldk; p.maps = maps;
+  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.q_prescaled = q_prescaled; p.kv_len = kv_len;
+  p.accumulate = accumulate; p.nd = 1;
+  return launch_attention_maps(p, (hipStream_t)stream);
+}
 int pea_op_attention_fwd_fewq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                               const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                               float scale, int nd, int q_prescaled, void* stream) {

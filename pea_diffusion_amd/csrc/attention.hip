@@ -23,6 +23,9 @@
 // per-wave LDS image as whole 128-byte rows.
 // Few queries (<= 32: the Resampler latents of the IP-Adapter "plus" files) over the union of two key sets under one softmax:
 // attn_fewq_kernel shares out the KEYS among a workgroup's waves and merges their partials in a fixed order.
+// Heat maps (the head-mean cross-attention probabilities of a layer, fp32 [B][Skv][Sq], no V / O / lse): xattn_maps_kernel deals
+// the HEADS of a 32-query block over a workgroup's eight waves and adds their partial sums in a fixed order; its launcher, like the
+// regional one, stands beside the decision table.
 // The three backward cross-attention kernels take their per-workgroup context (unit range, operand rows of the head, key
 // count, score factor) from xattn_ctx.  They still repeat, as text: K / V staging, the unit stage (stage_unit / fetch_o /
 // unit_head), the key-on-the-lane task, the query-on-the-lane key-block step, and the dQ and dK / dV exits -- so a fix to
@@ -1376,6 +1379,137 @@ __global__ __launch_bounds__(256, 2) void xattn_regions_fwd_kernel(const AttnReg
         if (q0w + row < p.Sq) *(bf16x8*)(Ob + (long long)(q0w + row) * p.ldo) = v;
       }
     }
+  }
+}
+
+// ============================================================================= cross-attention heat maps
+// M[b][key][q] (op)= (1 / H) sum_h softmax_key(s Q[b, q, h, :] . K[b, key, h, :]): the head-mean cross-attention probability of
+// every (key, query) pair, fp32, laid out [B][Skv][Sq] so that one token's map is one contiguous h_l x w_l image ("DAAM", diffusion
+// attentive attribution maps).  xattn_fwd_kernel keeps S and P in registers and writes O alone, and the heads of one (sample,
+// query) live in different workgroups there; summing them without atomics needs a kernel that has all heads of a query in ONE
+// workgroup.  No V, no O, no lse; 1 <= Skv <= 128 (KB = ceil(Skv / 32) key blocks), head_dim 64, any Sq.
+// A workgroup owns 32 queries of one sample (one MFMA column block) and deals the HEADS over its EIGHT waves: wave w runs heads
+// w, w + 8, w + 16, ... in that order.  Every wave has an LDS slot of its own -- the head's KB key blocks (32 rows x 128 bytes
+// each, descriptors that start at the block's first row and end with the sample's last key, as in attn_fewq_kernel: nothing
+// behind a sample's keys is read) and the 32 query rows of that head -- filled by LDS-DMA at the top of the head's iteration; no
+// barrier in the loop.  There is no second slot: what hides a wave's fetch is the other wave of its SIMD.  The first form had four
+// waves with a ring two slots deep (the same LDS); one wave per SIMD then ran fetch wait, 12 MFMAs and ~300 vector instructions
+// per head back to back with nothing to overlap them: 8.03 / 10.46 us at the two SDXL shapes against 6.49 / 7.62 us in this form
+// (profiles/EXPERIMENTS.md section 9, f10).  Per head: S^T = K . Q^T (in the S^T accumulator layout one register index
+// is one key over 32 consecutive queries), padding keys and keys at or past kv_len[b] to -inf by the compare of
+// xattn_fwd_kernel, a one-shot softmax in fp32 -- e = exp2(c s - c max), p = e x (1 / sum), the reciprocal taken once per query;
+// P is never rounded to bf16 -- and one fmaf per element into the wave's fp32 partial sum.  q_prescaled: c = 1, as there.
+// Reduction order (fixed, the same bits every run): within a wave its heads in ascending order; then the eight partial sums
+// meet in LDS (each wave's own, by now idle, slot: [KB x 32 keys][32 queries] fp32) and every element is summed in wave order,
+// ((((w0 + w1) + w2) + ...) + w7), and multiplied by 1 / H once.  A wave without a head contributes zeros.  The thread that owns an
+// element stores it, or with `accumulate` loads, adds and stores it (one fp32 add; plain vector memory instructions, no atomics;
+// no other workgroup of the launch touches that element).  32 lanes write 32 consecutive queries of one key: whole 128-byte runs
+// where Sq is a multiple of 32.  A cut key's probability is an exact 0.0f in every head, so its map is.
+// LDS: 8 waves x (KB + 1) x 4 096 bytes = 65 536 .. 163 840.
+#define MAPS_WAVES 8
+template <int KB>
+__global__ __launch_bounds__(64 * MAPS_WAVES) void xattn_maps_kernel(const AttnMapsP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int SLOT = (KB + 1) * 4096;                          // a wave's slot: KB key blocks, then the query rows
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int frow = lane & 31, fh = lane >> 5;
+  const int q0 = blockIdx.x * 32, b = blockIdx.y;
+  const float c = p.q_prescaled ? 1.f : p.scale * LOG2E;
+  const bf16* Qb = p.Q + ((long long)b * p.Sq + q0) * p.ldq;     // this unit's first query row, head 0
+  const bf16* Kb = p.K + (long long)b * p.Skv * p.ldk;
+  const int qrows = min(p.Sq - q0, 32);                          // >= 1: the grid has no unit past Sq
+  const int skv_b = __builtin_amdgcn_readfirstlane(p.kv_len ? p.kv_len[b] : p.Skv);
+  char* const my = smem + wave * SLOT;
+  // head `h`: its key blocks -> dst + kb * 4096, its query rows -> dst + KB * 4096 (pieces 0 / 1 of a tile: rows 0..15, 16..31)
+  auto stage_head = [&](int h, char* dst) {
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      const bf16* kblk = Kb + (long long)kb * 32 * p.ldk + h * 64;
+      const int left = min(p.Skv - kb * 32, 32);                 // >= 1: KB = ceil(Skv / 32)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) stage_tile(tile_src(kblk, p.ldk, left, hf, lane), 0, dst + kb * 4096, hf);
+    }
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) stage_tile(tile_src(Qb + h * 64, p.ldq, qrows, hf, lane), 0, dst + KB * 4096, hf);
+  };
+  int rf_off[4];
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 macc[KB];
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) macc[kb] = zero16;
+  for (int h = wave; h < p.H; h += MAPS_WAVES) {
+    char* const cur = my;
+    stage_head(h, cur);                                          // (the slot's last reader: the iteration before, closed below)
+    WAIT_VM0();                                                  // this head's rows have landed
+    bf16x8 qf[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(cur + KB * 4096 + rf_off[s]);
+    // S^T[key][q] = K . Q^T over the KB key blocks
+    f32x16 sacc[KB];
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + kb * 4096 + rf_off[0]), qf[0], zero16, 0, 0, 0);
+#pragma unroll
+      for (int s = 1; s < 4; ++s)
+        sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + kb * 4096 + rf_off[s]), qf[s], sacc[kb], 0, 0, 0);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // every read of `cur` is done before a later DMA may land in it
+    // padding keys / keys past this sample's count: -inf (only the blocks that hold any)
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+      if (kb * 32 + 32 > skv_b) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+          sacc[kb][r] = key < skv_b ? sacc[kb][r] : -INFINITY;
+        }
+      }
+    float mx = sacc[0][0];
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+      for (int r = (kb == 0 ? 1 : 0); r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
+    mx = xhalf_max(mx);
+    const float mc = mx * c;
+    float ls = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        sacc[kb][r] = fast_exp2(fmaf(sacc[kb][r], c, -mc));      // masked key: exp2(-inf) = 0
+        ls += sacc[kb][r];
+      }
+    const float inv = 1.f / xhalf_sum(ls);
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) macc[kb][r] = fmaf(sacc[kb][r], inv, macc[kb][r]);
+  }
+  // this wave's partial sum into its own slot (no DMA is in flight: each staged head was waited for and consumed)
+  float* const part = (float*)my;
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[(kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * 32 + frow] = macc[kb][r];
+  __syncthreads();
+  // merge: thread -> query tid & 31, keys (tid >> 5), (tid >> 5) + 16, ...; partials in wave order
+  const int q = tid & 31;
+  if (q >= qrows) return;                                        // rows of a ragged last unit
+  const float inv_h = 1.f / (float)p.H;
+  float* const mrow = p.maps + (long long)b * p.Skv * p.Sq + q0 + q;
+  for (int key = tid >> 5; key < p.Skv; key += 2 * MAPS_WAVES) {
+#pragma clang fp contract(off)                                   // `+=` is ONE fp32 add of the rounded mean, not an fma with 1 / H
+    const int e = (key * 32 + q) * 4;
+    float sum = *(const float*)(smem + e);
+#pragma unroll
+    for (int w = 1; w < MAPS_WAVES; ++w) sum = sum + *(const float*)(smem + w * SLOT + e);
+    const float v = sum * inv_h;
+    float* const dst = mrow + (long long)key * p.Sq;
+    if (p.accumulate) *dst = *dst + v;
+    else *dst = v;
   }
 }
 
@@ -2947,6 +3081,80 @@ extern "C" int pea_debug_attn_regions_dispatch(const int* q, int* out) {
   p.Bw = q[7] > 0 ? q[7] : 1;
   AttnRegionsPlan plan;
   const int rc = attn_plan_regions(p, plan);
+  if (rc) return rc;
+  out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
+  return PEA_OK;
+}
+
+// ============================================================================= host: cross-attention heat maps
+// A launcher of its own, like the regions' above; the decision table does not know it.  The grid and LDS rule, in this one
+// function: a workgroup is ONE 32-query unit of one sample (grid = ceil(Sq / 32) x B, every workgroup has work), its eight waves
+// share out the heads, and its LDS is 8 slots of (KB + 1) half tiles of 4 096 bytes, KB = ceil(Skv / 32).  The sum over heads has
+// to stay inside a workgroup (no atomics), and 32 queries are one MFMA column block, so a launch has B x Sq / 32 workgroups
+// whatever H is: 256 at SDXL's 4096-query level with B = 2, 64 at its 1024-query level (20 heads: two or three per wave).
+struct AttnMapsPlan { int kb, lds, upw; dim3 grid; };
+static int attn_plan_maps(AttnMapsP& p, AttnMapsPlan& plan) {
+  if (p.nd == 0) p.nd = 1;
+  SHAPECHK(p.B > 0 && p.B <= 65535 && p.H > 0 && p.H <= 65535 && p.Sq >= 1, "attention_maps: empty problem (B=%d H=%d Sq=%d)", p.B, p.H, p.Sq);
+  SHAPECHK(p.nd == 1, "attention_maps: head_dim 64 only (nd=%d)", p.nd);
+  SHAPECHK(p.Skv >= 1 && p.Skv <= 128, "attention_maps: 1..128 keys (Skv=%d)", p.Skv);
+  SHAPECHK(p.Q && p.K && p.maps, "attention_maps: null operand");
+  SHAPECHK(p.scale > 0.f && p.scale <= 3.0e38f, "attention_maps: a finite positive scale (%g)", (double)p.scale);
+  const int C = 64 * p.H;
+  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldq >= C && p.ldk >= C,
+           "attention_maps: ldq / ldk must be multiples of 8 and hold every head (%d %d)", p.ldq, p.ldk);
+  SHAPECHK(((unsigned long long)p.Q | (unsigned long long)p.K) % 16 == 0 && (unsigned long long)p.maps % 4 == 0 &&
+               (unsigned long long)p.kv_len % 4 == 0,
+           "attention_maps: Q / K 16-byte, maps / kv_len 4-byte aligned");
+  SHAPECHK((long long)p.ldq * 64 < (1ll << 30) && (long long)p.ldk * 64 < (1ll << 30), "attention_maps: leading dimension too large");
+  plan.kb = cdiv(p.Skv, 32);
+  plan.lds = MAPS_WAVES * (plan.kb + 1) * 4096;
+  plan.upw = 1;
+  plan.grid = dim3(cdiv(p.Sq, 32), p.B, 1);
+  return PEA_OK;
+}
+// (launch_lds launches 256 threads; this kernel's workgroup is eight waves)
+template <int KB>
+static int launch_maps(const AttnMapsPlan& plan, const AttnMapsP& p, hipStream_t s) {
+  static bool raised = false;
+  if (!raised) {
+    HIPCHK(hipFuncSetAttribute((const void*)xattn_maps_kernel<KB>, hipFuncAttributeMaxDynamicSharedMemorySize, plan.lds));
+    raised = true;
+  }
+  hipLaunchKernelGGL(xattn_maps_kernel<KB>, plan.grid, dim3(64 * MAPS_WAVES), plan.lds, s, p);
+  return PEA_OK;
+}
+int launch_attention_maps(const AttnMapsP& p0, hipStream_t s) {
+  AttnMapsP p = p0;
+  AttnMapsPlan plan;
+  const int rc = attn_plan_maps(p, plan);
+  if (rc) return rc;
+  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = 1; }
+  PROF_BEGIN(2, 2.0 * p.B * p.H * (double)p.Sq * p.Skv * 64,
+             2.0 * p.B * p.H * 64 * ((double)p.Sq + p.Skv) + (p.accumulate ? 8.0 : 4.0) * p.B * (double)p.Sq * p.Skv, s);
+  int lrc = PEA_OK;
+  switch (plan.kb) {
+    case 1: lrc = launch_maps<1>(plan, p, s); break;
+    case 2: lrc = launch_maps<2>(plan, p, s); break;
+    case 3: lrc = launch_maps<3>(plan, p, s); break;
+    default: lrc = launch_maps<4>(plan, p, s); break;
+  }
+  PROF_END(s);
+  if (lrc) return lrc;
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+extern "C" int pea_debug_attn_maps_dispatch(const int* q, int* out) {
+  static float page[64];
+  AttnMapsP p = AttnMapsP();
+  p.Q = p.K = (const bf16*)page; p.maps = page; p.scale = 0.125f;
+  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.Skv = q[3]; p.nd = q[4];
+  p.ldq = q[5] > 0 ? q[5] : 64 * p.H;
+  p.ldk = q[6] > 0 ? q[6] : 64 * p.H;
+  p.kv_len = q[7] & 1 ? (const int*)page : nullptr; p.accumulate = q[7] >> 1 & 1; p.q_prescaled = q[7] >> 2 & 1;
+  AttnMapsPlan plan;
+  const int rc = attn_plan_maps(p, plan);
   if (rc) return rc;
   out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
   return PEA_OK;

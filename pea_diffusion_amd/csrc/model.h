@@ -243,6 +243,20 @@ struct Tape {
   };
   RegionState* regions = nullptr;
   int regions_check(int R, bool need_weights) const;   // what a context must be to run R regions (tape.hip)
+  // Cross-attention heat maps (graph 0, inference only; api_model.hip: pea_unet_enable_attention_maps): while this is set, every
+  // selected cross-attention on t_kvall is followed by ONE launch_attention_maps over the same Q and K columns that adds the
+  // layer's head-mean probabilities into the accumulator of its query count.  The ordinary launch, the tape, the plans, the arenas
+  // and the attention census do not change.  Outside the arenas: release_acts keeps the accumulators.
+  struct MapState {
+    std::map<int, int> layer_of_col;           // K column of a cross-attention layer in the stack -> its index in the file's order
+    std::vector<char> on;                      // per layer in that order: captured or not
+    std::map<int, float*> acc;                 // query count -> device fp32 [B][L][Sq]
+    std::map<int, long long> count;            // query count -> layer-forwards added since the last reset (host)
+    ~MapState() {
+      for (auto& m : acc) (void)hipFree(m.second);
+    }
+  };
+  MapState* maps = nullptr;
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

@@ -154,6 +154,19 @@ struct AttnRegionsP {
   int nd;                          // padded head_dim / 64 (0 is read as 1); anything but 1 is refused
 };
 int launch_attention_fwd_regions(const AttnRegionsP& p, hipStream_t s);
+// Cross-attention heat maps, head_dim 64, 1 <= Skv <= 128: maps[b][key][q] (op)= (1 / H) sum_h softmax_key(scale Q_h K_h^T), fp32
+// [B][Skv][Sq], (op) a store or (accumulate) a += by the thread that owns the element (xattn_maps_kernel, 512 threads; no V, no O, no lse).
+// Its own launcher, shape checks and grid rule: the decision table of launch_attention_fwd / _bwd does not know it.
+struct AttnMapsP {
+  const bf16 *Q, *K; int ldq, ldk;
+  float* maps;
+  int B, H, Sq, Skv;
+  float scale; int q_prescaled;
+  const int* kv_len;               // optional per-sample key counts (device, [B], 1..Skv): keys at or past it map to exact zeros
+  int accumulate;
+  int nd;                          // padded head_dim / 64 (0 is read as 1); anything but 1 is refused
+};
+int launch_attention_maps(const AttnMapsP& p, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise.hip
 int launch_geglu_fwd(const bf16* hg, bf16* y, long long rows, int inner, hipStream_t s);   // hg [rows][2*inner]

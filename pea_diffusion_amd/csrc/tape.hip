@@ -269,6 +269,7 @@ Tape::~Tape() {
   if (fu_buf) (void)hipFree(fu_buf);
   delete ip;
   delete regions;
+  delete maps;
 }
 
 int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s) {
@@ -586,6 +587,11 @@ int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype
   }
   RC(ip_masks_complete(*this));
   if (regions) RC(regions_check(regions->R, true));
+  if (maps && regions) {
+    pea_set_error("pea_unet_forward: cross-attention heat maps cannot be combined with regional prompts (a context of several prompts has "
+                  "a softmax per region; pea_unet_disable_attention_maps or pea_unet_clear_prompt_regions)");
+    return PEA_E_STATE;
+  }
   RC(ensure_acts());
   RC(ensure_folded(s));
   x_in = x; t_in = t; tid_in = time_ids; eps_out = eps;
@@ -812,6 +818,17 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
         }
         if (ip && o.b == t_kvall) RC(ip_attach(o, p));               // image prompts: the layer's own columns of the image K|V
         RC(launch_attention_fwd(p, s));
+        if (maps && o.b == t_kvall) {                               // heat maps: the text softmax's head mean, added to the level's sum
+          const auto lay = maps->layer_of_col.find(o.bcol);
+          if (lay != maps->layer_of_col.end() && maps->on[lay->second]) {
+            AttnMapsP m = AttnMapsP();
+            m.Q = p.Q; m.ldq = p.ldq; m.K = p.K; m.ldk = p.ldk; m.maps = maps->acc.find(o.p1)->second;
+            m.B = B; m.H = o.p0; m.Sq = o.p1; m.Skv = o.p2; m.scale = o.f0; m.q_prescaled = o.pre; m.nd = o.p3;
+            m.kv_len = cross_kvlen; m.accumulate = 1;
+            RC(launch_attention_maps(m, s));
+            ++maps->count[o.p1];
+          }
+        }
         break;
       }
       case OP_ATTN_FEWQ: {             // the latents over the image rows' keys and their own, one softmax, both read in place

@@ -374,6 +374,33 @@ def attention_fwd_regions(q, k, v, heads, R, w, q_prescaled=False, scale=None):
     return o
 
 
+def attention_maps(q, k, heads, scale=None, q_prescaled=False, kv_len=None, out=None, accumulate=False):
+    """Cross-attention heat maps in one launch (pea_op_attention_maps):
+    m[b, key, q] = mean_h softmax_key(scale q_h k_h^T), head_dim 64, fp32, probabilities never rounded to bf16.  q [B,Sq,H*64] bf16;
+    k [B,Skv,>=H*64] bf16, 1 <= Skv <= 128; kv_len: optional int32 [B] (keys at or past it map to exact zeros).  out: a contiguous
+    fp32 buffer of at least B*Skv*Sq elements to write (or, accumulate=True, add) into; the maps are its first B*Skv*Sq elements.
+    -> fp32 [B, Skv, Sq] (a view of `out` when given).  The same bits every run."""
+    B, Sq, C = q.shape
+    Skv = k.shape[1]
+    if C != heads * 64:
+        raise PeaError(f"attention_maps: head_dim {C // max(heads, 1)} (the kernel is built for 64)")
+    scale = float(scale) if scale is not None else 64 ** -0.5
+    n = B * Skv * Sq
+    if out is None:
+        if accumulate:
+            raise PeaError("attention_maps: accumulate=True needs the buffer to add into (out=)")
+        out = torch.empty(n, device=q.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n or out.device != q.device:
+        raise PeaError(f"attention_maps: out {tuple(out.shape)} {out.dtype}, expected contiguous fp32 with at least {n} elements")
+    if kv_len is not None:
+        if kv_len.dtype != torch.int32 or kv_len.numel() != B:
+            raise PeaError(f"attention_maps: kv_len {tuple(kv_len.shape)} {kv_len.dtype}, expected int32 [{B}]")
+        kv_len = kv_len.contiguous()
+    check(lib().pea_op_attention_maps(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(out), B, heads, Sq, Skv, scale, int(q_prescaled),
+                                      ptr(kv_len), int(bool(accumulate)), stream_ptr()))
+    return out.view(-1)[:n].view(B, Skv, Sq)
+
+
 def attention_fwd_fewq(q, k, v, k2=None, v2=None, heads=1, scale=None, q_prescaled=False, want_lse=False, kv_rows=None,
                        kv2_rows=None):
     """Few-query attention over the union of two key sets in one launch (pea_op_attention_fwd_fewq):

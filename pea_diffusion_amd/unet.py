@@ -37,6 +37,14 @@ class _BlockShim:
         return _HookHandle(self._hooks, fn)
 
 
+class _DeviceF32:
+    """a device fp32 buffer of the library, as `torch.as_tensor` reads it (the buffer stays the library's: clone what is kept)"""
+
+    def __init__(self, address: int, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(int(s) for s in shape), "typestr": "<f4", "data": (int(address), False),
+                                         "strides": None, "version": 2}
+
+
 class _Config:
     def __init__(self, cfg):
         self.__dict__.update(cfg.__dict__)
@@ -419,6 +427,42 @@ class HipUNet(HipTape):
     def clear_prompt_regions(self):
         """back to one softmax over the whole context"""
         check(lib().pea_unet_clear_prompt_regions(self._h))
+
+    def enable_attention_maps(self, layers=None):
+        """Cross-attention heat maps (DAAM): from now on every selected cross-attention layer adds its head-mean softmax
+        probabilities to an fp32 accumulator [B, L, h_l * w_l] of its latent grid, in one extra launch per layer; the forward's own
+        results do not change.  layers: None (every cross-attention layer) or a spec in the vocabulary of
+        `ip_adapter.resolve_layer_scales` (`{"up": 1.0}`, `{"down_blocks.2": 1.0, "mid": 1.0}`, ...; non-zero = capture).  Enable
+        before a denoising loop and read `attention_maps()` / `attention_maps.heat_maps(unet)` after it: the sums then run over
+        layers and steps.  Accumulators start at zero; `reset_attention_maps()` zeroes them again."""
+        if layers is None:
+            check(lib().pea_unet_enable_attention_maps(self._h, None, 0))
+            return
+        from .ip_adapter import resolve_layer_scales
+        vec = resolve_layer_scales(self.cfg, layers)
+        arr = (ctypes.c_float * len(vec))(*vec)
+        check(lib().pea_unet_enable_attention_maps(self._h, arr, len(vec)))
+
+    def disable_attention_maps(self):
+        """stop capturing and free the accumulators"""
+        check(lib().pea_unet_disable_attention_maps(self._h))
+
+    def reset_attention_maps(self):
+        """zero the accumulators and their counters (on the current stream)"""
+        check(lib().pea_unet_reset_attention_maps(self._h, stream_ptr()))
+
+    def attention_maps(self):
+        """-> {(h_l, w_l): (fp32 tensor [B, L, h_l, w_l], n_accumulated)}: per latent grid the sum of the head-mean cross-attention
+        probabilities over every layer-forward since the last reset, and how many layer-forwards that is (a host counter).  The
+        tensors are copies made on the current stream."""
+        out = {}
+        for c in self.ip_query_counts():
+            p, n = ctypes.c_void_p(), ctypes.c_longlong()
+            check(lib().pea_unet_attention_maps(self._h, c, ctypes.byref(p), ctypes.byref(n)))
+            h, w = self._grid_of(c)
+            t = torch.as_tensor(_DeviceF32(p.value, (self.B, self.L, h, w)), device=self.device).clone()
+            out[(h, w)] = (t, int(n.value))
+        return out
 
     def clear_ip_tokens(self, index=None):
         """back to plain cross-attention launches (index: for that adapter alone); the adapters' weights stay loaded"""
