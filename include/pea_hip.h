@@ -884,6 +884,47 @@ int pea_unet_attention_maps(void* unet, int Sq, float** maps, long long* n_accum
  * refused problem.  grid = ceil(Sq / 32) x B x 1, workgroups of 512 threads; LDS = 8 waves x (KB + 1) x 4096 bytes. */
 int pea_debug_attn_maps_dispatch(const int* q, int* out);
 
+/* ---- prompt-to-prompt editing (Hertz et al.): keep the picture, change one word.  A batch holds N prompts denoised from the same
+ * initial latents; sample b with src[b] = s >= 0 is edited with the unedited sample s as its source (src[b] < 0, or src[b] = b,
+ * a sample that is its own source: not edited).
+ * pea_op_attention_fwd_edit, ONE launch over the whole batch, forward only, head_dim 64, 1 <= Skv <= 96, any Sq >= 1, B <= 32:
+ *   edited b:    P0 = softmax(scale Q[s] K[s]^T), P1 = softmax(scale Q[b] K[b]^T), each with its own maximum and sum,
+ *                A[q][j] = c[b][j] sum_k P0[q][k] Mt[b][j][k] + d[b][j] P1[q][j],  O[b] = A V[b]   (no renormalisation)
+ *   unedited b:  O[b] = softmax(scale Q[b] K[b]^T) V[b], the bits of pea_op_attention_fwd; no table row of that sample is read.
+ * src: HOST int[B], validated before any launch and passed in the kernel arguments.  Mt: device bf16 [B][Skv][ldm], the transposed
+ * token mapper (row j the target key, column k the source key; ldm a multiple of 8, >= Skv; columns at or past Skv are ignored).
+ * c, d: device fp32 [B][Skv].  The mixture is formed in fp32 and rounded to bf16 once; c = 0, d = 1 on a sample gives that sample
+ * the bits of the plain kernel (Sq >= 128: below, pea_op_attention_fwd is another kernel, which then writes the unedited samples).
+ * No atomics: the same bits every run.  ld* and alignment as for pea_op_attention_fwd_regions; Mt 16-byte aligned.  PEA_E_SHAPE
+ * before any launch: src[b] >= B, a source that is itself edited, B > 32, Skv > 96, a leading dimension that is no multiple of 8,
+ * an empty problem, a null table while any sample is edited.  PEA_E_INVALID: null src. */
+int pea_op_attention_fwd_edit(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H,
+                              int Sq, int Skv, const int* src, const void* Mt, int ldm, const float* c, const float* d, float scale,
+                              int q_prescaled, void* stream);
+/* The same in a UNet context (graph 0, inference), a runtime state like regions and maps: the tape, the plans and the arenas do not
+ * change.  pea_unet_set_prompt_edit: src host int[B]; Mt device bf16 [B][L][L] (ldm = L rounded up to 8 is made inside); cd device
+ * fp32 [T][2][B][L], c then d for every one of T steps; all copied into buffers outside the arenas (cd also to the host, so the
+ * launch choice per step reads no device memory).  pea_unet_set_prompt_edit_step sets the current step, a host int: nothing is
+ * transferred inside a denoising loop.  While set, every cross-attention layer runs pea_op_attention_fwd_edit at a step that has
+ * any c != 0 or d != 1 on an edited sample, and the plain launch otherwise; every self-attention layer with at most
+ * self_max_tokens queries, while step < self_until, runs its ordinary launch and then ONE more plain launch per edited sample
+ * (B = 1: Q and K of the source, V and O of the sample), O[b] = softmax(scale Q[s] K[s]^T) V[b].  A forward refuses
+ * (PEA_E_STATE / PEA_E_SHAPE, before the first launch): a PEA_UNET_GRAD context, live image prompts, prompt regions, attention-map
+ * capture, per-sample context lengths, L > 96, head_dim other than 64 in the cross-attention, a step outside 0..T-1.  After
+ * pea_unet_clear_prompt_edit a forward gives the bits it gave before. */
+int pea_unet_set_prompt_edit(void* unet, const int* src, const void* Mt, const float* cd, int T, int self_until, int self_max_tokens,
+                             void* stream);
+int pea_unet_set_prompt_edit_step(void* unet, int step);
+int pea_unet_clear_prompt_edit(void* unet);
+/* Test aid, needs no device: what pea_op_attention_fwd_edit launches (shape checks included).  q[40] = { B, H, Sq, Skv, nd, ldk
+ * (<= 0: 64 H, like every other leading dimension), ldm (<= 0: Skv rounded up to 8), flags (bit 0: null tables), src[0..31] }.
+ * Returns PEA_OK and out[8] = { KB (the instantiation xattn_edit_fwd_kernel<KB>), grid x / y / z, dynamic LDS bytes, 128-query
+ * units per workgroup of an unedited sample, 1 if the plain launch runs first and the kernel writes the edited samples only, units
+ * per workgroup of an edited sample }, or the error code of a refused problem.  The grid is 1-D: H x ceil(units / units per
+ * workgroup) workgroups per sample with the count of its kind, the edited samples' first; y = z = 1.  LDS = 3 KB 4096 + KB 32 (KB 64 + 16) + KB 256 + 4 4096 + 8 4096 bytes (own keys, values, the source's keys; the
+ * mapper; c and d; the O images; the Q images of both samples). */
+int pea_debug_attn_edit_dispatch(const int* q, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -705,6 +705,70 @@ int pea_unet_clear_prompt_regions(void* h) {
   u->regions = nullptr;
   return PEA_OK;
 }
+// ------------------------------------------------------------------------------ prompt-to-prompt editing
+int pea_unet_set_prompt_edit(void* h, const int* src, const void* Mt, const float* cd, int T, int self_until, int self_max_tokens,
+                             void* stream) {
+  NOTNULL(h, "pea_unet_set_prompt_edit");
+  Tape* u = (Tape*)h;
+  if (u->graph != 0 || u->t_kvall < 0) { pea_set_error("pea_unet_set_prompt_edit: not a UNet handle (graph %d has no text cross-attention to edit)", u->graph); return PEA_E_INVALID; }
+  if (!src || !Mt || !cd) { pea_set_error("pea_unet_set_prompt_edit: null src, Mt or cd"); return PEA_E_INVALID; }
+  RCX(u->edit_check(false));
+  const int B = u->B, L = u->L;
+  SHAPECHK(T >= 1 && T <= (1 << 20), "pea_unet_set_prompt_edit: T=%d steps", T);
+  SHAPECHK(self_until >= 0 && self_max_tokens >= 0, "pea_unet_set_prompt_edit: self_until=%d, self_max_tokens=%d (>= 0)", self_until, self_max_tokens);
+  int n_edited = 0;
+  for (int b = 0; b < B; ++b) {
+    if (src[b] < 0 || src[b] == b) continue;                       // (its own source: not edited)
+    SHAPECHK(src[b] < B, "pea_unet_set_prompt_edit: src[%d]=%d is out of range (batch %d)", b, src[b], B);
+    SHAPECHK(src[src[b]] < 0 || src[src[b]] == src[b], "pea_unet_set_prompt_edit: src[%d]=%d names a source that is itself edited", b, src[b]);
+    ++n_edited;
+  }
+  RCX(pea_unet_clear_prompt_edit(h));
+  Tape::EditState* e = new Tape::EditState();
+  for (int b = 0; b < 32; ++b) e->src[b] = b < B && src[b] != b ? src[b] : -1;
+  e->n_edited = n_edited; e->T = T; e->self_until = self_until; e->self_max_tokens = self_max_tokens; e->ldm = (L + 7) / 8 * 8;
+  const size_t cd_elems = (size_t)T * 2 * B * L;
+  std::vector<float> host(cd_elems);
+  hipError_t err = hipMalloc((void**)&e->Mt, (size_t)B * L * e->ldm * sizeof(bf16));
+  if (err == hipSuccess) err = hipMalloc((void**)&e->cd, cd_elems * sizeof(float));
+  if (err == hipSuccess) err = hipMemsetAsync(e->Mt, 0, (size_t)B * L * e->ldm * sizeof(bf16), (hipStream_t)stream);
+  if (err == hipSuccess) err = hipMemcpy2DAsync(e->Mt, (size_t)e->ldm * sizeof(bf16), Mt, (size_t)L * sizeof(bf16), (size_t)L * sizeof(bf16),
+                                                (size_t)B * L, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (err == hipSuccess) err = hipMemcpyAsync(e->cd, cd, cd_elems * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (err == hipSuccess) err = hipMemcpyAsync(host.data(), cd, cd_elems * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream);
+  if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t)stream);
+  if (err != hipSuccess) {
+    pea_set_error("pea_unet_set_prompt_edit: %s", hipGetErrorString(err));
+    delete e;
+    return PEA_E_HIP;
+  }
+  e->cd_live.assign(T, 0);
+  for (int t = 0; t < T; ++t)
+    for (int b = 0; b < B && !e->cd_live[t]; ++b) {
+      if (e->src[b] < 0) continue;
+      const float* c = host.data() + ((size_t)t * 2 * B + b) * L;
+      const float* d = c + (size_t)B * L;
+      for (int j = 0; j < L; ++j)
+        if (c[j] != 0.f || d[j] != 1.f) { e->cd_live[t] = 1; break; }
+    }
+  u->edit = e;
+  return PEA_OK;
+}
+int pea_unet_set_prompt_edit_step(void* h, int step) {
+  NOTNULL(h, "pea_unet_set_prompt_edit_step");
+  Tape* u = (Tape*)h;
+  if (!u->edit) { pea_set_error("pea_unet_set_prompt_edit_step: call pea_unet_set_prompt_edit first"); return PEA_E_STATE; }
+  u->edit->step = step;                               // (a step outside 0..T-1 is refused by the forward that would use it)
+  return PEA_OK;
+}
+int pea_unet_clear_prompt_edit(void* h) {
+  NOTNULL(h, "pea_unet_clear_prompt_edit");
+  Tape* u = (Tape*)h;
+  if (u->edit) HIPCHK(hipDeviceSynchronize());        // a queued forward may still read the tables
+  delete u->edit;
+  u->edit = nullptr;
+  return PEA_OK;
+}
 // ------------------------------------------------------------------------------ cross-attention heat maps
 int pea_unet_enable_attention_maps(void* h, const float* layer_on, int n_layers) {
   NOTNULL(h, "pea_unet_enable_attention_maps");

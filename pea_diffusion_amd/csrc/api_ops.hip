@@ -321,6 +321,18 @@ int pea_op_attention_maps(const void* Q, int ldq, const void* K, int ldk, float*
   p.accumulate = accumulate; p.nd = 1;
   return launch_attention_maps(p, (hipStream_t)stream);
 }
+int pea_op_attention_fwd_edit(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H,
+                              int Sq, int Skv, const int* src, const void* Mt, int ldm, const float* c, const float* d, float scale,
+                              int q_prescaled, void* stream) {
+  if (!src) { pea_set_error("pea_op_attention_fwd_edit: null src (a host int[B]; negative entries for unedited samples)"); return PEA_E_INVALID; }
+  AttnEditP p = AttnEditP();
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.Mt = (const bf16*)Mt; p.ldm = ldm; p.c = c; p.d = d;
+  p.scale = scale; p.q_prescaled = q_prescaled; p.nd = 1;
+  for (int b = 0; b < 32; ++b) p.src[b] = b < B ? src[b] : -1;      // (B > 32 is refused by the launcher)
+  return launch_attention_fwd_edit(p, (hipStream_t)stream);
+}
 int pea_op_attention_fwd_fewq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                               const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                               float scale, int nd, int q_prescaled, void* stream) {

@@ -1513,6 +1513,262 @@ __global__ __launch_bounds__(64 * MAPS_WAVES) void xattn_maps_kernel(const AttnM
   }
 }
 
+// ============================================================================= prompt-to-prompt editing
+// A batch of prompts denoised from the same latents; sample b with s = src[b] >= 0 is "edited": per head
+//   P0 = softmax(scale Q[s] K[s]^T)   the source's probabilities at the same query positions,   P1 = softmax(scale Q[b] K[b]^T)
+//   A[q][j] = c[b][j] sum_k P0[q][k] Mt[b][j][k] + d[b][j] P1[q][j],   O[b] = A V[b]            (no renormalisation)
+// in ONE launch over the whole batch.  The branch is per workgroup: one of an unedited sample (src[b] < 0) stages its own K and V,
+// runs the arithmetic of xattn_fwd_kernel in its order (same bits) and reads no table; one of an edited sample stages K of the
+// source, its own K and V (KB = ceil(Skv / 32) half tiles of 32 keys each, through descriptors that end with the sample's last
+// row: padding slots arrive as zeros and score -inf), Mt[b] and c[b] / d[b], and every wave walks its 128-query units with the
+// Q fragments of both samples resident (two LDS-DMA images per wave, one unit ahead).
+// The mapper product needs no shuffle: S^T is keys x queries, and the un-normalised bf16 P0^T fragments pf0[] that the softmax
+// leaves are the B operand of mfma_f32_32x32x16_bf16 exactly as the value product uses them, so (Mt P0^T)[j][q] is one more
+// product of that shape, 2 KB^2 MFMAs per 32 queries, whose result lands in the layout P1^T has.  Slot (fh, i) of fragment ks
+// holds key 16 ks + 4 fh + (i & 3) + 8 (i >> 2); the Mt image is written with the two middle quads of every 16 columns swapped,
+// so that a lane's A fragment is one 16-byte read of row j (pitch KB * 64 + 16 bytes).  Mt is staged by ordinary loads, not by
+// LDS-DMA: rows are ldm wide and columns at or past Skv must be ZERO (P0 is 0 there, but 0 x anything the caller left is not).
+// Each softmax has its own maximum and sum (a spike in the source cannot underflow the target).  The mixture is formed in fp32,
+// mix = fmaf(mapped, c (sum1 / sum0), d e1), rounded to bf16 ONCE, and O is scaled by 1 / sum1 at the end as in the plain kernel:
+// with c = 0, d = 1 that is fmaf(x, 0, e1) = e1, the bits of xattn_fwd_kernel.  No atomics: the same bits every run.
+// Units per workgroup differ: an edited unit is 54 MFMAs and two softmaxes where a plain one is 24 and one, and an edited workgroup
+// stages twice as much, so an edited sample's workgroups take upw_edit units and an unedited sample's upw_plain (attn_plan_edit
+// balances them: with one count for both, 28.6 - 34.9 us at 10 heads x 4096 queries against 19.2 with 8 and 3).
+// LDS: 3 KB 4096 (K, V, source K) + KB 32 (KB 64 + 16) (Mt) + KB 256 (c, d) + 4 x 4096 (O images, XOR-swizzled at a 128-byte
+// pitch as in xattn_regions_fwd_kernel) + 8 x 4096 (Q images): 106 752 bytes at three key blocks -- one workgroup per CU.
+template <int KB>
+__global__ __launch_bounds__(256, KB == 1 ? 2 : 1) void xattn_edit_fwd_kernel(const AttnEditP p, int upw_plain, int upw_edit) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int MP = KB * 64 + 16;                               // bytes of an Mt row in LDS
+  char* const K1sm = smem;
+  char* const Vsm = smem + KB * 4096;
+  char* const K0sm = smem + 2 * KB * 4096;
+  char* const Mtsm = smem + 3 * KB * 4096;
+  float* const cdsm = (float*)(Mtsm + KB * 32 * MP);             // c[KB * 32], then d[KB * 32]; zeros past Skv
+  char* const Osm = (char*)(cdsm + 2 * KB * 32);                 // 4 waves x 32 rows x 128 bytes, then the 8 Q images
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int frow = lane & 31, fh = lane >> 5;
+  // blockIdx.x counts the workgroups that have work, the edited samples' first (the longer ones), then the unedited samples':
+  // H x splits each, with the split count of its kind.  A 1-D grid without idle workgroups: dispatch order deals it evenly over
+  // the XCDs whatever the mix (a 3-D grid with early exits put 40 workgroups on one XCD's 32 CUs: two rounds there).
+  const int nu = (p.Sq + 127) >> 7;
+  const int s_edit = (nu + upw_edit - 1) / upw_edit, s_plain = (nu + upw_plain - 1) / upw_plain;
+  int id = blockIdx.x, b = -1;
+  for (int pass = 0; pass < 2 && b < 0; ++pass)
+    for (int bb = 0; bb < p.B; ++bb) {
+      if ((p.src[bb] >= 0) != (pass == 0)) continue;
+      const int cnt = p.H * (pass == 0 ? s_edit : s_plain);
+      if (id < cnt) { b = bb; break; }
+      id -= cnt;
+    }
+  if (b < 0) return;                                             // (never: the grid is sized by the same count)
+  const int sb = __builtin_amdgcn_readfirstlane(p.src[b]);
+  const bool ed = sb >= 0;
+  const int upw = ed ? upw_edit : upw_plain, splits = ed ? s_edit : s_plain;
+  const int head = id / splits, split = id % splits;
+  const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
+  const float sc = p.q_prescaled ? 1.f : p.scale * LOG2E;
+  {                                                              // waves 0 / 1: the 32 rows of every K block, waves 2 / 3: of every V block
+    const bool isv = wave >= 2;
+    const int ld = isv ? p.ldv : p.ldk;
+    const bf16* base = (isv ? p.V : p.K) + (long long)b * p.Skv * ld + head * 64;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      const TileSrc src = tile_src(base + (long long)kb * 32 * ld, ld, p.Skv - kb * 32, wave & 1, lane);
+      stage_tile(src, 0, (isv ? Vsm : K1sm) + kb * 4096, wave & 1);
+    }
+    if (ed && !isv) {
+      const bf16* base0 = p.K + (long long)sb * p.Skv * p.ldk + head * 64;
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) {
+        const TileSrc src = tile_src(base0 + (long long)kb * 32 * p.ldk, p.ldk, p.Skv - kb * 32, wave & 1, lane);
+        stage_tile(src, 0, K0sm + kb * 4096, wave & 1);
+      }
+    }
+  }
+  if (ed) {
+    const bf16* Mtb = p.Mt + (long long)b * p.Skv * p.ldm;
+    for (int idx = tid; idx < KB * 32 * KB * 4; idx += 256) {    // 8-column pieces of the KB * 32 x KB * 32 image
+      const int row = idx / (KB * 4), c8 = idx % (KB * 4);
+      bf16x8 v;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (bf16)0.f;
+      if (row < p.Skv && 8 * c8 < p.Skv) {                       // (ldm is a multiple of 8 and >= Skv: the piece lies inside the row)
+        const bf16x8 g = *(const bf16x8*)(Mtb + (long long)row * p.ldm + 8 * c8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = 8 * c8 + j < p.Skv ? g[j] : (bf16)0.f;
+      }
+      bf16x4 lo, hi;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { lo[j] = v[j]; hi[j] = v[4 + j]; }
+      char* const dst = Mtsm + row * MP + (c8 >> 1) * 32 + (c8 & 1) * 8;
+      *(bf16x4*)dst = lo;                                        // columns 0..3 | 8..11 | 4..7 | 12..15 of every 16
+      *(bf16x4*)(dst + 16) = hi;
+    }
+    for (int idx = tid; idx < 2 * KB * 32; idx += 256) {
+      const int key = idx % (KB * 32);
+      const float* const t = idx < KB * 32 ? p.c : p.d;
+      cdsm[idx] = key < p.Skv ? t[(long long)b * p.Skv + key] : 0.f;
+    }
+  }
+  int rf_off[4], tr_off[2][2];
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
+  {
+    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
+  }
+  char* const qst1 = Osm + 4 * 4096 + wave * 8192;               // this wave's Q image, one unit ahead (as in xattn_fwd_kernel)
+  char* const qst0 = qst1 + 4096;                                // ... and the same rows of the source sample
+  const TileSrc qsrc1 = tile_src(p.Q + (long long)b * p.Sq * p.ldq + head * 64, p.ldq, p.Sq, 0, lane);
+  const TileSrc qsrc0 = tile_src(p.Q + (long long)(ed ? sb : b) * p.Sq * p.ldq + head * 64, p.ldq, p.Sq, 0, lane);
+  auto stage_q = [&](int row0) {
+    stage_tile(qsrc1, row0, qst1, 0);
+    stage_tile(qsrc1, row0 + 16, qst1 + 2048, 0);
+    if (ed) {
+      stage_tile(qsrc0, row0, qst0, 0);
+      stage_tile(qsrc0, row0 + 16, qst0 + 2048, 0);
+    }
+  };
+  if (u_begin < u_end) stage_q(u_begin * 128 + wave * 32);
+  WAIT_VM0();
+  __syncthreads();
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // S^T[key][q] = K . Q^T over the KB key blocks, padding slots of the last block -inf
+  auto scores = [&](const char* Ksm, const bf16x8 (&qf)[4], f32x16 (&sacc)[KB]) {
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      bf16x8 kfr[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) kfr[s] = *(const bf16x8*)(Ksm + rf_off[s] + kb * 4096);
+      sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[0], qf[0], zero16, 0, 0, 0);
+#pragma unroll
+      for (int s = 1; s < 4; ++s) sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[s], qf[s], sacc[kb], 0, 0, 0);
+    }
+    if (KB * 32 > p.Skv) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int key = (KB - 1) * 32 + (i & 3) + 8 * (i >> 2) + 4 * fh;
+        sacc[KB - 1][i] = key < p.Skv ? sacc[KB - 1][i] : -INFINITY;
+      }
+    }
+  };
+  // sacc <- exp2(sc (s - max)) in place, in the order xattn_fwd_kernel sums them; returns the sum over all keys
+  auto softmax = [&](f32x16 (&sacc)[KB]) -> float {
+    float mx = sacc[0][0];
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+      for (int i = (kb == 0 ? 1 : 0); i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
+    mx = xhalf_max(mx);
+    const float mc = mx * sc;
+    float ls = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float e = fast_exp2(fmaf(sacc[kb][i], sc, -mc));
+        ls += e;
+        sacc[kb][i] = e;
+      }
+    return xhalf_sum(ls);
+  };
+  for (int u = u_begin; u < u_end; ++u) {
+    WAIT_VM0();                                                  // this wave's Q images (and its stores of the last unit)
+    bf16x8 qf1[4], qf0[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf1[s] = *(const bf16x8*)(qst1 + rf_off[s]);
+    if (ed) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) qf0[s] = *(const bf16x8*)(qst0 + rf_off[s]);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (u + 1 < u_end) stage_q((u + 1) * 128 + wave * 32);
+    bf16x8 pf[2 * KB];
+    float l1;
+    if (ed) {
+      f32x16 mp[KB];                                             // (Mt P0^T)[j][q], P0 un-normalised
+      float l0;
+      {
+        f32x16 s0[KB];
+        scores(K0sm, qf0, s0);
+        l0 = softmax(s0);
+        bf16x8 pf0[2 * KB];
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) pf0[2 * kb + (i >> 3)][i & 7] = (bf16)s0[kb][i];
+#pragma unroll
+        for (int jb = 0; jb < KB; ++jb)
+#pragma unroll
+          for (int ks = 0; ks < 2 * KB; ++ks) {
+            const bf16x8 mf = *(const bf16x8*)(Mtsm + (jb * 32 + frow) * MP + ks * 32 + fh * 16);
+            mp[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mf, pf0[ks], ks == 0 ? zero16 : mp[jb], 0, 0, 0);
+          }
+      }
+      f32x16 s1[KB];
+      scores(K1sm, qf1, s1);
+      l1 = softmax(s1);
+      const float ratio = l1 / l0;                               // P0 = e0 / sum0, and O is divided by sum1 at the end
+#pragma unroll
+      for (int jb = 0; jb < KB; ++jb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x4 cj = *(const f32x4*)(cdsm + jb * 32 + 8 * g + 4 * fh);
+          const f32x4 dj = *(const f32x4*)(cdsm + KB * 32 + jb * 32 + 8 * g + 4 * fh);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int i = 4 * g + j;
+            pf[2 * jb + (i >> 3)][i & 7] = (bf16)fmaf(mp[jb][i], cj[j] * ratio, dj[j] * s1[jb][i]);
+          }
+        }
+    } else {
+      f32x16 s1[KB];
+      scores(K1sm, qf1, s1);
+      l1 = softmax(s1);
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pf[2 * kb + (i >> 3)][i & 7] = (bf16)s1[kb][i];
+    }
+    // O^T[d][q] = V^T[d][key] A^T[key][q]
+    f32x16 oacc[2];
+#pragma unroll
+    for (int ks = 0; ks < 2 * KB; ++ks)
+#pragma unroll
+      for (int db = 0; db < 2; ++db) {
+        const bf16x8 tf = read_transposed_frag_at(Vsm + tr_off[db][0] + ks * 2048, Vsm + tr_off[db][1] + ks * 2048);
+        oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[ks], ks == 0 ? zero16 : oacc[db], 0, 0, 0);
+      }
+    const float inv = 1.f / l1;
+    char* const ost = Osm + wave * 4096;                         // O leaves through a per-wave LDS image, as in xattn_regions_fwd_kernel
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        bf16x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (bf16)(oacc[db][4 * g + j] * inv);
+        *(bf16x4*)(ost + frow * 128 + (((db * 4 + g) ^ swz_x(frow)) << 4) + fh * 8) = o;
+      }
+    {
+      const int r8 = lane >> 3, ch = lane & 7;
+      const int q0w = u * 128 + wave * 32;
+      bf16* Ob = p.O + (long long)b * p.Sq * p.ldo + head * 64 + ch * 8;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = i * 8 + r8;
+        const bf16x8 v = *(const bf16x8*)(ost + row * 128 + ((ch ^ swz_x(row)) << 4));
+        if (q0w + row < p.Sq) *(bf16x8*)(Ob + (long long)(q0w + row) * p.ldo) = v;
+      }
+    }
+  }
+}
+
 // ============================================================================= few queries, keys split across the waves
 // O = softmax(scale [Q K1^T | Q K2^T]) [V1 ; V2]: at most 32 queries over ONE softmax of two key sets read in place (the
 // Perceiver Resampler of the IP-Adapter "plus" files: 16 latents over 257 image rows and the 16 latents themselves; K1 / V1 and
@@ -3157,5 +3413,130 @@ extern "C" int pea_debug_attn_maps_dispatch(const int* q, int* out) {
   const int rc = attn_plan_maps(p, plan);
   if (rc) return rc;
   out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
+  return PEA_OK;
+}
+
+// ============================================================================= host: prompt-to-prompt editing
+// A launcher of its own beside the decision table (which, with AK_COUNT, attn_plan and pea_debug_attn_dispatch, does not know
+// it): the shape checks, src validated on the host before any launch, the LDS and the grid rule (units per workgroup for one
+// round of the workgroups per CU the LDS allows -- two at one key block, one above --, as the regions launcher sizes them, but with
+// a count of its own for the edited samples).
+// plain_first: xattn_edit_fwd_kernel gives its unedited samples the bits of xattn_fwd_kernel.  Where the plain launch of the
+// same problem is another kernel (fewer than 128 queries: attn_q_kernel; PEA_XATTN_OFF), that launch runs first over the whole
+// batch and the edit kernel overwrites the edited samples only, so an unedited sample keeps the bits of pea_op_attention_fwd
+// at every shape.  With no edited sample at all the plain launch is all there is.
+// What a workgroup of xattn_edit_fwd_kernel<3> takes, in tenths of a microsecond: a fixed part (staging) and a part per 128-query
+// unit, for a workgroup of an edited and of an unedited sample.  MEASURED at 77 keys (KB = 3) on one MI355X at 2089 MHz
+// (profiles/EXPERIMENTS.md section 9, f11) and used at every KB for want of figures there: only their RATIOS enter the rule below,
+// which balances the two kinds of workgroup.  A change to the kernel's unit loop or staging invalidates them: re-run the sweep of
+// f11 (scripts/p2p_bench.py times the result) and tests/test_p2p_cpu.py, which pins the pairs they give at the SDXL shapes.
+constexpr long long EDIT_WG_FIXED = 64, EDIT_WG_UNIT = 37, PLAIN_WG_FIXED = 30, PLAIN_WG_UNIT = 20;
+struct AttnEditPlan { int kb, lds, upw, upw_edit, plain_first, n_edited; dim3 grid; AttnP plain; AttnPlan pplan; };
+static int attn_plan_edit(AttnEditP& p, AttnEditPlan& plan) {
+  if (p.nd == 0) p.nd = 1;
+  SHAPECHK(p.B > 0 && p.H > 0 && p.H <= 65535 && p.Sq >= 1 && p.Skv >= 1, "attention_edit: empty problem (B=%d H=%d Sq=%d Skv=%d)", p.B, p.H, p.Sq, p.Skv);
+  SHAPECHK(p.B <= 32, "attention_edit: at most 32 samples, src travels in the kernel arguments (B=%d)", p.B);
+  SHAPECHK(p.nd == 1, "attention_edit: head_dim 64 only (nd=%d)", p.nd);
+  SHAPECHK(p.Skv <= 96, "attention_edit: 1..96 keys (Skv=%d)", p.Skv);
+  SHAPECHK(p.Q && p.K && p.V && p.O, "attention_edit: null operand");
+  SHAPECHK(p.scale > 0.f && p.scale <= 3.0e38f, "attention_edit: a finite positive scale (%g)", (double)p.scale);
+  const int C = 64 * p.H;
+  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldq >= C && p.ldk >= C && p.ldv >= C,
+           "attention_edit: leading dimensions ldq / ldk / ldv must be multiples of 8 and hold every head (%d %d %d)", p.ldq, p.ldk, p.ldv);
+  SHAPECHK(p.ldo % 4 == 0 && p.ldo >= C, "attention_edit: ldo %% 4, ldo >= 64 H (ldo=%d)", p.ldo);
+  const unsigned long long in_bits = (unsigned long long)p.Q | (unsigned long long)p.K | (unsigned long long)p.V;
+  SHAPECHK(in_bits % 16 == 0 && (unsigned long long)p.O % 8 == 0, "attention_edit: Q / K / V 16-byte, O 8-byte aligned");
+  plan.n_edited = 0;
+  for (int b = 0; b < p.B; ++b)
+    if (p.src[b] == b) p.src[b] = -1;                              // its own source: not edited
+  for (int b = 0; b < p.B; ++b) {
+    const int s = p.src[b];
+    if (s < 0) continue;
+    SHAPECHK(s < p.B, "attention_edit: src[%d]=%d is out of range (a sample of the batch of %d, or negative for an unedited sample)", b, s, p.B);
+    SHAPECHK(p.src[s] < 0, "attention_edit: src[%d]=%d names a source that is itself edited (src[%d]=%d)", b, s, s, p.src[s]);
+    ++plan.n_edited;
+  }
+  if (plan.n_edited) {
+    SHAPECHK(p.Mt && p.c && p.d, "attention_edit: null table (Mt, c and d are needed while any sample is edited)");
+    SHAPECHK(p.ldm % 8 == 0 && p.ldm >= p.Skv, "attention_edit: leading dimension ldm must be a multiple of 8 and hold %d keys (ldm=%d)", p.Skv, p.ldm);
+    SHAPECHK((unsigned long long)p.Mt % 16 == 0 && ((unsigned long long)p.c | (unsigned long long)p.d) % 4 == 0,
+             "attention_edit: Mt 16-byte, c / d 4-byte aligned");
+  }
+  plan.kb = cdiv(p.Skv, 32);
+  plan.lds = 3 * plan.kb * 4096 + plan.kb * 32 * (plan.kb * 64 + 16) + plan.kb * 256 + 4 * 4096 + 8 * 4096;
+  AttnP& a = plan.plain;
+  a = AttnP();
+  a.Q = p.Q; a.ldq = p.ldq; a.K = p.K; a.ldk = p.ldk; a.V = p.V; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
+  a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
+  plan.pplan = AttnPlan();
+  const int rc = attn_plan(0, a, g_attn_env, plan.pplan);
+  if (rc) return rc;
+  const int k0 = plan.pplan.l[0].kernel;
+  plan.plain_first = !(plan.pplan.n == 1 && k0 >= AK_XFWD && k0 < AK_XFWD + 4);
+  // Units per workgroup, one count for the unedited samples' workgroups and one for the edited ones': ONE round of the
+  // workgroups per CU the LDS allows (the aim of attn_plan_maps and the regions launcher; NOT their formula, which has one count
+  // for all workgroups and left the edited ones as the critical path), and among the pairs that fit,
+  // the one whose longest workgroup is shortest by the times measured at 77 keys (profiles/EXPERIMENTS.md section 9, f11): an edited
+  // workgroup of u units 6.4 + 3.7 u us, a plain one 3.0 + 2.0 u.  Where not even one workgroup per (sample, head) fits in a
+  // round, each takes all units of its head.  The grid is 1-D and holds exactly the workgroups that have work.
+  const int nu = cdiv(p.Sq, 128), slots = 256 * (2 * plan.lds <= 160 * 1024 ? 2 : 1);
+  const long long n_ed = plan.n_edited, n_un = plan.plain_first ? 0 : p.B - n_ed;    // (plain first: the grid holds the edited samples only)
+  plan.upw = plan.upw_edit = nu;
+  long long best = -1;
+  for (int ue = 1; ue <= nu; ++ue) {
+    const long long left = slots - n_ed * p.H * cdiv(nu, ue);
+    if (left < n_un * p.H) continue;
+    int uu = nu;
+    if (n_un) {
+      const long long splits = left / (n_un * p.H);
+      uu = cdiv(nu, (int)(splits > nu ? nu : splits));
+    }
+    const long long te = EDIT_WG_FIXED + EDIT_WG_UNIT * ue, tu = n_un ? PLAIN_WG_FIXED + PLAIN_WG_UNIT * uu : 0, cost = te > tu ? te : tu;
+    if (best < 0 || cost < best) { best = cost; plan.upw = uu; plan.upw_edit = ue; }
+  }
+  plan.grid = dim3((unsigned)(p.H * (n_ed * cdiv(nu, plan.upw_edit) + n_un * cdiv(nu, plan.upw))));
+  return PEA_OK;
+}
+int launch_attention_fwd_edit(const AttnEditP& p0, hipStream_t s) {
+  AttnEditP p = p0;
+  AttnEditPlan plan;
+  int rc = attn_plan_edit(p, plan);
+  if (rc) return rc;
+  if (!plan.n_edited) return launch_attention_fwd(plan.plain, s);
+  if (plan.plain_first) {
+    rc = launch_attention_fwd(plan.plain, s);
+    if (rc) return rc;
+  }
+  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = 1; }
+  const double pairs = (double)(p.B + plan.n_edited) * p.H * (double)p.Sq * p.Skv;     // a second score product per edited sample
+  PROF_BEGIN(2, 4.0 * pairs * 64 + 2.0 * plan.n_edited * p.H * (double)p.Sq * p.Skv * p.Skv,
+             2.0 * p.H * 64 * ((2.0 * p.B + plan.n_edited) * p.Sq + (2.0 * p.B + plan.n_edited) * p.Skv), s);
+  switch (plan.kb) {
+    case 1: rc = launch_lds<xattn_edit_fwd_kernel<1>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit); break;
+    case 2: rc = launch_lds<xattn_edit_fwd_kernel<2>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit); break;
+    default: rc = launch_lds<xattn_edit_fwd_kernel<3>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit); break;
+  }
+  PROF_END(s);
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+extern "C" int pea_debug_attn_edit_dispatch(const int* q, int* out) {
+  static float page[64];
+  bf16* const any = (bf16*)page;
+  AttnEditP p = AttnEditP();
+  p.Q = p.K = p.V = any; p.O = any; p.scale = 0.125f;
+  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.Skv = q[3]; p.nd = q[4];
+  p.ldq = p.ldk = p.ldv = p.ldo = 64 * p.H;
+  if (q[5] > 0) p.ldk = q[5];
+  p.ldm = q[6] > 0 ? q[6] : (p.Skv + 7) / 8 * 8;
+  if (!(q[7] & 1)) { p.Mt = any; p.c = p.d = page; }
+  for (int b = 0; b < 32; ++b) p.src[b] = b < p.B ? q[8 + b] : -1;
+  AttnEditPlan plan;
+  const int rc = attn_plan_edit(p, plan);
+  if (rc) return rc;
+  out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
+  out[6] = plan.plain_first; out[7] = plan.upw_edit;
   return PEA_OK;
 }

@@ -257,6 +257,25 @@ struct Tape {
     }
   };
   MapState* maps = nullptr;
+  // Prompt-to-prompt editing (graph 0, inference only; api_model.hip: pea_unet_set_prompt_edit): the batch holds N prompts denoised
+  // from the same latents, src[b] >= 0 names the unedited source of sample b.  While this is set, a cross-attention on t_kvall is
+  // ONE launch_attention_fwd_edit at a step whose tables do anything (cd_live), the plain launch otherwise; a self-attention with
+  // at most self_max_tokens queries, while step < self_until, is its ordinary launch and one B = 1 launch per edited sample that
+  // overwrites O[b] with softmax(Q[s] K[s]^T) V[b].  The tape, the plans, the arenas and the attention census do not change.
+  // Outside the arenas: release_acts keeps the tables.
+  struct EditState {
+    int src[32];
+    int n_edited = 0, T = 0, step = 0, self_until = 0, self_max_tokens = 1024, ldm = 0;
+    bf16* Mt = nullptr;                        // device [B][L][ldm]
+    float* cd = nullptr;                       // device fp32 [T][2][B][L]
+    std::vector<char> cd_live;                 // per step (host): some edited sample has a c != 0 or a d != 1
+    ~EditState() {
+      if (Mt) (void)hipFree(Mt);
+      if (cd) (void)hipFree(cd);
+    }
+  };
+  EditState* edit = nullptr;
+  int edit_check(bool forward) const;          // what a context must be to run an edit (tape.hip)
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

@@ -154,6 +154,22 @@ struct AttnRegionsP {
   int nd;                          // padded head_dim / 64 (0 is read as 1); anything but 1 is refused
 };
 int launch_attention_fwd_regions(const AttnRegionsP& p, hipStream_t s);
+// Prompt-to-prompt editing, forward only, head_dim 64, 1..96 keys, B <= 32: sample b with src[b] = s >= 0 mixes the softmax
+// of its source s (an unedited sample of the same batch, at the same query positions) into its own before the value product,
+// A[q][j] = c[b][j] sum_k P0[q][k] Mt[b][j][k] + d[b][j] P1[q][j], O[b] = A V[b] (xattn_edit_fwd_kernel); src[b] < 0: plain
+// attention, no table row of that sample is read.  Mt: bf16 [B][Skv][ldm]; c, d: fp32 [B][Skv].  src travels in the kernel
+// arguments.  Its own launcher, shape checks and grid rule: the decision table of launch_attention_fwd / _bwd does not know it.
+struct AttnEditP {
+  const bf16 *Q, *K, *V; int ldq, ldk, ldv;
+  bf16* O; int ldo;
+  int B, H, Sq, Skv;
+  const bf16* Mt; int ldm;
+  const float *c, *d;
+  float scale; int q_prescaled;
+  int nd;                          // padded head_dim / 64 (0 is read as 1); anything but 1 is refused
+  int src[32];
+};
+int launch_attention_fwd_edit(const AttnEditP& p, hipStream_t s);
 // Cross-attention heat maps, head_dim 64, 1 <= Skv <= 128: maps[b][key][q] (op)= (1 / H) sum_h softmax_key(scale Q_h K_h^T), fp32
 // [B][Skv][Sq], (op) a store or (accumulate) a += by the thread that owns the element (xattn_maps_kernel, 512 threads; no V, no O, no lse).
 // Its own launcher, shape checks and grid rule: the decision table of launch_attention_fwd / _bwd does not know it.

@@ -270,6 +270,7 @@ Tape::~Tape() {
   delete ip;
   delete regions;
   delete maps;
+  delete edit;
 }
 
 int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s) {
@@ -578,6 +579,36 @@ int Tape::regions_check(int R, bool need_weights) const {
   return PEA_OK;
 }
 
+// Prompt-to-prompt editing: what the context must be.  Checked when the tables are set and again (forward) before the first launch
+// of a forward: image prompts, regions, map capture or per-sample context lengths may have arrived in between.
+int Tape::edit_check(bool forward) const {
+  const char* const who = forward ? "pea_unet_forward" : "pea_unet_set_prompt_edit";
+  if (needs_grad) {
+    pea_set_error("%s: prompt editing is an inference feature (no backward through it); this context was created with PEA_UNET_GRAD", who);
+    return PEA_E_STATE;
+  }
+  if (cross_kvlen) { pea_set_error("%s: prompt editing cannot be combined with per-sample context lengths", who); return PEA_E_STATE; }
+  if (ip)
+    for (int j = 0; j < ip->nsets; ++j)
+      if (ip->set[j].live) {
+        pea_set_error("%s: prompt editing cannot be combined with live image prompts (set %d; pea_unet_ip_clear)", who, j);
+        return PEA_E_STATE;
+      }
+  if (regions) { pea_set_error("%s: prompt editing cannot be combined with prompt regions (pea_unet_clear_prompt_regions)", who); return PEA_E_STATE; }
+  if (maps) { pea_set_error("%s: prompt editing cannot be combined with attention-map capture (pea_unet_disable_attention_maps)", who); return PEA_E_STATE; }
+  SHAPECHK(L >= 1 && L <= 96, "%s: prompt editing takes a context of 1..96 rows (L=%d)", who, L);
+  SHAPECHK(B <= 32, "%s: prompt editing takes a batch of at most 32 (B=%d)", who, B);
+  for (const Op& o : ops) {
+    if (o.kind != OP_ATTN || o.b != t_kvall) continue;
+    SHAPECHK(o.p3 == 1 && o.p2 == L, "%s: prompt editing needs head_dim 64 cross-attention over the whole context (nd=%d, %d keys)", who, o.p3, o.p2);
+  }
+  if (forward && (edit->step < 0 || edit->step >= edit->T)) {
+    pea_set_error("%s: prompt-edit step %d is outside 0..%d (pea_unet_set_prompt_edit_step)", who, edit->step, edit->T - 1);
+    return PEA_E_STATE;
+  }
+  return PEA_OK;
+}
+
 int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype, const void* text, int text_dtype,
                   const float* time_ids, float* eps, hipStream_t s) {
   std::string miss;
@@ -592,6 +623,7 @@ int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype
                   "a softmax per region; pea_unet_disable_attention_maps or pea_unet_clear_prompt_regions)");
     return PEA_E_STATE;
   }
+  if (edit) RC(edit_check(true));
   RC(ensure_acts());
   RC(ensure_folded(s));
   x_in = x; t_in = t; tid_in = time_ids; eps_out = eps;
@@ -816,8 +848,31 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
           RC(launch_attention_fwd_regions(r, s));
           break;
         }
+        if (edit && o.b == t_kvall && edit->cd_live[edit->step]) {   // prompt editing: the source's softmax mixed into the edited samples'
+          AttnEditP e = AttnEditP();                                  // (edit_check has passed; a step whose tables do nothing runs the plain launch)
+          e.Q = p.Q; e.ldq = p.ldq; e.K = p.K; e.ldk = p.ldk; e.V = p.V; e.ldv = p.ldv; e.O = p.O; e.ldo = p.ldo;
+          e.B = B; e.H = o.p0; e.Sq = o.p1; e.Skv = o.p2; e.scale = o.f0; e.q_prescaled = o.pre; e.nd = o.p3;
+          e.Mt = edit->Mt; e.ldm = edit->ldm;
+          e.c = edit->cd + (size_t)edit->step * 2 * B * L; e.d = e.c + (size_t)B * L;
+          memcpy(e.src, edit->src, sizeof(e.src));
+          RC(launch_attention_fwd_edit(e, s));
+          break;
+        }
         if (ip && o.b == t_kvall) RC(ip_attach(o, p));               // image prompts: the layer's own columns of the image K|V
         RC(launch_attention_fwd(p, s));
+        if (edit && graph == 0 && o.b != t_kvall && !o.mask && o.p1 == o.p2 && o.p1 <= edit->self_max_tokens && edit->step < edit->self_until) {
+          // prompt editing, self-attention: O[b] = softmax(Q[s] K[s]^T) V[b], one B = 1 launch per edited sample behind the
+          // ordinary one (unedited samples keep their bits by construction)
+          for (int b = 0; b < B; ++b) {
+            const int sb = edit->src[b];
+            if (sb < 0) continue;
+            AttnP e = p;
+            e.B = 1; e.lse = nullptr;
+            e.Q = p.Q + (size_t)sb * p.Sq * p.ldq; e.K = p.K + (size_t)sb * p.Skv * p.ldk;
+            e.V = p.V + (size_t)b * p.Skv * p.ldv; e.O = p.O + (size_t)b * p.Sq * p.ldo;
+            RC(launch_attention_fwd(e, s));
+          }
+        }
         if (maps && o.b == t_kvall) {                               // heat maps: the text softmax's head mean, added to the level's sum
           const auto lay = maps->layer_of_col.find(o.bcol);
           if (lay != maps->layer_of_col.end() && maps->on[lay->second]) {

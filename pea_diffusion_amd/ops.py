@@ -401,6 +401,33 @@ def attention_maps(q, k, heads, scale=None, q_prescaled=False, kv_len=None, out=
     return out.view(-1)[:n].view(B, Skv, Sq)
 
 
+def attention_fwd_edit(q, k, v, heads, src, Mt, c, d, q_prescaled=False, scale=None):
+    """Prompt-to-prompt editing in one launch over the batch (pea_op_attention_fwd_edit), head_dim 64, at most 96 keys, B <= 32:
+    sample b with s = src[b] >= 0:  o[b] = (c[b] * (softmax(scale q[s] k[s]^T) Mt[b]^T) + d[b] * softmax(scale q[b] k[b]^T)) v[b],
+    src[b] < 0: plain attention (the sample's table rows are never read).  q [B,Sq,H*64], k/v [B,Skv,>=H*64] bf16; src: B ints
+    (host); Mt bf16 [B,Skv,ldm>=Skv] (row = target key, column = source key; ldm a multiple of 8); c, d fp32 [B,Skv].  -> o."""
+    B, Sq, C, scale, o, _ = _attn_fwd_out(q, heads, scale, want_lse=False)
+    if C != heads * 64:
+        raise PeaError(f"attention_fwd_edit: head_dim {C // heads} (the kernel is built for 64)")
+    Skv = k.shape[1]
+    src = [int(x) for x in (src.tolist() if hasattr(src, "tolist") else src)]
+    if len(src) != B:
+        raise PeaError(f"attention_fwd_edit: {len(src)} sources for a batch of {B}")
+    hsrc = (ctypes.c_int * max(B, 1))(*src)
+    ldm = 0
+    if Mt is not None:
+        if Mt.dtype != BF or Mt.dim() != 3 or Mt.shape[0] != B or Mt.shape[1] != Skv or Mt.stride(2) != 1 or Mt.stride(0) != Skv * Mt.stride(1):
+            raise PeaError(f"attention_fwd_edit: Mt {tuple(Mt.shape)} {Mt.dtype}, expected bf16 [{B}, {Skv}, >= {Skv}] with dense rows")
+        ldm = Mt.stride(1)
+    for name, t in (("c", c), ("d", d)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (B, Skv) or not t.is_contiguous()):
+            raise PeaError(f"attention_fwd_edit: {name} {tuple(t.shape)} {t.dtype}, expected fp32 [{B}, {Skv}]")
+    check(lib().pea_op_attention_fwd_edit(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(v), v.stride(1), ptr(o), C, B, heads, Sq, Skv,
+                                          hsrc, None if Mt is None else ctypes.c_void_p(Mt.data_ptr()), ldm, ptr(c), ptr(d), scale,
+                                          int(q_prescaled), stream_ptr()))
+    return o
+
+
 def attention_fwd_fewq(q, k, v, k2=None, v2=None, heads=1, scale=None, q_prescaled=False, want_lse=False, kv_rows=None,
                        kv2_rows=None):
     """Few-query attention over the union of two key sets in one launch (pea_op_attention_fwd_fewq):

@@ -464,6 +464,35 @@ class HipUNet(HipTape):
             out[(h, w)] = (t, int(n.value))
         return out
 
+    def set_prompt_edit(self, edit, do_cfg=False):
+        """Prompt-to-prompt editing (`prompt2prompt.PromptEdit`): the batch of this UNet holds N prompts denoised from the same
+        latents, and sample b with edit.src[b] >= 0 takes its cross-attention probabilities partly from that source (word swap,
+        refinement, re-weighting) and, in the first steps, its self-attention probabilities in the layers with at most
+        edit.self_max_tokens queries.  do_cfg: the batch is [uncond x N | cond x N]; the tables of an edit composed without it are
+        laid out for it here.  The step is set with `set_prompt_edit_step`; holds until `clear_prompt_edit()`."""
+        if do_cfg:
+            edit = edit.with_cfg()
+        B, L = self.B, edit.Mt.shape[-1]
+        if L != self.L:                                        # the library copies B * L * L and T * 2 * B * L elements by ITS L
+            raise PeaError(f"set_prompt_edit: tables for a context of {L} rows, this UNet has {self.L} (compose the edit with "
+                           f"L = ctx_len, not the number of tokens)")
+        if edit.src.numel() != B or tuple(edit.Mt.shape) != (B, L, L) or tuple(edit.cd.shape[1:]) != (2, B, L):
+            raise PeaError(f"set_prompt_edit: tables for a batch of {edit.src.numel()} (Mt {tuple(edit.Mt.shape)}, cd "
+                           f"{tuple(edit.cd.shape)}), this UNet has batch {B}")
+        src = (ctypes.c_int * B)(*[int(x) for x in edit.src.tolist()])
+        Mt = edit.Mt.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        cd = edit.cd.to(device=self.device, dtype=torch.float32).contiguous()
+        check(lib().pea_unet_set_prompt_edit(self._h, src, ptr(Mt), ptr(cd), int(edit.cd.shape[0]), int(edit.self_until),
+                                             int(edit.self_max_tokens), stream_ptr()))
+
+    def set_prompt_edit_step(self, i):
+        """the denoising step the next forward belongs to (a host integer: nothing is transferred)"""
+        check(lib().pea_unet_set_prompt_edit_step(self._h, int(i)))
+
+    def clear_prompt_edit(self):
+        """back to plain attention; a forward then gives the bits it gave before"""
+        check(lib().pea_unet_clear_prompt_edit(self._h))
+
     def clear_ip_tokens(self, index=None):
         """back to plain cross-attention launches (index: for that adapter alone); the adapters' weights stay loaded"""
         if index is None:
