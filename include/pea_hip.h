@@ -925,6 +925,58 @@ int pea_unet_clear_prompt_edit(void* unet);
  * mapper; c and d; the O images; the Q images of both samples). */
 int pea_debug_attn_edit_dispatch(const int* q, int* out);
 
+/* ---- StyleAligned generation (Hertz et al. 2023, "Style Aligned Image Generation via Shared Attention"): a batch of N prompts
+ * denoised together keeps one style.  Sample b with ref[b] = r >= 0 is a TARGET of the reference r, a plain sample of the same batch
+ * (ref[b] < 0, or ref[b] = b, a sample that is its own reference: plain).  Everything below is per head, head_dim 64; a
+ * restatement from the paper and the authors' public code (unpinned).
+ * pea_op_attn_adain_coef: the AdaIN coefficients.  Q [B][S][ldq], K [B][S][ldk] bf16, C = 64 H columns each.  Over the S tokens of a
+ * sample, per channel, mu(X) the mean and sigma(X) = sqrt(var_unbiased(X) + eps); for a target b with reference r and X in {Q, K}
+ *   a = sigma(X[r]) / sigma(X[b]),  s = mu(X[r]) - a mu(X[b])          (AdaIN: X' = a o X + s)
+ * coef fp32 [B][4][C] = (a_q, s_q, a_k, s_k); a pair switched off (adain_queries / adain_keys = 0) is (1, 0); rows of plain samples
+ * are not written.  eps = 1e-5, and (scale log2 e)^2 1e-5 for a q_prescaled Q, whose statistics are those of q times scale log2 e.
+ * Sums of (x - x[row 0]) and its square in fp32, split over token slabs whose partials (scratch: pea_op_attn_adain_scratch_bytes,
+ * always needed while there is a target) are added in slab order: no atomics, the same bits every run.  PEA_E_SHAPE before any
+ * launch: B > 32, S < 2 while any sample is a target, ref[b] >= B, a reference that is itself a target, a leading dimension that is
+ * no multiple of 8, an empty problem, a null operand.  PEA_E_INVALID: null ref.  ref: HOST int[B]. */
+long long pea_op_attn_adain_scratch_bytes(int B, int H, int S);
+int pea_op_attn_adain_coef(const void* Q, int ldq, const void* K, int ldk, int B, int H, int S, const int* ref, float scale,
+                           int q_prescaled, int adain_queries, int adain_keys, float* coef, void* scratch, void* stream);
+/* pea_op_attention_fwd_shared, ONE launch over the whole batch, forward only, no lse, head_dim 64, Sq == Skv = S, B <= 32:
+ *   target b:  q' = a_q o q + s_q;  own scores  scale (q' o a_k) . K[b][j] + scale q' . s_k   ( = scale q' . (a_k o K[b][j] + s_k) ),
+ *              reference scores  shared_score_scale scale q' . K[r][j] + shared_score_shift,
+ *              O[b] = softmax over the 2 S scores . [V[b]; V[r]]
+ *   plain b:   O[b] = softmax(scale Q[b] K[b]^T) V[b], the bits of pea_op_attention_fwd; no coef row of that sample is read.
+ * K is never rewritten and nothing is concatenated: the own segment runs a second resident Q fragment set against the untouched K
+ * tiles with one constant per query in the accumulator operand, the reference's K and V are read in place.  coef: device fp32
+ * [B][4][64 H] from pea_op_attn_adain_coef, 16-byte aligned; null is accepted while no sample is a target.  ref: HOST int[B],
+ * validated before any launch and passed in the kernel arguments.  The workgroups of the targets, which run twice the key tiles,
+ * are dispatched first.  No atomics: the same bits every run.  ld* in elements, Q / K / V / O 16-byte aligned.  PEA_E_SHAPE before any
+ * launch: S < 2 while any sample is a target, Sq != Skv, nd != 1, B > 32, ref[b] >= B, a reference that is itself a target, a
+ * leading dimension that is no multiple of 8, null coef while any sample is a target, an empty problem.  PEA_E_INVALID: null ref. */
+int pea_op_attention_fwd_shared(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H,
+                                int Sq, int Skv, const int* ref, const float* coef, float scale, int q_prescaled,
+                                float shared_score_scale, float shared_score_shift, int nd, void* stream);
+/* The same in a UNet context (graph 0, inference), a runtime state like regions, maps and edits: the tape, the plans and the arenas
+ * do not change.  ref: host int[B] as above.  layer_on: one switch per SELF-attention layer in the order a forward runs them (down
+ * blocks, mid block, up blocks), non-zero = shared; null (n_layers ignored) = every layer; n_layers must equal
+ * pea_unet_num_self_attention_layers otherwise.  While set, every switched-on self-attention layer runs pea_op_attn_adain_coef over
+ * its Q and K columns and then pea_op_attention_fwd_shared instead of its plain launch; the coefficient buffer [B][4][widest layer]
+ * and the scratch are allocated here, once, outside the arenas.  Refused (PEA_E_STATE / PEA_E_SHAPE; by a forward too, before its
+ * first launch): a PEA_UNET_GRAD context, live prompt editing (whose self-attention rule rewrites the same outputs), B > 32, a
+ * self-attention layer whose head_dim is not 64 or that has fewer than 2 tokens.  Image prompts, regions, heat maps, FreeU and
+ * ControlNet residuals combine freely: they never see a self-attention launch.  Not a UNet handle, null ref: PEA_E_INVALID.  After
+ * pea_unet_clear_style_aligned a forward gives the bits it gave before. */
+int pea_unet_set_style_aligned(void* unet, const int* ref, const float* layer_on, int n_layers, int adain_queries, int adain_keys,
+                               float shared_score_scale, float shared_score_shift, void* stream);
+int pea_unet_clear_style_aligned(void* unet);
+int pea_unet_num_self_attention_layers(void* unet);      /* a count, or a negative error code */
+/* Test aid, needs no device: what pea_op_attention_fwd_shared launches (shape checks included).  q[39] = { B, H, Sq, Skv, nd, ldk
+ * (<= 0: 64 H, like every other leading dimension), flags (bit 0: null coef), ref[0..31] }.  Returns PEA_OK and out[8] = { grid x /
+ * y / z, dynamic LDS bytes, workgroups of target samples, workgroups of plain samples, 1 if the plain launch runs first and the
+ * kernel's grid holds the targets only, number of target samples }, or the error code of a refused problem.  The grid is 1-D: H x
+ * ceil(S / 128) workgroups per sample, the targets' first; y = z = 1.  LDS = 2 stages x (K tile + V tile) x 8192 bytes. */
+int pea_debug_attn_shared_dispatch(const int* q, int* out);
+
 #ifdef __cplusplus
 }
 #endif

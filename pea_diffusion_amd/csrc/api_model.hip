@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 
 #include "../../include/pea_hip.h"
 #include "model.h"
@@ -767,6 +768,74 @@ int pea_unet_clear_prompt_edit(void* h) {
   if (u->edit) HIPCHK(hipDeviceSynchronize());        // a queued forward may still read the tables
   delete u->edit;
   u->edit = nullptr;
+  return PEA_OK;
+}
+// ------------------------------------------------------------------------------ StyleAligned generation
+static int self_attn_layers(const Tape& u, std::map<int, int>* layer_of_op) {
+  int n = 0;
+  for (size_t i = 0; i < u.ops.size(); ++i)
+    if (u.is_self_attn(u.ops[i])) {
+      if (layer_of_op) (*layer_of_op)[(int)i] = n;
+      ++n;
+    }
+  return n;
+}
+int pea_unet_num_self_attention_layers(void* h) {
+  NOTNULL(h, "pea_unet_num_self_attention_layers");
+  return self_attn_layers(*(Tape*)h, nullptr);
+}
+int pea_unet_set_style_aligned(void* h, const int* ref, const float* layer_on, int n_layers, int adain_queries, int adain_keys,
+                               float shared_score_scale, float shared_score_shift, void* stream) {
+  NOTNULL(h, "pea_unet_set_style_aligned");
+  Tape* u = (Tape*)h;
+  if (u->graph != 0) { pea_set_error("pea_unet_set_style_aligned: not a UNet handle (graph %d)", u->graph); return PEA_E_INVALID; }
+  if (!ref) { pea_set_error("pea_unet_set_style_aligned: null ref (a host int[B]; negative entries for plain samples)"); return PEA_E_INVALID; }
+  RCX(u->style_check(false));
+  const int B = u->B;
+  SHAPECHK(shared_score_scale == shared_score_scale && shared_score_shift == shared_score_shift && fabsf(shared_score_scale) <= 3.0e38f &&
+               fabsf(shared_score_shift) <= 1.0e30f,
+           "pea_unet_set_style_aligned: finite shared_score_scale / shared_score_shift (%g %g)", (double)shared_score_scale, (double)shared_score_shift);
+  Tape::StyleState* st = new Tape::StyleState();
+  std::unique_ptr<Tape::StyleState> guard(st);
+  for (int b = 0; b < 32; ++b) st->ref[b] = -1;
+  for (int b = 0; b < B; ++b) {
+    if (ref[b] < 0 || ref[b] == b) continue;                       // (its own reference: plain)
+    SHAPECHK(ref[b] < B, "pea_unet_set_style_aligned: ref[%d]=%d is out of range (batch %d)", b, ref[b], B);
+    SHAPECHK(ref[ref[b]] < 0 || ref[ref[b]] == ref[b], "pea_unet_set_style_aligned: ref[%d]=%d names a reference that is itself a target", b, ref[b]);
+    st->ref[b] = ref[b];
+    ++st->n_targets;
+  }
+  const int want = self_attn_layers(*u, &st->layer_of_op);
+  if (layer_on && n_layers != want) {
+    pea_set_error("pea_unet_set_style_aligned: %d layer switches, this UNet has %d self-attention layers", n_layers, want);
+    return PEA_E_SHAPE;
+  }
+  st->on.assign(want, 1);
+  for (int i = 0; layer_on && i < want; ++i) st->on[i] = layer_on[i] != 0.f;
+  st->adain_q = adain_queries != 0; st->adain_k = adain_keys != 0;
+  st->share_scale = shared_score_scale; st->share_shift = shared_score_shift;
+  size_t coef_bytes = 0, scratch_bytes = 0;
+  for (const Op& o : u->ops) {
+    if (!u->is_self_attn(o)) continue;
+    coef_bytes = std::max(coef_bytes, sizeof(float) * (size_t)B * 4 * 64 * o.p0);
+    scratch_bytes = std::max(scratch_bytes, attn_adain_scratch_bytes(B, o.p0, o.p1));
+  }
+  RCX(pea_unet_clear_style_aligned(h));
+  if (st->n_targets && coef_bytes) {
+    hipError_t err = hipMalloc((void**)&st->coef, coef_bytes);
+    if (err == hipSuccess) err = hipMalloc((void**)&st->scratch, std::max(scratch_bytes, (size_t)16));
+    if (err != hipSuccess) { pea_set_error("pea_unet_set_style_aligned: %s", hipGetErrorString(err)); return PEA_E_HIP; }
+  }
+  (void)stream;                                                     // nothing is transferred: ref is a host table
+  u->style = guard.release();
+  return PEA_OK;
+}
+int pea_unet_clear_style_aligned(void* h) {
+  NOTNULL(h, "pea_unet_clear_style_aligned");
+  Tape* u = (Tape*)h;
+  if (u->style && u->style->coef) HIPCHK(hipDeviceSynchronize());   // a queued forward may still use the buffers
+  delete u->style;
+  u->style = nullptr;
   return PEA_OK;
 }
 // ------------------------------------------------------------------------------ cross-attention heat maps

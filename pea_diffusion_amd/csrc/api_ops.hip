@@ -333,6 +333,26 @@ int pea_op_attention_fwd_edit(const void* Q, int ldq, const void* K, int ldk, co
   for (int b = 0; b < 32; ++b) p.src[b] = b < B ? src[b] : -1;      // (B > 32 is refused by the launcher)
   return launch_attention_fwd_edit(p, (hipStream_t)stream);
 }
+// StyleAligned shared self-attention (attention.hip: attn_adain_part_kernel / attn_adain_coef_kernel, attn_shared_kernel)
+long long pea_op_attn_adain_scratch_bytes(int B, int H, int S) { return (long long)attn_adain_scratch_bytes(B, H, S); }
+int pea_op_attn_adain_coef(const void* Q, int ldq, const void* K, int ldk, int B, int H, int S, const int* ref, float scale,
+                           int q_prescaled, int adain_queries, int adain_keys, float* coef, void* scratch, void* stream) {
+  if (!ref) { pea_set_error("pea_op_attn_adain_coef: null ref (a host int[B]; negative entries for plain samples)"); return PEA_E_INVALID; }
+  return launch_attn_adain_coef((const bf16*)Q, ldq, (const bf16*)K, ldk, B, H, S, ref, scale, q_prescaled, adain_queries, adain_keys,
+                                coef, (float*)scratch, (hipStream_t)stream);
+}
+int pea_op_attention_fwd_shared(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H,
+                                int Sq, int Skv, const int* ref, const float* coef, float scale, int q_prescaled,
+                                float shared_score_scale, float shared_score_shift, int nd, void* stream) {
+  if (!ref) { pea_set_error("pea_op_attention_fwd_shared: null ref (a host int[B]; negative entries for plain samples)"); return PEA_E_INVALID; }
+  AttnSharedP p = AttnSharedP();
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.coef = coef; p.scale = scale; p.q_prescaled = q_prescaled;
+  p.share_scale = shared_score_scale; p.share_shift = shared_score_shift; p.nd = nd;
+  for (int b = 0; b < 32; ++b) p.ref[b] = b < B ? ref[b] : -1;      // (B > 32 is refused by the launcher)
+  return launch_attention_fwd_shared(p, (hipStream_t)stream);
+}
 int pea_op_attention_fwd_fewq(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* K2, int ldk2,
                               const void* V2, int ldv2, void* O, int ldo, float* lse, int B, int H, int Sq, int Skv, int Skv2,
                               float scale, int nd, int q_prescaled, void* stream) {

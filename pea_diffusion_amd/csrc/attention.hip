@@ -26,6 +26,10 @@
 // Heat maps (the head-mean cross-attention probabilities of a layer, fp32 [B][Skv][Sq], no V / O / lse): xattn_maps_kernel deals
 // the HEADS of a 32-query block over a workgroup's eight waves and adds their partial sums in a fixed order; its launcher, like the
 // regional one, stands beside the decision table.
+// StyleAligned shared self-attention (bottom of the file): attn_shared_kernel runs the forward loop of attn_q_body over the keys of
+// a target sample and then over its reference's, with a second resident Q fragment set and a per-segment constant in the C operand
+// of the S^T products; plain samples of the same launch run attn_q_body itself.  attn_adain_part_kernel / attn_adain_coef_kernel
+// make the per-channel coefficients it reads.  Their launchers, too, stand beside the decision table.
 // The three backward cross-attention kernels take their per-workgroup context (unit range, operand rows of the head, key
 // count, score factor) from xattn_ctx.  They still repeat, as text: K / V staging, the unit stage (stage_unit / fetch_o /
 // unit_head), the key-on-the-lane task, the query-on-the-lane key-block step, and the dQ and dK / dV exits -- so a fix to
@@ -3538,5 +3542,475 @@ extern "C" int pea_debug_attn_edit_dispatch(const int* q, int* out) {
   if (rc) return rc;
   out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
   out[6] = plan.plain_first; out[7] = plan.upw_edit;
+  return PEA_OK;
+}
+
+// ============================================================================= StyleAligned: shared self-attention
+// (Hertz et al. 2023.)  Target sample b with reference r: its queries and keys are moved onto r's per-channel statistics (AdaIN,
+// X' = a o X + s) and it attends to r's keys and values as well as its own, under one softmax.  Nothing of that is materialised:
+//   q' . (a_k o k + s_k) = (q' o a_k) . k + q' . s_k
+// so the own segment is a second resident Q fragment set (q' o a_k) against the untouched K tiles plus ONE constant per query,
+// which enters where -m_run enters, in the C operand of the S^T MFMAs; the reference segment is the fragment set
+// share_scale q' against K[r] with the constant share_shift log2(e).  K and V of both samples are staged by the same DMA from
+// where the projection wrote them: the reference's tiles differ in the base address of the buffer resource only.
+//
+// ---- the coefficients: column statistics over the tokens, split over token slabs, merged in slab order (no atomics)
+#define ADAIN_CG 16                // 8-channel column groups of a workgroup: 256 contiguous bytes of every row
+#define ADAIN_RL 16                // row lanes: thread (rl, cg) takes rows rl, rl + 16, ... of its slab
+struct AdainP {
+  const bf16 *Q, *K; int ldq, ldk;
+  int B, C, S, rps, nslab;
+  float epsq, epsk; int adain_q, adain_k;
+  unsigned used;                   // bit b: sample b is a target or a reference (the others are not read)
+  float* part;                     // [B][2][nslab][2][C]: sums of (x - x[row 0]) and of its square, X = Q then K
+  float* coef;
+  int ref[32];
+};
+__global__ __launch_bounds__(256) void attn_adain_part_kernel(const AdainP p) {
+  __shared__ float red[2][ADAIN_RL][ADAIN_CG * 8];
+  const int b = blockIdx.z >> 1, x = blockIdx.z & 1, slab = blockIdx.y;
+  if (!(p.used >> b & 1)) return;                                   // (workgroup-uniform)
+  const int tid = threadIdx.x, cg = tid & (ADAIN_CG - 1), rl = tid / ADAIN_CG;
+  const int col = (blockIdx.x * ADAIN_CG + cg) * 8, ld = x ? p.ldk : p.ldq;
+  const bf16* X = (x ? p.K : p.Q) + (long long)b * p.S * ld;
+  float s1[8], s2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
+  if (col < p.C) {
+    // the shift: the channel's value in row 0 of the sample, the same for every slab, so the slabs' sums add up
+    const bf16x8 sh = *(const bf16x8*)(X + col);
+    const int r1 = min(p.S, (slab + 1) * p.rps);
+    for (int r = slab * p.rps + rl; r < r1; r += ADAIN_RL) {
+      const bf16x8 v = *(const bf16x8*)(X + (long long)r * ld + col);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = (float)v[j] - (float)sh[j];
+        s1[j] += d;
+        s2[j] = fmaf(d, d, s2[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { red[0][rl][cg * 8 + j] = s1[j]; red[1][rl][cg * 8 + j] = s2[j]; }
+  __syncthreads();
+  const int k = tid >> 7, cc = tid & 127, oc = blockIdx.x * (ADAIN_CG * 8) + cc;
+  if (oc < p.C) {
+    float t = 0.f;
+    for (int i = 0; i < ADAIN_RL; ++i) t += red[k][i][cc];
+    p.part[((((long long)b * 2 + x) * p.nslab + slab) * 2 + k) * p.C + oc] = t;
+  }
+}
+__global__ __launch_bounds__(256) void attn_adain_coef_kernel(const AdainP p) {
+  const int i = blockIdx.x * 256 + threadIdx.x;                     // one thread per (sample, X, channel)
+  if (i >= p.B * 2 * p.C) return;
+  const int c = i % p.C, x = (i / p.C) & 1, b = i / (2 * p.C), r = p.ref[b];
+  if (r < 0) return;
+  float* out = p.coef + ((long long)b * 4 + 2 * x) * p.C + c;
+  if (!(x ? p.adain_k : p.adain_q)) { out[0] = 1.f; out[p.C] = 0.f; return; }
+  const bf16* X = x ? p.K : p.Q;
+  const int ld = x ? p.ldk : p.ldq;
+  const float n = (float)p.S, eps = x ? p.epsk : p.epsq;
+  float mu[2], sg[2];
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const int bb = w ? r : b;
+    const float* pp = p.part + (((long long)bb * 2 + x) * p.nslab) * 2 * p.C + c;
+    float S1 = 0.f, S2 = 0.f;
+    for (int sl = 0; sl < p.nslab; ++sl) { S1 += pp[(long long)(2 * sl) * p.C]; S2 += pp[(long long)(2 * sl + 1) * p.C]; }
+    const float d = S1 / n;
+    mu[w] = (float)X[(long long)bb * p.S * ld + c] + d;
+    sg[w] = sqrtf(fmaxf(S2 - S1 * d, 0.f) / (n - 1.f) + eps);
+  }
+  const float a = sg[1] / sg[0];
+  out[0] = a;
+  out[p.C] = mu[1] - a * mu[0];
+}
+// token rows per slab: about two workgroups per CU over the samples that are read, a slab of at least 64 rows (four per row lane)
+static int adain_rows_per_slab(int B, int H, int S) {
+  const int wg = 2 * B * cdiv(8 * H, ADAIN_CG);
+  const int want = std::max(1, cdiv(512, wg));
+  return std::min(std::max(S, 1), cdiv(std::max(cdiv(S, want), 64), ADAIN_RL) * ADAIN_RL);
+}
+static int adain_shapechk(int B, int H, int S) {
+  SHAPECHK(B >= 1 && H >= 1 && H <= 4096 && S >= 1, "attn_adain_coef: empty problem (B=%d H=%d S=%d)", B, H, S);
+  SHAPECHK(B <= 32, "attn_adain_coef: at most 32 samples, ref travels in the kernel arguments (B=%d)", B);
+  return PEA_OK;
+}
+size_t attn_adain_scratch_bytes(int B, int H, int S) {
+  if (adain_shapechk(B, H, S) != PEA_OK) return 0;
+  return sizeof(float) * (size_t)B * 2 * cdiv(S, adain_rows_per_slab(B, H, S)) * 2 * 64 * H;
+}
+// ref as the shared launcher reads it: ref[b] == b is a plain sample; -> bit masks of the targets and of everything that is read
+static int shared_ref_check(const char* who, const int* ref, int B, unsigned& targets, unsigned& used) {
+  targets = used = 0;
+  for (int b = 0; b < B; ++b) {
+    const int r = ref[b];
+    if (r < 0 || r == b) continue;
+    SHAPECHK(r < B, "%s: ref[%d]=%d is out of range (a sample of the batch of %d, or negative for a plain sample)", who, b, r, B);
+    const int rr = ref[r];
+    SHAPECHK(rr < 0 || rr == r, "%s: ref[%d]=%d names a reference that is itself a target (ref[%d]=%d)", who, b, r, r, rr);
+    targets |= 1u << b;
+    used |= 1u << b | 1u << r;
+  }
+  return PEA_OK;
+}
+int launch_attn_adain_coef(const bf16* Q, int ldq, const bf16* K, int ldk, int B, int H, int S, const int* ref, float scale,
+                           int q_prescaled, int adain_queries, int adain_keys, float* coef, float* scratch, hipStream_t s) {
+  if (int rc = adain_shapechk(B, H, S)) return rc;
+  AdainP p = AdainP();
+  unsigned targets = 0;
+  if (int rc = shared_ref_check("attn_adain_coef", ref, B, targets, p.used)) return rc;
+  if (!targets) return PEA_OK;                                      // no target: no row to write
+  SHAPECHK(S >= 2, "attn_adain_coef: the unbiased variance needs at least two tokens (S=%d)", S);
+  const int C = 64 * H;
+  SHAPECHK(ldq % 8 == 0 && ldk % 8 == 0 && ldq >= C && ldk >= C,
+           "attn_adain_coef: leading dimensions ldq / ldk must be multiples of 8 and hold every head (%d %d)", ldq, ldk);
+  SHAPECHK(Q && K && coef && scratch, "attn_adain_coef: null operand (Q, K, coef and the scratch of attn_adain_scratch_bytes)");
+  SHAPECHK(((unsigned long long)Q | (unsigned long long)K) % 16 == 0 && ((unsigned long long)coef | (unsigned long long)scratch) % 4 == 0,
+           "attn_adain_coef: Q / K 16-byte, coef / scratch 4-byte aligned");
+  SHAPECHK(scale > 0.f && scale <= 3.0e38f, "attn_adain_coef: a finite positive scale (%g)", (double)scale);
+  p.Q = Q; p.K = K; p.ldq = ldq; p.ldk = ldk; p.B = B; p.C = C; p.S = S;
+  p.rps = adain_rows_per_slab(B, H, S); p.nslab = cdiv(S, p.rps);
+  const float c = scale * LOG2E;
+  p.epsk = 1e-5f; p.epsq = q_prescaled ? c * c * 1e-5f : 1e-5f;
+  p.adain_q = adain_queries; p.adain_k = adain_keys; p.part = scratch; p.coef = coef;
+  for (int b = 0; b < 32; ++b) p.ref[b] = (targets >> b & 1) ? ref[b] : -1;
+  PROF_BEGIN(6, 6.0 * B * S * C, 4.0 * B * S * C, s);
+  hipLaunchKernelGGL(attn_adain_part_kernel, dim3(cdiv(C / 8, ADAIN_CG), p.nslab, 2 * B), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(attn_adain_coef_kernel, dim3(cdiv(B * 2 * C, 256)), dim3(256), 0, s, p);
+  PROF_END(s);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
+// ---- the forward.  A target's workgroup is attn_q_body's forward loop (same tiles, same fragment addresses, same online softmax)
+// run over 2 ceil(S / 64) key tiles: first the sample's own, then the reference's.  `segc` is the segment's score constant in the
+// log2 domain (q' . s_k, then share_shift log2 e): rowc = segc - m_run, rebuilt where the loop changes segment and in the rescale
+// branch.  Each segment's last tile is masked at S.
+__device__ __forceinline__ void attn_shared_body(const AttnSharedP& p, char* smem, int blk_x, int head, int b, int r) {
+  constexpr int STG = 2 * TILE_BYTES;                            // smem: [2 stages][K tile | V tile]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q0 = blk_x * 128 + wave * 32;
+  const int frow = lane & 31, fh = lane >> 5;
+  const int S = p.Sq, C = 64 * p.H;
+  const float cq = p.q_prescaled ? 1.f : p.scale * LOG2E;        // what takes q into the log2 domain
+
+  const bf16* Qb = p.Q + (long long)b * S * p.ldq + head * 64;
+  int qrow = q0 + frow;
+  const bool qvalid = qrow < S;
+  qrow = qvalid ? qrow : S - 1;
+  // both resident fragment sets from ONE read of the query row, each rounded to bf16 once from fp32; the own segment's constant
+  // from the fp32 q' (this lane holds 32 of the 64 channels, its partner half the others)
+  bf16x8 qo[4], qr[4];
+  float kc = 0.f;
+  {
+    const float* cf = p.coef + (long long)b * 4 * C + head * 64 + 8 * fh;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const bf16x8 qv = *(const bf16x8*)(Qb + (long long)qrow * p.ldq + 16 * s + 8 * fh);
+#pragma unroll
+      for (int h4 = 0; h4 < 2; ++h4) {
+        const f32x4 aq = *(const f32x4*)(cf + 16 * s + 4 * h4), sq = *(const f32x4*)(cf + C + 16 * s + 4 * h4);
+        const f32x4 ak = *(const f32x4*)(cf + 2 * C + 16 * s + 4 * h4), sk = *(const f32x4*)(cf + 3 * C + 16 * s + 4 * h4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float qp = fmaf(aq[j], (float)qv[4 * h4 + j], sq[j]) * cq;
+          qo[s][4 * h4 + j] = (bf16)(qp * ak[j]);
+          qr[s][4 * h4 + j] = (bf16)(qp * p.share_scale);
+          kc = fmaf(qp, sk[j], kc);
+        }
+      }
+    }
+    float ka = kc, kb = kc;
+    swap_halves32(ka, kb);
+    kc = ka + kb;
+  }
+  float segc = kc;
+  f32x16 rowc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) rowc[i] = segc;
+
+  f32x16 oacc[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int i2 = 0; i2 < 16; ++i2) oacc[i][i2] = 0.f;
+  float m_run = 0.f, l_run = 0.f;
+
+  const TileSrc ko = tile_src(p.K + (long long)b * S * p.ldk + head * 64, p.ldk, S, wave, lane);
+  const TileSrc vo = tile_src(p.V + (long long)b * S * p.ldv + head * 64, p.ldv, S, wave, lane);
+  const TileSrc kr = tile_src(p.K + (long long)r * S * p.ldk + head * 64, p.ldk, S, wave, lane);
+  const TileSrc vr = tile_src(p.V + (long long)r * S * p.ldv + head * 64, p.ldv, S, wave, lane);
+  const int nt = (S + 63) / 64;
+  stage_tile(ko, 0, smem, wave);
+  stage_tile(vo, 0, smem + TILE_BYTES, wave);
+  WAIT_VM0();
+  __syncthreads();
+
+  int rf_off[4], tr_off[2][2];                                   // per-lane LDS byte offsets (attn_q_body)
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
+  {
+    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
+  }
+
+  for (int t = 0; t < 2 * nt; ++t) {
+    const int cur = t & 1;
+    const bool own = t < nt;                                     // workgroup-uniform
+    if (t + 1 < 2 * nt) {
+      char* dst = smem + (cur ^ 1) * STG;
+      if (t + 1 < nt) {
+        stage_tile(ko, (t + 1) * 64, dst, wave);
+        stage_tile(vo, (t + 1) * 64, dst + TILE_BYTES, wave);
+      } else {
+        stage_tile(kr, (t + 1 - nt) * 64, dst, wave);
+        stage_tile(vr, (t + 1 - nt) * 64, dst + TILE_BYTES, wave);
+      }
+    }
+    if (t == nt) {                                               // the reference segment begins: its constant in the C operand
+      segc = p.share_shift * LOG2E;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) rowc[i] = segc - m_run;
+    }
+    int rfc[4], trc[2][2];
+    {
+      const int sb = cur * STG, tb = sb + TILE_BYTES;
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) rfc[s4] = rf_off[s4] + sb;
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int hl = 0; hl < 2; ++hl) trc[db][hl] = tr_off[db][hl] + tb;
+    }
+    f32x16 sacc[2];
+    {
+      bf16x8 kfr[2][4];
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) kfr[kb][s] = *(const bf16x8*)(smem + rfc[s] + kb * 4096);
+      __builtin_amdgcn_sched_barrier(0);
+      if (own) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb)
+            sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][s], qo[s], s == 0 ? rowc : sacc[kb], 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb)
+            sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][s], qr[s], s == 0 ? rowc : sacc[kb], 0, 0, 0);
+      }
+    }
+    const int kv0 = (own ? t : t - nt) * 64;                     // key index inside the segment
+    if (kv0 + 64 > S) {                                          // the segment's last tile, where it is ragged
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int key = kv0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * fh;
+          sacc[kb][i] = key < S ? sacc[kb][i] : -INFINITY;
+        }
+    }
+    float mx = fmaxf(sacc[0][0], sacc[1][0]);
+#pragma unroll
+    for (int i = 1; i < 16; ++i) mx = fmaxf(fmaxf(mx, sacc[0][i]), sacc[1][i]);
+    mx = xhalf_max(mx);
+    const bool first = t == 0;
+    const bool moved = first || mx > ATTN_MOVE_THR;
+    if (__any(moved)) {
+      const float mrel = moved ? mx : 0.f;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sacc[kb][i] -= mrel;
+      const float alpha = first ? 0.f : fast_exp2(-mrel);
+      l_run *= alpha;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int i2 = 0; i2 < 16; ++i2) oacc[i][i2] *= alpha;
+      m_run += mrel;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) rowc[i] = segc - m_run;
+    }
+    float ls = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float e = fast_exp2(sacc[kb][i]);
+        sacc[kb][i] = e;
+        ls += e;
+      }
+    l_run += ls;
+    bf16x8 pf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pf[ks][j] = (bf16)sacc[ks >> 1][8 * (ks & 1) + j];
+    {
+      bf16x8 tfr[4][2];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+          tfr[ks][db] = read_transposed_frag_at(smem + trc[db][0] + ks * 2048, smem + trc[db][1] + ks * 2048);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int db = 0; db < 2; ++db) oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfr[ks][db], pf[ks], oacc[db], 0, 0, 0);
+    }
+    WAIT_VM0();
+    __syncthreads();
+  }
+
+  // epilogue (attn_q_body): normalise, through a per-wave LDS image, whole 128-byte rows out
+  float la = l_run, lb = l_run;
+  swap_halves32(la, lb);
+  const float inv = 1.f / (la + lb);
+  char* const ost = smem + wave * (32 * 144);
+  const int r8 = lane >> 3, ch = lane & 7;
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      bf16x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = (bf16)(oacc[db][4 * g + j] * inv);
+      *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
+    }
+  bf16* Ob = p.O + (long long)b * S * p.ldo + head * 64 + ch * 8;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = i * 8 + r8;
+    if (q0 + row < S) *(bf16x8*)(Ob + (long long)(q0 + row) * p.ldo) = *(const bf16x8*)(ost + row * 144 + ch * 16);
+  }
+}
+
+// attn_block_coords' rule on a 1-D range of `total` workgroups: dispatch position -> position in an order where each XCD runs
+// one contiguous stretch (positions are dealt to the 8 XCDs round-robin)
+__device__ __forceinline__ unsigned xcd_contiguous(unsigned lin, unsigned total) {
+  const unsigned q = total >> 3, r = total & 7, xcd = lin & 7, j = lin >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+// One launch over the batch, 1-D grid: the n_tgt_wg workgroups of the target samples come FIRST in dispatch order (they run twice
+// the key tiles of a plain one, so the tail of the launch is made of short workgroups), then those of the plain samples.  Inside
+// each of the two ranges the XCD rule above holds, so the query blocks of a (sample, head) -- which stream the same K and V, for a
+// target its reference's too -- share an L2.  order[]: the samples in that order.  A plain workgroup is attn_q_body itself on an
+// AttnP made of the same operands: the bits of attn_q_kernel<0, true, 1>.
+__global__ __launch_bounds__(256, 3) void attn_shared_kernel(const AttnSharedP p, int n_tgt_wg) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const unsigned nu = (unsigned)(p.Sq + 127) >> 7, per = nu * p.H, i = blockIdx.x, nt = (unsigned)n_tgt_wg;
+  const bool tgt = i < nt;
+  const unsigned lin = tgt ? xcd_contiguous(i, nt) : nt + xcd_contiguous(i - nt, gridDim.x - nt);
+  const unsigned slot = lin / per, rem = lin - slot * per;
+  const int head = (int)(rem / nu), blk = (int)(rem - head * nu), b = p.order[slot];
+  if (tgt) {
+    attn_shared_body(p, smem, blk, head, b, p.ref[b]);
+  } else {
+    AttnP a = AttnP();
+    a.Q = p.Q; a.K = p.K; a.V = p.V; a.ldq = p.ldq; a.ldk = p.ldk; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
+    a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
+    attn_q_body<0, true, 1, false, true>(a, smem, blk, head, b);
+  }
+}
+
+// ---- host.  A launcher of its own beside the decision table, like the regions, maps and edit launchers.
+// plain_first: the plain workgroups above give attn_q_kernel<0, true, 1>'s bits.  Where pea_op_attention_fwd of the same problem
+// is another kernel (S = 128: the resident-key kernel; the gather instance under pea_debug_set_attn_tr(0)), that launch runs first
+// over the whole batch and the shared kernel's grid holds the targets only, so a plain sample keeps pea_op_attention_fwd's bits
+// at every shape.  With no target at all the plain launch is all there is.
+struct AttnSharedPlan { int lds, n_tgt, n_tgt_wg, n_plain_wg, plain_first; dim3 grid; AttnP plain; AttnPlan pplan; };
+static int attn_plan_shared(AttnSharedP& p, AttnSharedPlan& plan) {
+  if (p.nd == 0) p.nd = 1;
+  SHAPECHK(p.B > 0 && p.H > 0 && p.H <= 65535 && p.Sq >= 1 && p.Skv >= 1, "attention_shared: empty problem (B=%d H=%d Sq=%d Skv=%d)", p.B, p.H, p.Sq, p.Skv);
+  SHAPECHK(p.B <= 32, "attention_shared: at most 32 samples, ref travels in the kernel arguments (B=%d)", p.B);
+  SHAPECHK(p.nd == 1, "attention_shared: head_dim 64 only (nd=%d)", p.nd);
+  SHAPECHK(p.Sq == p.Skv, "attention_shared: self-attention only, Sq == Skv (Sq=%d Skv=%d)", p.Sq, p.Skv);
+  SHAPECHK(p.Q && p.K && p.V && p.O, "attention_shared: null operand");
+  SHAPECHK(p.scale > 0.f && p.scale <= 3.0e38f, "attention_shared: a finite positive scale (%g)", (double)p.scale);
+  const int C = 64 * p.H;
+  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldq >= C && p.ldk >= C && p.ldv >= C,
+           "attention_shared: leading dimensions ldq / ldk / ldv must be multiples of 8 and hold every head (%d %d %d)", p.ldq, p.ldk, p.ldv);
+  SHAPECHK(p.ldo % 8 == 0 && p.ldo >= C, "attention_shared: leading dimension ldo must be a multiple of 8 and hold every head (ldo=%d)", p.ldo);
+  const unsigned long long bits = (unsigned long long)p.Q | (unsigned long long)p.K | (unsigned long long)p.V | (unsigned long long)p.O;
+  SHAPECHK(bits % 16 == 0, "attention_shared: Q / K / V / O 16-byte aligned");
+  unsigned targets = 0, used = 0;
+  if (int rc = shared_ref_check("attention_shared", p.ref, p.B, targets, used)) return rc;
+  plan.n_tgt = __builtin_popcount(targets);
+  for (int b = 0; b < 32; ++b)
+    if (!(targets >> b & 1)) p.ref[b] = -1;                        // (its own reference, or past the batch: plain)
+  if (plan.n_tgt) {
+    SHAPECHK(p.Sq >= 2, "attention_shared: a target needs S >= 2, the unbiased variance of its AdaIN has no value at one token (S=%d)", p.Sq);
+    SHAPECHK(p.coef != nullptr, "attention_shared: null coef (the AdaIN coefficients are needed while any sample is a target)");
+    SHAPECHK((unsigned long long)p.coef % 16 == 0, "attention_shared: coef 16-byte aligned");
+    SHAPECHK(p.share_scale == p.share_scale && p.share_shift == p.share_shift && fabsf(p.share_scale) <= 3.0e38f && fabsf(p.share_shift) <= 1.0e30f,
+             "attention_shared: finite shared_score_scale / shared_score_shift (%g %g)", (double)p.share_scale, (double)p.share_shift);
+  }
+  plan.lds = 2 * 2 * TILE_BYTES;
+  AttnP& a = plan.plain;
+  a = AttnP();
+  a.Q = p.Q; a.ldq = p.ldq; a.K = p.K; a.ldk = p.ldk; a.V = p.V; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
+  a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
+  plan.pplan = AttnPlan();
+  if (int rc = attn_plan(0, a, g_attn_env, plan.pplan)) return rc;
+  plan.plain_first = !(plan.pplan.n == 1 && plan.pplan.l[0].kernel == AK_Q + 3);
+  const int nu = cdiv(p.Sq, 128);
+  int n = 0;
+  for (int b = 0; b < p.B; ++b)
+    if (targets >> b & 1) p.order[n++] = b;
+  for (int b = 0; b < p.B && !plan.plain_first; ++b)
+    if (!(targets >> b & 1)) p.order[n++] = b;
+  for (int b = n; b < 32; ++b) p.order[b] = 0;
+  const long long tw = (long long)plan.n_tgt * p.H * nu, pw = (long long)(n - plan.n_tgt) * p.H * nu;
+  SHAPECHK(tw + pw <= 0x7fffffffLL, "attention_shared: %lld workgroups", tw + pw);
+  plan.n_tgt_wg = (int)tw; plan.n_plain_wg = (int)pw;
+  plan.grid = dim3((unsigned)(tw + pw));
+  return PEA_OK;
+}
+int launch_attention_fwd_shared(const AttnSharedP& p0, hipStream_t s) {
+  AttnSharedP p = p0;
+  AttnSharedPlan plan;
+  int rc = attn_plan_shared(p, plan);
+  if (rc) return rc;
+  if (!plan.n_tgt) return launch_attention_fwd(plan.plain, s);
+  if (plan.plain_first) {
+    rc = launch_attention_fwd(plan.plain, s);
+    if (rc) return rc;
+  }
+  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = 1; }
+  const double pairs = (double)(plan.n_tgt * 2 + (plan.plain_first ? 0 : p.B - plan.n_tgt)) * p.H * (double)p.Sq * p.Skv;
+  PROF_BEGIN(2, 4.0 * pairs * 64, 2.0 * p.H * 64 * 4.0 * (p.B + plan.n_tgt) * p.Sq, s);
+  rc = launch_lds<attn_shared_kernel>(plan.grid, plan.lds, s, p, plan.n_tgt_wg);
+  PROF_END(s);
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+extern "C" int pea_debug_attn_shared_dispatch(const int* q, int* out) {
+  static float page[64] __attribute__((aligned(16)));
+  bf16* const any = (bf16*)page;
+  AttnSharedP p = AttnSharedP();
+  p.Q = p.K = p.V = any; p.O = any; p.scale = 0.125f; p.share_scale = 1.f;
+  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.Skv = q[3]; p.nd = q[4];
+  p.ldq = p.ldk = p.ldv = p.ldo = 64 * p.H;
+  if (q[5] > 0) p.ldk = q[5];
+  if (!(q[6] & 1)) p.coef = page;
+  for (int b = 0; b < 32; ++b) p.ref[b] = b < p.B ? q[7 + b] : -1;
+  AttnSharedPlan plan;
+  const int rc = attn_plan_shared(p, plan);
+  if (rc) return rc;
+  out[0] = (int)plan.grid.x; out[1] = (int)plan.grid.y; out[2] = (int)plan.grid.z; out[3] = plan.lds;
+  out[4] = plan.n_tgt_wg; out[5] = plan.n_plain_wg; out[6] = plan.plain_first; out[7] = plan.n_tgt;
   return PEA_OK;
 }

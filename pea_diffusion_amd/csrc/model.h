@@ -276,6 +276,26 @@ struct Tape {
   };
   EditState* edit = nullptr;
   int edit_check(bool forward) const;          // what a context must be to run an edit (tape.hip)
+  // StyleAligned generation (graph 0, inference only; api_model.hip: pea_unet_set_style_aligned): ref[b] >= 0 names the style
+  // reference of sample b.  While this is set, a self-attention op (is_self_attn) whose layer is switched on is ONE
+  // launch_attn_adain_coef over its Q and K columns and ONE launch_attention_fwd_shared instead of launch_attention_fwd.  The
+  // tape, the plans, the arenas and the attention census do not change.  Outside the arenas: release_acts keeps the buffers.
+  struct StyleState {
+    int ref[32];
+    int n_targets = 0, adain_q = 1, adain_k = 1;
+    float share_scale = 1.f, share_shift = 0.f;
+    std::map<int, int> layer_of_op;            // index of a self-attention op in `ops` -> its index among them, in tape order
+    std::vector<char> on;                      // per self-attention layer in that order: shared or not
+    float* coef = nullptr;                     // device fp32 [B][4][widest layer]; a layer uses the first B * 4 * C floats
+    float* scratch = nullptr;                  // the coefficient launch's partials, sized for the largest layer
+    ~StyleState() {
+      if (coef) (void)hipFree(coef);
+      if (scratch) (void)hipFree(scratch);
+    }
+  };
+  StyleState* style = nullptr;
+  bool is_self_attn(const Op& o) const { return graph == 0 && o.kind == OP_ATTN && o.b != t_kvall && !o.mask && o.p1 == o.p2; }
+  int style_check(bool forward) const;         // what a context must be to share self-attention (tape.hip)
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

@@ -170,6 +170,34 @@ struct AttnEditP {
   int src[32];
 };
 int launch_attention_fwd_edit(const AttnEditP& p, hipStream_t s);
+// StyleAligned shared self-attention (Hertz et al. 2023), forward only, head_dim 64, Sq == Skv = S, B <= 32.  Target sample b
+// (ref[b] = r >= 0, r a plain sample of the same batch) attends to its own keys and to its reference's under ONE softmax:
+//   q' = a_q o q + s_q,  own scores  scale (q' o a_k) . K[b][j] + scale q' . s_k,  reference scores  share_scale scale q' . K[r][j]
+//   + share_shift,  O[b] = softmax over the 2 S scores . [V[b]; V[r]]   (attn_shared_kernel; K, V of both samples are read in place).
+// coef: fp32 [B][4][64 H] = (a_q, s_q, a_k, s_k) per target sample (launch_attn_adain_coef); rows of plain samples are never read.
+// ref[b] < 0, or ref[b] == b: a plain sample, the bits of launch_attention_fwd.  ref travels in the kernel arguments.  Its own
+// launcher, shape checks and grid rule: the decision table of launch_attention_fwd / _bwd does not know it.
+struct AttnSharedP {
+  const bf16 *Q, *K, *V; int ldq, ldk, ldv;
+  bf16* O; int ldo;
+  int B, H, Sq, Skv;
+  const float* coef;
+  float scale; int q_prescaled;
+  float share_scale, share_shift;
+  int nd;                          // padded head_dim / 64 (0 is read as 1); anything but 1 is refused
+  int ref[32];
+  int order[32];                   // written by the launcher: the samples its grid covers, targets first
+};
+int launch_attention_fwd_shared(const AttnSharedP& p, hipStream_t s);
+// The AdaIN coefficients of launch_attention_fwd_shared from the per-channel statistics over the S tokens of Q [B][S][ldq] and
+// K [B][S][ldk] (C = 64 H columns each): for a target b with reference r and X in {Q, K},  sigma(X) = sqrt(var_unbiased(X) + eps),
+// a = sigma(X[r]) / sigma(X[b]),  s = mu(X[r]) - a mu(X[b]);  coef[b] = (a_q, s_q, a_k, s_k), (1, 0) for a pair that is switched
+// off.  eps = 1e-5 for K and a plain Q, (scale log2 e)^2 1e-5 for a prescaled Q.  Two launches: per-slab sums of (x - x[row 0]) and
+// its square (a mean far above the spread costs no digits), then their merge in slab order; no atomics.  scratch:
+// attn_adain_scratch_bytes, always needed.
+size_t attn_adain_scratch_bytes(int B, int H, int S);
+int launch_attn_adain_coef(const bf16* Q, int ldq, const bf16* K, int ldk, int B, int H, int S, const int* ref, float scale,
+                           int q_prescaled, int adain_queries, int adain_keys, float* coef, float* scratch, hipStream_t s);
 // Cross-attention heat maps, head_dim 64, 1 <= Skv <= 128: maps[b][key][q] (op)= (1 / H) sum_h softmax_key(scale Q_h K_h^T), fp32
 // [B][Skv][Sq], (op) a store or (accumulate) a += by the thread that owns the element (xattn_maps_kernel, 512 threads; no V, no O, no lse).
 // Its own launcher, shape checks and grid rule: the decision table of launch_attention_fwd / _bwd does not know it.

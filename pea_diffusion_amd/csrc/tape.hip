@@ -271,6 +271,7 @@ Tape::~Tape() {
   delete regions;
   delete maps;
   delete edit;
+  delete style;
 }
 
 int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s) {
@@ -609,6 +610,28 @@ int Tape::edit_check(bool forward) const {
   return PEA_OK;
 }
 
+// StyleAligned sharing: what the context must be.  Checked when the state is set and again (forward) before the first launch of a
+// forward: a prompt edit may have arrived in between.  Image prompts, regions, heat maps, FreeU and ControlNet residuals are
+// welcome: none of them sees a self-attention launch.
+int Tape::style_check(bool forward) const {
+  const char* const who = forward ? "pea_unet_forward" : "pea_unet_set_style_aligned";
+  if (needs_grad) {
+    pea_set_error("%s: StyleAligned sharing is an inference feature (no backward through it); this context was created with PEA_UNET_GRAD", who);
+    return PEA_E_STATE;
+  }
+  if (edit) {
+    pea_set_error("%s: StyleAligned sharing cannot be combined with prompt editing, whose self-attention rule rewrites the same outputs "
+                  "(pea_unet_clear_prompt_edit or pea_unet_clear_style_aligned)", who);
+    return PEA_E_STATE;
+  }
+  SHAPECHK(B <= 32, "%s: StyleAligned sharing takes a batch of at most 32 (B=%d)", who, B);
+  for (const Op& o : ops) {
+    if (!is_self_attn(o)) continue;
+    SHAPECHK(o.p3 == 1 && o.p1 >= 2, "%s: StyleAligned sharing needs head_dim 64 self-attention over at least 2 tokens (nd=%d, %d tokens)", who, o.p3, o.p1);
+  }
+  return PEA_OK;
+}
+
 int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype, const void* text, int text_dtype,
                   const float* time_ids, float* eps, hipStream_t s) {
   std::string miss;
@@ -624,6 +647,7 @@ int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype
     return PEA_E_STATE;
   }
   if (edit) RC(edit_check(true));
+  if (style) RC(style_check(true));
   RC(ensure_acts());
   RC(ensure_folded(s));
   x_in = x; t_in = t; tid_in = time_ids; eps_out = eps;
@@ -859,6 +883,19 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
           break;
         }
         if (ip && o.b == t_kvall) RC(ip_attach(o, p));               // image prompts: the layer's own columns of the image K|V
+        if (style && style->n_targets && is_self_attn(o) && style->on[style->layer_of_op.find((int)oi)->second]) {
+          // StyleAligned: the targets' AdaIN coefficients from this layer's Q and K columns, then one launch in which they attend
+          // to their reference's keys and values as well (style_check has passed; plain samples keep their bits)
+          RC(launch_attn_adain_coef(p.Q, p.ldq, p.K, p.ldk, B, o.p0, o.p1, style->ref, o.f0, o.pre, style->adain_q, style->adain_k,
+                                    style->coef, style->scratch, s));
+          AttnSharedP e = AttnSharedP();
+          e.Q = p.Q; e.ldq = p.ldq; e.K = p.K; e.ldk = p.ldk; e.V = p.V; e.ldv = p.ldv; e.O = p.O; e.ldo = p.ldo;
+          e.B = B; e.H = o.p0; e.Sq = o.p1; e.Skv = o.p2; e.scale = o.f0; e.q_prescaled = o.pre; e.nd = o.p3;
+          e.coef = style->coef; e.share_scale = style->share_scale; e.share_shift = style->share_shift;
+          memcpy(e.ref, style->ref, sizeof(e.ref));
+          RC(launch_attention_fwd_shared(e, s));
+          break;
+        }
         RC(launch_attention_fwd(p, s));
         if (edit && graph == 0 && o.b != t_kvall && !o.mask && o.p1 == o.p2 && o.p1 <= edit->self_max_tokens && edit->step < edit->self_until) {
           // prompt editing, self-attention: O[b] = softmax(Q[s] K[s]^T) V[b], one B = 1 launch per edited sample behind the

@@ -428,6 +428,59 @@ def attention_fwd_edit(q, k, v, heads, src, Mt, c, d, q_prescaled=False, scale=N
     return o
 
 
+def _rows(name, t, B, S, who):
+    """a [B, S, >= C] bf16 operand whose rows may sit inside a wider buffer (the Q | K | V projection's) -> its address"""
+    if t.dtype != BF or t.dim() != 3 or t.shape[0] != B or t.shape[1] != S or t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
+        raise PeaError(f"{who}: {name} {tuple(t.shape)} {t.dtype} strides {t.stride()}, expected bf16 [{B}, {S}, C] with dense samples")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _host_ref(ref, B, who):
+    ref = [int(x) for x in (ref.tolist() if hasattr(ref, "tolist") else ref)]
+    if len(ref) != B:
+        raise PeaError(f"{who}: {len(ref)} references for a batch of {B}")
+    return (ctypes.c_int * max(B, 1))(*ref)
+
+
+def attn_adain_coef(q, k, heads, ref, q_prescaled=False, scale=None, adain_queries=True, adain_keys=True, out=None):
+    """The AdaIN coefficients of StyleAligned sharing (pea_op_attn_adain_coef), head_dim 64: q, k [B,S,H*64] bf16 (rows may be
+    column slices of a wider buffer); ref: B ints (host), ref[b] >= 0 the style reference of target b.  -> fp32 [B,4,H*64] =
+    (a_q, s_q, a_k, s_k) with a = sigma(X[ref]) / sigma(X[b]), s = mu(X[ref]) - a mu(X[b]) over the tokens; rows of plain samples
+    are left as they were (zeros in a fresh buffer).  q_prescaled: q holds q * scale * log2(e); the variance epsilon follows."""
+    B, S, C = q.shape
+    who = "attn_adain_coef"
+    if C != heads * 64:
+        raise PeaError(f"{who}: head_dim {C // heads} (the kernel is built for 64)")
+    scale = scale if scale is not None else 64 ** -0.5
+    href = _host_ref(ref, B, who)
+    coef = out if out is not None else torch.zeros(B, 4, C, device=q.device, dtype=torch.float32)
+    nbytes = int(lib().pea_op_attn_adain_scratch_bytes(B, heads, S))
+    scratch = torch.empty(max(nbytes, 16) // 4, device=q.device, dtype=torch.float32)
+    check(lib().pea_op_attn_adain_coef(_rows("q", q, B, S, who), q.stride(1), _rows("k", k, B, S, who), k.stride(1), B, heads, S, href,
+                                       scale, int(q_prescaled), int(adain_queries), int(adain_keys),
+                                       ptr(coef), ptr(scratch), stream_ptr()))
+    return coef
+
+
+def attention_fwd_shared(q, k, v, heads, ref, coef, q_prescaled=False, scale=None, shared_score_scale=1.0, shared_score_shift=0.0):
+    """StyleAligned shared self-attention in one launch over the batch (pea_op_attention_fwd_shared), head_dim 64, B <= 32:
+    target b with r = ref[b] >= 0 and coef[b] = (a_q, s_q, a_k, s_k):  q' = a_q q + s_q,
+      o[b] = softmax([scale q' (a_k k[b] + s_k)^T | shared_score_scale scale q' k[r]^T + shared_score_shift]) [v[b]; v[r]],
+    ref[b] < 0: plain attention, the bits of attention_fwd (the sample's coef row is never read).  q, k, v [B,S,H*64] bf16 (rows
+    may be column slices of a wider buffer); coef fp32 [B,4,H*64] from attn_adain_coef, or None while no sample is a target.  -> o."""
+    B, Sq, C, scale, o, _ = _attn_fwd_out(q, heads, scale, want_lse=False)
+    who = "attention_fwd_shared"
+    Skv = k.shape[1]
+    href = _host_ref(ref, B, who)
+    if coef is not None and (coef.dtype != torch.float32 or tuple(coef.shape) != (B, 4, C) or not coef.is_contiguous()):
+        raise PeaError(f"{who}: coef {tuple(coef.shape)} {coef.dtype}, expected fp32 [{B}, 4, {C}]")
+    check(lib().pea_op_attention_fwd_shared(_rows("q", q, B, Sq, who), q.stride(1), _rows("k", k, B, Skv, who), k.stride(1),
+                                            _rows("v", v, B, Skv, who), v.stride(1), ptr(o), C, B, heads, Sq, Skv, href, ptr(coef), scale,
+                                            int(q_prescaled), float(shared_score_scale), float(shared_score_shift), C // heads // 64,
+                                            stream_ptr()))
+    return o
+
+
 def attention_fwd_fewq(q, k, v, k2=None, v2=None, heads=1, scale=None, q_prescaled=False, want_lse=False, kv_rows=None,
                        kv2_rows=None):
     """Few-query attention over the union of two key sets in one launch (pea_op_attention_fwd_fewq):

@@ -493,6 +493,36 @@ class HipUNet(HipTape):
         """back to plain attention; a forward then gives the bits it gave before"""
         check(lib().pea_unet_clear_prompt_edit(self._h))
 
+    def set_style_aligned(self, ref=None, layers=None, adain_queries=True, adain_keys=True, shared_score_scale=1.0,
+                          shared_score_shift=0.0, do_cfg=False):
+        """StyleAligned generation (Hertz et al. 2023): the batch of this UNet holds N prompts denoised together, and in the
+        self-attention layers every target sample moves its queries and keys onto its reference's per-channel statistics (AdaIN)
+        and attends to the reference's keys and values as well as its own, under one softmax.  ref: None (sample 0 is the
+        reference of all others; with do_cfg the batch is [uncond x n | cond x n] and each half has its own, see
+        `style_aligned.reference_index`) or B ints, ref[b] >= 0 the reference of b, negative = plain.  layers: None (every
+        self-attention layer), a fraction 0..1 of them (`style_aligned.level_switches`), or names / prefixes of
+        `style_aligned.layer_names(self)`.  Reference logits are shared_score_scale * logit + shared_score_shift.  Holds until
+        `clear_style_aligned()`; `sampler.denoise` over the batch is the generation loop."""
+        from . import style_aligned as sa
+        if ref is None:
+            if do_cfg and self.B % 2:
+                raise PeaError(f"set_style_aligned: do_cfg needs an even batch (B={self.B})")
+            ref = sa.reference_index(self.B // 2 if do_cfg else self.B, do_cfg)
+        ref = [int(x) for x in (ref.tolist() if hasattr(ref, "tolist") else ref)]
+        if len(ref) != self.B:
+            raise PeaError(f"set_style_aligned: {len(ref)} references for a batch of {self.B}")
+        href = (ctypes.c_int * self.B)(*ref)
+        arr, n = None, 0
+        if layers is not None:
+            vec = sa.resolve_layers(self, layers)
+            arr, n = (ctypes.c_float * len(vec))(*vec), len(vec)
+        check(lib().pea_unet_set_style_aligned(self._h, href, arr, n, int(bool(adain_queries)), int(bool(adain_keys)),
+                                               float(shared_score_scale), float(shared_score_shift), stream_ptr()))
+
+    def clear_style_aligned(self):
+        """back to plain self-attention; a forward then gives the bits it gave before"""
+        check(lib().pea_unet_clear_style_aligned(self._h))
+
     def clear_ip_tokens(self, index=None):
         """back to plain cross-attention launches (index: for that adapter alone); the adapters' weights stay loaded"""
         if index is None:
