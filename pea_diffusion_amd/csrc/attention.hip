@@ -30,6 +30,9 @@
 // a target sample and then over its reference's, with a second resident Q fragment set and a per-segment constant in the C operand
 // of the S^T products; plain samples of the same launch run attn_q_body itself.  attn_adain_part_kernel / attn_adain_coef_kernel
 // make the per-channel coefficients it reads.  Their launchers, too, stand beside the decision table.
+// The four forward kernels with resident keys (xattn_fwd / _regions_fwd / _maps / _edit_fwd) are sequences of one set of building
+// blocks that stands above xattn_fwd_kernel (Q stager, scores, key mask, one-shot softmax, value product, O image): one copy of
+// the arithmetic whose bits the tests compare between them.
 // The three backward cross-attention kernels take their per-workgroup context (unit range, operand rows of the head, key
 // count, score factor) from xattn_ctx.  They still repeat, as text: K / V staging, the unit stage (stage_unit / fetch_o /
 // unit_head), the key-on-the-lane task, the query-on-the-lane key-block step, and the dQ and dK / dV exits -- so a fix to
@@ -203,6 +206,70 @@ __device__ __forceinline__ bf16x8 read_row_frag(const char* tile, int row, int s
   return *(const bf16x8*)(tile + row * 128 + ((((2 * s + h)) ^ swz_x(row)) << 4));
 }
 
+// Per-lane LDS byte offsets of the two fragment kinds inside a swizzled image, computed once per kernel.  rf[s]: the row
+// fragment (ds_read_b128) of row lane & 31, k-slice s.  tr[db][hl]: the transposed fragment (read_transposed_frag_at) of
+// column block db, 8-row half hl, of a 16-row k-slice.  The swizzle term of a row is unchanged by +16 / +32 rows, so every
+// fragment address is (image base) + (one of these) + (a compile-time offset: 4096 per 32-row block for rf, 2048 per 16-row
+// slice for tr): integer adds per key tile instead of one address computation per ds_read (45 of the ~200 VALU instructions
+// of a tile of the VALU-bound forward loop were address arithmetic).
+struct AttnFragOff { int rf[4], tr[2][2]; };
+__device__ __forceinline__ AttnFragOff attn_frag_off(int lane) {
+  AttnFragOff o;
+  const int frow = lane & 31, fh = lane >> 5;
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) o.rf[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
+  const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int hl = 0; hl < 2; ++hl) o.tr[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
+  return o;
+}
+
+// A wave's 32 x 64 output block (O, dQ, dK, dV) leaves through an LDS image of its own.  The accumulator layout X^T has a row
+// per lane -- acc[db][4g + j] = X^T[d = db * 32 + 8g + 4 fh + j][row = lane & 31] -- which written straight out is eight 8-byte
+// stores per lane that each touch 32 different 128-byte lines; from the image every store instruction writes eight whole rows,
+// 16 bytes per lane.  val(db, i): the fp32 value of element i of accumulator db (the caller's normalisation), rounded to bf16
+// once here.  Rows row0 + r < nrows go to base[(row0 + r) * ld + 0..63]; accum: added to what is there (fp32 sum, one more
+// rounding).  Two layouts of the image: 144-byte pitch (4 608 bytes), or XOR-swizzled at a 128-byte pitch (4 096 bytes: where
+// the LDS total decides how many workgroups a CU holds); the 8-byte writes conflict two ways in either.
+template <bool SWZ, class Val>
+__device__ __forceinline__ void store_o_image(char* ost, int lane, Val val, bf16* base, int ld, int row0, int nrows, bool accum) {
+  const int frow = lane & 31, fh = lane >> 5, r8 = lane >> 3, ch = lane & 7;
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      bf16x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = (bf16)val(db, 4 * g + j);
+      if constexpr (SWZ) *(bf16x4*)(ost + frow * 128 + (((db * 4 + g) ^ swz_x(frow)) << 4) + fh * 8) = o;
+      else *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
+    }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = i * 8 + r8;
+    bf16x8 v = *(const bf16x8*)(SWZ ? ost + row * 128 + ((ch ^ swz_x(row)) << 4) : ost + row * 144 + ch * 16);
+    if (row0 + row < nrows) {
+      bf16* dst = base + (long long)(row0 + row) * ld + ch * 8;
+      if (accum) {
+        const bf16x8 old = *(const bf16x8*)dst;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (bf16)((float)v[j] + (float)old[j]);
+      }
+      *(bf16x8*)dst = v;
+    }
+  }
+}
+template <class Val>
+__device__ __forceinline__ void store_o_image_144(char* ost, int lane, Val val, bf16* base, int ld, int row0, int nrows, bool accum = false) {
+  store_o_image<false>(ost, lane, val, base, ld, row0, nrows, accum);
+}
+template <class Val>
+__device__ __forceinline__ void store_o_image_swz(char* ost, int lane, Val val, bf16* base, int ld, int row0, int nrows) {
+  store_o_image<true>(ost, lane, val, base, ld, row0, nrows, false);
+}
+
 // XCD-aware workgroup order.  Workgroups are handed to the 8 XCDs round-robin in dispatch order (x fastest), so the
 // query blocks of one head -- which all stream that head's K and V (or Q and dO) -- would land on 8 different L2s and
 // every XCD would see every head: a working set of all heads per 4-MB L2.  Remapped, XCD x runs a contiguous range of
@@ -335,20 +402,7 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
   WAIT_VM0();
   __syncthreads();
 
-  // Per-lane LDS byte offsets, computed once.  The swizzle term of a row is unchanged by +16 / +32 rows, so every fragment
-  // address in the loop is (stage base) + (one of these eight per-lane constants) + (a compile-time offset): eight integer
-  // adds per key tile instead of one address computation per ds_read (45 of the ~200 VALU instructions of a tile of the
-  // VALU-bound forward loop were address arithmetic).
-  int rf_off[4], tr_off[2][2];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
-  {
-    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
-  }
+  const AttnFragOff fo = attn_frag_off(lane);
 
   for (int t = 0; t < nt; ++t) {
     const int cur = t & 1;
@@ -360,11 +414,11 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
       const int sb = cur * STG;
       const int tb = sb + (MODE == 0 ? ND * TILE_BYTES : chunk * TILE_BYTES);   // fwd: V sub-tiles; dQ: this chunk's K sub-tile
 #pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) rfc[s4] = rf_off[s4] + sb;
+      for (int s4 = 0; s4 < 4; ++s4) rfc[s4] = fo.rf[s4] + sb;
 #pragma unroll
       for (int db = 0; db < 2; ++db)
 #pragma unroll
-        for (int hl = 0; hl < 2; ++hl) trc[db][hl] = tr_off[db][hl] + tb;
+        for (int hl = 0; hl < 2; ++hl) trc[db][hl] = fo.tr[db][hl] + tb;
     }
 
     // S^T[key][q] = K . Q^T  (sum over the ND sub-tiles of the head dimension).  All K fragments of a sub-tile are requested
@@ -542,41 +596,14 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
     if (p.lse && qvalid && fh == 0)
       p.lse[((long long)b * p.H + head) * p.Sq + qrow] = (m_run + log2f(l_tot)) * 0.6931471805599453f;
   }
-  // The accumulator layout has a query row per lane: written straight out that is eight 8-byte stores per lane, each
-  // touching 32 different 128-byte lines.  The wave's 32 x 64 block goes through an LDS image instead (its own 4.5 KiB of
-  // the K / V ring, which every wave has left behind the loop's last barrier; 144-byte pitch), from which every store
-  // instruction writes eight whole rows, 16 bytes per lane.
+  // the wave's image: its own 4.5 KiB of the K / V ring, which every wave has left behind the loop's last barrier
   const bool accum = MODE == 1 && p.accum_dq;
   char* const ost = smem + wave * (32 * 144);
-  const int r8 = lane >> 3, ch = lane & 7;
 #pragma unroll
   for (int no = 0; no < NO; ++no) {
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16)(oacc[2 * no + db][4 * g + j] * inv);
-        *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
-      }
-    bf16* Ob = MODE == 0 ? p.O + (long long)b * p.Sq * p.ldo + head * 64 * ND + no * 64 + ch * 8
-                         : p.dQ + (long long)b * p.Sq * p.lddq + head * 64 * ND + chunk * 64 + ch * 8;
-    const int ldo_ = MODE == 0 ? p.ldo : p.lddq;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = i * 8 + r8;
-      if (q0 + row < p.Sq) {
-        bf16x8 v = *(const bf16x8*)(ost + row * 144 + ch * 16);
-        bf16* dst = Ob + (long long)(q0 + row) * ldo_;
-        if (accum) {
-          const bf16x8 old = *(const bf16x8*)dst;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = (bf16)((float)v[j] + (float)old[j]);
-        }
-        *(bf16x8*)dst = v;
-      }
-    }
+    bf16* Ob = MODE == 0 ? p.O + (long long)b * p.Sq * p.ldo + head * 64 * ND + no * 64
+                         : p.dQ + (long long)b * p.Sq * p.lddq + head * 64 * ND + chunk * 64;
+    store_o_image_144(ost, lane, [&](int db, int i) { return oacc[2 * no + db][i] * inv; }, Ob, MODE == 0 ? p.ldo : p.lddq, q0, p.Sq, accum);
   }
 }
 
@@ -805,41 +832,14 @@ __device__ __forceinline__ void attn_dkv_body(const AttnP& p, char* smem, int bl
     return;
   }
   if (lds_epi) {
-    // The accumulator layout has a key row per lane: written straight out that is sixteen 8-byte stores per lane, each
-    // touching 32 different 128-byte lines (store-issue-bound: ~9 k cycles per workgroup, paid once per 16 query tiles at
-    // 1024 tokens).  Each wave's 32 x 64 blocks of dK, then dV, go through its own 4.5 KiB LDS image (the ring is free
-    // behind the loop's last barrier; 144-byte pitch) and leave as whole rows, 16 bytes per lane, eight rows per instruction.
+    // A key row per lane here: sixteen 8-byte stores per lane written straight out (store-issue-bound: ~9 k cycles per
+    // workgroup, paid once per 16 query tiles at 1024 tokens).  Each wave's blocks of dK, then dV, go through its own image
+    // (the ring is free behind the loop's last barrier).
     char* const ost = smem + wave * (32 * 144);
-    const int r8 = lane >> 3, ch = lane & 7;
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-      f32x16* acc = which ? dv : dk;
-#pragma unroll
-      for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          bf16x4 o;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) o[j] = (bf16)acc[db][4 * g + j];
-          *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
-        }
-      bf16* base = (which ? p.dV : p.dK) + (long long)b * p.Skv * (which ? p.lddv : p.lddk) + head * D + chunk * 64 + ch * 8;
-      const int ld_ = which ? p.lddv : p.lddk;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = i * 8 + r8;
-        if (k0 + row < p.Skv) {
-          bf16x8 v = *(const bf16x8*)(ost + row * 144 + ch * 16);
-          bf16* dst = base + (long long)(k0 + row) * ld_;
-          if (p.accum_dkv) {
-            const bf16x8 old = *(const bf16x8*)dst;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (bf16)((float)v[j] + (float)old[j]);
-          }
-          *(bf16x8*)dst = v;
-        }
-      }
-    }
+    store_o_image_144(ost, lane, [&](int db, int i) { return dk[db][i]; }, p.dK + (long long)b * p.Skv * p.lddk + head * D + chunk * 64,
+                      p.lddk, k0, p.Skv, p.accum_dkv != 0);
+    store_o_image_144(ost, lane, [&](int db, int i) { return dv[db][i]; }, p.dV + (long long)b * p.Skv * p.lddv + head * D + chunk * 64,
+                      p.lddv, k0, p.Skv, p.accum_dkv != 0);
     return;
   }
   bf16* dKr = p.dK + ((long long)b * p.Skv + krow) * p.lddk + head * D + chunk * 64;
@@ -929,7 +929,106 @@ __device__ __forceinline__ float xhalf_sum(float x) {
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
   return a + b;
 }
-//
+
+// ----------------------------------------------------------------------------- cross-attention building blocks
+// What xattn_fwd_kernel, xattn_regions_fwd_kernel, xattn_maps_kernel and xattn_edit_fwd_kernel are made of: a wave's 32 queries
+// (query lane & 31 on the lane, both half-waves) against KB resident blocks of 32 keys.  One copy of the arithmetic, so that
+// the bit-equality the tests assert between these kernels holds by construction.  A block of K or V is 32 rows x 128 bytes
+// (4 096 bytes, source-side XOR swizzle), block kb at kb * 4096 -- a 64-row tile is two of them.  In the S^T accumulator slot
+// r of half-wave fh of block kb is key kb * 32 + (r & 3) + 8 (r >> 2) + 4 fh.
+__device__ __forceinline__ f32x16 zero_f32x16() {
+  return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+}
+// A wave's 32 query rows as a 4 KiB swizzled image in its own LDS region, filled by LDS-DMA (whole 128-byte rows per 8 lanes)
+// one unit ahead; direct 16-byte loads of a row per lane touched 32 lines per instruction.  src: tile_src(.., wave 0, lane) --
+// pieces 0 / 1 of a tile are rows 0..15, the other 16 rows come through the scalar offset.  The caller waits (WAIT_VM0) before
+// load() and for lgkmcnt(0) behind it before it stages the next unit over the image.
+struct XattnQStage {
+  TileSrc src;
+  char* img;
+  __device__ __forceinline__ void stage(int row0) const {
+    stage_tile(src, row0, img, 0);
+    stage_tile(src, row0 + 16, img + 2048, 0);
+  }
+  __device__ __forceinline__ void load(bf16x8 (&qf)[4], const AttnFragOff& fo) const {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(img + fo.rf[s]);
+  }
+};
+// S^T[key][q] = K . Q^T over the KB key blocks at Ksm
+template <int KB>
+__device__ __forceinline__ void xattn_scores(const char* Ksm, const AttnFragOff& fo, const bf16x8 (&qf)[4], f32x16 (&sacc)[KB]) {
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) {
+    bf16x8 kfr[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) kfr[s] = *(const bf16x8*)(Ksm + fo.rf[s] + kb * 4096);
+    sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[0], qf[0], zero_f32x16(), 0, 0, 0);
+#pragma unroll
+    for (int s = 1; s < 4; ++s) sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[s], qf[s], sacc[kb], 0, 0, 0);
+  }
+}
+// keys at or past nkeys (padding slots, keys past a sample's count) score -inf; only blocks FIRST.. are looked at, and of
+// those only the ones that hold such a key (wave-uniform).  FIRST = KB - 1 where nkeys > (KB - 1) * 32 is known.
+template <int KB, int FIRST = 0>
+__device__ __forceinline__ void xattn_mask_keys(f32x16 (&sacc)[KB], int nkeys, int fh) {
+#pragma unroll
+  for (int kb = FIRST; kb < KB; ++kb)
+    if (kb * 32 + 32 > nkeys) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+        sacc[kb][r] = key < nkeys ? sacc[kb][r] : -INFINITY;
+      }
+    }
+}
+// The softmax in one shot (all scores of a query are in registers: no running max, no rescale): e = exp2(c s - c max), handed
+// to put(kb, r, e); returns the sum of e over all keys, mx the maximum of the raw scores.  A masked key gives exp2(-inf) = 0.
+// The ORDER is the contract between the kernels: the maximum starts at sacc[0][0] and takes the blocks in order, registers in
+// order; the sum starts at 0 and adds in (kb, r) order; the half-wave combine (xhalf_max / xhalf_sum) comes last.
+template <int KB, class Put>
+__device__ __forceinline__ float xattn_softmax(const f32x16 (&sacc)[KB], float c, float& mx, Put put) {
+  mx = sacc[0][0];
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+    for (int r = (kb == 0 ? 1 : 0); r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
+  mx = xhalf_max(mx);
+  const float mc = mx * c;
+  float ls = 0.f;
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float e = fast_exp2(fmaf(sacc[kb][r], c, -mc));
+      ls += e;
+      put(kb, r, e);
+    }
+  return xhalf_sum(ls);
+}
+// ... leaving the un-normalised P^T rounded to bf16, as the B-operand fragments of the value product (k-permuted)
+template <int KB>
+__device__ __forceinline__ float xattn_softmax_bf16(const f32x16 (&sacc)[KB], float c, float& mx, bf16x8 (&pf)[2 * KB]) {
+  return xattn_softmax<KB>(sacc, c, mx, [&](int kb, int r, float e) { pf[2 * kb + (r >> 3)][r & 7] = (bf16)e; });
+}
+// ... leaving the fp32 exponentials in place of the scores
+template <int KB>
+__device__ __forceinline__ float xattn_softmax_f32(f32x16 (&sacc)[KB], float c, float& mx) {
+  return xattn_softmax<KB>(sacc, c, mx, [&](int kb, int r, float e) { sacc[kb][r] = e; });
+}
+// O^T[d][q] = V^T[d][key] P^T[key][q] over the 2 KB 16-key slices at Vsm (transposed reads of the row-major V blocks)
+template <int KB>
+__device__ __forceinline__ void xattn_pv(const char* Vsm, const AttnFragOff& fo, const bf16x8 (&pf)[2 * KB], f32x16 (&oacc)[2]) {
+#pragma unroll
+  for (int ks = 0; ks < 2 * KB; ++ks)
+#pragma unroll
+    for (int db = 0; db < 2; ++db) {
+      const bf16x8 tf = read_transposed_frag_at(Vsm + fo.tr[db][0] + ks * 2048, Vsm + fo.tr[db][1] + ks * 2048);
+      if (ks == 0) oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[0], zero_f32x16(), 0, 0, 0);
+      else oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[ks], oacc[db], 0, 0, 0);
+    }
+}
+
 // IP: the decoupled cross-attention of an image prompt (IP-Adapter), O = softmax(s Q K^T) V + scale2 * softmax(s Q K2^T) V2
 // with 1..32 image keys (AttnP::K2 / V2 / Skv2).  Unfused that is two of these launches and an add: Q read twice, three
 // O-sized writes and two O-sized reads, where the output alone is already most of this kernel's traffic.  Here the image
@@ -940,8 +1039,8 @@ __device__ __forceinline__ float xhalf_sum(float x) {
 // fourth block of the text tiles would only serve <= 96 text keys).  kv_len masks text keys only; lse is the text softmax's.
 // scale2 rides in inv2 (scale2 / sum): one multiply per element fewer, and scale2 = 0 returns the text term bit for bit.
 // The LDS allows two workgroups per CU at most, so the launch bound asks for no more.  What hipcc makes of the four instances
-// (profiles/ip_adapter_bench_regs.txt): 104 / 106 / 131 / 163 VGPRs for 1..4 text key blocks, no AGPRs, no scratch -- against
-// 68 / 88 / 91 / 130 without the image keys; all under the 256 a two-workgroup CU leaves a wave.
+// (profiles/ip_adapter_bench_regs.txt): 104 / 108 / 130 / 153 VGPRs for 1..4 text key blocks, no AGPRs, no scratch -- against
+// 68 / 78 / 91 / 130 without the image keys; all under the 256 a two-workgroup CU leaves a wave.
 //
 // MS (with IP): several image prompts at once, O = o_text + sum_j w_j m_j[b][q] softmax(s Q K2_j^T) V2_j for 1..4 sets that lie
 // back to back in the SAME 32-key block (4 + 16, 16 + 16, 4 + 4 + 16 slots of it), each with a weight and an optional per-query
@@ -966,17 +1065,11 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
-  int split, head, b;
-  attn_block_coords(split, head, b);
-  const int nu = (p.Sq + 127) >> 7;
-  const int u_begin = split * upw, u_end = min(nu, u_begin + upw);
-  const float c = p.q_prescaled ? 1.f : p.scale * LOG2E;         // prescaled Q: the scores are in the log2 domain already
-  const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq + head * 64;
-  const bf16* Kb = p.K + (long long)b * p.Skv * p.ldk + head * 64;
-  const bf16* Vb = p.V + (long long)b * p.Skv * p.ldv + head * 64;
-  const int skv_b = __builtin_amdgcn_readfirstlane(p.kv_len ? p.kv_len[b] : p.Skv);
+  const XattnCtx x = xattn_ctx<128>(p, upw);
+  const int head = x.head, b = x.b, u_begin = x.u_begin, u_end = x.u_end, skv_b = x.skv_b;
+  const float c = x.c;                                           // prescaled Q: 1, the scores are in the log2 domain already
   {
-    const TileSrc ksrc = tile_src(Kb, p.ldk, p.Skv, wave, lane), vsrc = tile_src(Vb, p.ldv, p.Skv, wave, lane);
+    const TileSrc ksrc = tile_src(x.Kb, p.ldk, p.Skv, wave, lane), vsrc = tile_src(x.Vb, p.ldv, p.Skv, wave, lane);
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
       stage_tile(ksrc, t * 64, Ksm + t * TILE_BYTES, wave);
@@ -989,36 +1082,19 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
       stage_tile(src2, 0, isv ? V2sm : K2sm, wave & 1);
     }
   }
-  int rf_off[4], tr_off[2][2];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
-  {
-    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
-  }
+  const AttnFragOff fo = attn_frag_off(lane);
   int qrow = u_begin * 128 + wave * 32 + frow;
   bf16x8 qf[4];
-  // Q: this wave's 32 rows as a 4 KiB swizzled image in its own LDS region, filled by LDS-DMA (whole 128-byte rows per
-  // 8 lanes) one unit ahead; direct 16-byte loads of a row per lane touched 32 lines per instruction
-  char* const qst = Osm + 4 * 32 * 144 + wave * 4096;
-  const TileSrc qsrc = tile_src(Qb, p.ldq, p.Sq, 0, lane);      // pieces 0 / 1 of a tile: rows 0..15; + 16 rows via the scalar offset
-  auto stage_q = [&](int row0) {
-    stage_tile(qsrc, row0, qst, 0);
-    stage_tile(qsrc, row0 + 16, qst + 2048, 0);
-  };
-  if (u_begin < u_end) stage_q(u_begin * 128 + wave * 32);
+  const XattnQStage qs = {tile_src(x.Qb, p.ldq, p.Sq, 0, lane), Osm + 4 * 32 * 144 + wave * 4096};
+  if (u_begin < u_end) qs.stage(u_begin * 128 + wave * 32);
   WAIT_VM0();
   __syncthreads();
   for (int u = u_begin; u < u_end; ++u, qrow += 128) {
     const bool qvalid = qrow < p.Sq;
     WAIT_VM0();                                                  // this wave's Q image (and its stores of the last unit)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qst + rf_off[s]);
+    qs.load(qf, fo);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (u + 1 < u_end) stage_q((u + 1) * 128 + wave * 32);      // next unit's rows fly under this unit's work
+    if (u + 1 < u_end) qs.stage((u + 1) * 128 + wave * 32);     // next unit's rows fly under this unit's work
     [[maybe_unused]] float wm[4];                                // MS: w_j m_j[b][this lane's query]; the loads fly under the score products
     if constexpr (MS) {
 #pragma unroll
@@ -1030,73 +1106,19 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
         }
       }
     }
-    // S^T[key][q] = K . Q^T over the KB key blocks
     f32x16 sacc[KB];
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      bf16x8 kfr[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) kfr[s] = *(const bf16x8*)(Ksm + rf_off[s] + ((kb >> 1) * TILE_BYTES + (kb & 1) * 4096));
-      const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[0], qf[0], zero16, 0, 0, 0);
-#pragma unroll
-      for (int s = 1; s < 4; ++s) sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[s], qf[s], sacc[kb], 0, 0, 0);
-    }
-    // padding keys / keys past this sample's count: -inf (only the blocks that hold any)
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-      if (kb * 32 + 32 > skv_b) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-          sacc[kb][r] = key < skv_b ? sacc[kb][r] : -INFINITY;
-        }
-      }
-    [[maybe_unused]] f32x16 sacc2;                               // IP: S2^T = K2 . Q^T, slots past Skv2 -inf
+    xattn_scores<KB>(Ksm, fo, qf, sacc);
+    xattn_mask_keys<KB>(sacc, skv_b, fh);                        // padding keys / keys past this sample's count
+    [[maybe_unused]] f32x16 sacc2[1];                            // IP: S2^T = K2 . Q^T, slots past Skv2 -inf
     if constexpr (IP) {
-      const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      sacc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(K2sm + rf_off[0]), qf[0], zero16, 0, 0, 0);
-#pragma unroll
-      for (int s = 1; s < 4; ++s) sacc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(K2sm + rf_off[s]), qf[s], sacc2, 0, 0, 0);
-      if (p.Skv2 < 32) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sacc2[r] = (r & 3) + 8 * (r >> 2) + 4 * fh < p.Skv2 ? sacc2[r] : -INFINITY;
-      }
+      xattn_scores<1>(K2sm, fo, qf, sacc2);
+      xattn_mask_keys<1>(sacc2, p.Skv2, fh);
     }
-    float mx = sacc[0][0];
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-      for (int r = (kb == 0 ? 1 : 0); r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
-    mx = xhalf_max(mx);
-    const float mc = mx * c;
-    float ls = 0.f;
+    float mx;
     bf16x8 pf[2 * KB];
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = fast_exp2(fmaf(sacc[kb][r], c, -mc));
-        ls += e;
-        pf[2 * kb + (r >> 3)][r & 7] = (bf16)e;
-      }
-    const float l_tot = xhalf_sum(ls);
-    // O^T[d][q] = V^T[d][key] P^T[key][q]
+    const float l_tot = xattn_softmax_bf16<KB>(sacc, c, mx, pf);
     f32x16 oacc[2];
-#pragma unroll
-    for (int ks = 0; ks < 2 * KB; ++ks) {
-      const int vb = (ks >> 2) * TILE_BYTES + (ks & 3) * 2048;
-#pragma unroll
-      for (int db = 0; db < 2; ++db) {
-        const bf16x8 tf = read_transposed_frag_at(Vsm + tr_off[db][0] + vb, Vsm + tr_off[db][1] + vb);
-        if (ks == 0) {
-          const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[0], zero16, 0, 0, 0);
-        } else {
-          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[ks], oacc[db], 0, 0, 0);
-        }
-      }
-    }
+    xattn_pv<KB>(Vsm, fo, pf, oacc);
     const float inv = 1.f / l_tot;
     [[maybe_unused]] f32x16 oacc2[2];
     [[maybe_unused]] float inv2 = 0.f;                           // scale2 / (sum of the image softmax)
@@ -1111,7 +1133,7 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
         const auto from = [&](int j, int r) { return kb >= p.set_end[j - 1] - ((r & 3) + 8 * (r >> 2)); };
         float mcs[4], fs[4], cur[16], mcr[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) cur[r] = sacc2[r];
+        for (int r = 0; r < 16; ++r) cur[r] = sacc2[0][r];
 #pragma unroll
         for (int j = 3; j >= 1; --j) {
           mcs[j] = 0.f;
@@ -1141,7 +1163,7 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
           }
         float e2[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) cur[r] = e2[r] = fast_exp2(fmaf(sacc2[r], c, -mcr[r]));
+        for (int r = 0; r < 16; ++r) cur[r] = e2[r] = fast_exp2(fmaf(sacc2[0][r], c, -mcr[r]));
 #pragma unroll
         for (int j = 3; j >= 1; --j) {
           fs[j] = 0.f;
@@ -1172,58 +1194,21 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
 #pragma unroll
         for (int r = 0; r < 16; ++r) pf2[r >> 3][r & 7] = (bf16)(e2[r] * mcr[r]);
       } else {
-        float mx2 = sacc2[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx2 = fmaxf(mx2, sacc2[r]);
-        const float mc2 = xhalf_max(mx2) * c;
-        float ls2 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = fast_exp2(fmaf(sacc2[r], c, -mc2));
-          ls2 += e;
-          pf2[r >> 3][r & 7] = (bf16)e;
-        }
-        inv2 = p.scale2 / xhalf_sum(ls2);
+        float mx2;
+        inv2 = p.scale2 / xattn_softmax_bf16<1>(sacc2, c, mx2, pf2);
       }
-      const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int db = 0; db < 2; ++db) {
-        oacc2[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(read_transposed_frag_at(V2sm + tr_off[db][0], V2sm + tr_off[db][1]),
-                                                            pf2[0], zero16, 0, 0, 0);
-        oacc2[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            read_transposed_frag_at(V2sm + tr_off[db][0] + 2048, V2sm + tr_off[db][1] + 2048), pf2[1], oacc2[db], 0, 0, 0);
-      }
+      xattn_pv<1>(V2sm, fo, pf2, oacc2);
     }
     if (qvalid && p.lse && fh == 0)
       p.lse[((long long)b * p.H + head) * p.Sq + qrow] = mx * (p.q_prescaled ? 0.6931471805599453f : p.scale) + log2f(l_tot) * 0.6931471805599453f;
-    // O leaves through a per-wave LDS image (32 rows x 128 bytes, 144-byte pitch): the accumulator layout has a query row
-    // per lane, i.e. eight 8-byte stores per lane that each touch 32 different 128-byte lines; from the image every store
-    // instruction writes eight whole rows (16 bytes per lane).  With 77 keys the output is most of this kernel's traffic.
-    char* const ost = Osm + wave * (32 * 144);
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if constexpr (MS) o[j] = (bf16)(oacc[db][4 * g + j] * inv + oacc2[db][4 * g + j]);       // the factors are in P
-          else if constexpr (IP) o[j] = (bf16)(oacc[db][4 * g + j] * inv + oacc2[db][4 * g + j] * inv2);
-          else o[j] = (bf16)(oacc[db][4 * g + j] * inv);
-        }
-        *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
-      }
-    {
-      const int r8 = lane >> 3, ch = lane & 7;
-      const int q0w = u * 128 + wave * 32;
-      bf16* Ob = p.O + (long long)b * p.Sq * p.ldo + head * 64 + ch * 8;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = i * 8 + r8;
-        const bf16x8 v = *(const bf16x8*)(ost + row * 144 + ch * 16);
-        if (q0w + row < p.Sq) *(bf16x8*)(Ob + (long long)(q0w + row) * p.ldo) = v;
-      }
-    }
+    // with 77 keys the output is most of this kernel's traffic
+    store_o_image_144(Osm + wave * (32 * 144), lane,
+                      [&](int db, int i) {
+                        if constexpr (MS) return oacc[db][i] * inv + oacc2[db][i];                // the factors are in P
+                        else if constexpr (IP) return oacc[db][i] * inv + oacc2[db][i] * inv2;
+                        else return oacc[db][i] * inv;
+                      },
+                      p.O + (long long)b * p.Sq * p.ldo + head * 64, p.ldo, u * 128 + wave * 32, p.Sq);
   }
 }
 
@@ -1233,14 +1218,14 @@ __global__ __launch_bounds__(256, IP ? 2 : 3) void xattn_fwd_kernel(const AttnP 
 // R launches of xattn_fwd_kernel and R weighted adds: Q read R times, O written and re-read R times, in a kernel whose output
 // is most of its traffic.  Here a workgroup stages all R regions once, each padded to KB = ceil(Lr / 32) whole 32-key blocks
 // (half tiles of 4 096 bytes, region r at r * KB * 8 192: its K blocks, then its V blocks), and a wave walks the regions on
-// its resident Q fragments: S^T over the region's blocks, a one-shot softmax with the region's OWN maximum and sum (a spike in
-// one region cannot underflow another), P rounded to bf16 un-normalised exactly as xattn_fwd_kernel rounds it, O_r^T = V_r^T
-// P^T, and one fmaf per element by w / sum into a running fp32 total: 32 more VGPRs whatever R is.  O is rounded once.
+// its resident Q fragments: the building blocks per region (scores, mask, softmax with the region's OWN maximum and sum -- a
+// spike in one region cannot underflow another --, value product), and one fmaf per element by w / sum into a running fp32
+// total: 32 more VGPRs whatever R is.  O is rounded once.
 // LDS: R x KB x 8 192 bytes of keys and values, four O images and four Q images of 4 096 bytes each: 81 920 bytes for two regions
-// of 77 keys, which is exactly two workgroups per CU, 131 072 at the maximum of twelve blocks.  The O image is XOR-swizzled at a
-// 128-byte pitch for that reason: padded to 144 bytes per row as in xattn_fwd_kernel the two-region launch took 83 968 bytes and
+// of 77 keys, which is exactly two workgroups per CU, 131 072 at the maximum of twelve blocks.  The O image is the swizzled one
+// (store_o_image_swz) for that reason: at a 144-byte pitch the two-region launch took 83 968 bytes and
 // ran one workgroup per CU (same bits; 9.11 -> 8.64 us at 10 heads x 4096 queries, 8.36 -> 7.21 us at 20 x 1024, the other
-// region counts unchanged: profiles/EXPERIMENTS.md section 9, f9).  Its 8-byte writes conflict two ways in either layout.
+// region counts unchanged: profiles/EXPERIMENTS.md section 9, f9).
 // Every block goes through a descriptor that starts at the block's first row and ends with the region's last (as the blocks
 // of attn_fewq_kernel do), so no row of the next region, the next sample or anything behind the buffer is read: such slots
 // arrive as zeros and score -inf.
@@ -1274,115 +1259,43 @@ __global__ __launch_bounds__(256, 2) void xattn_regions_fwd_kernel(const AttnReg
         stage_tile(src, 0, smem + r * RB + (isv ? KB * 4096 : 0) + kb * 4096, wave & 1);
       }
   }
-  int rf_off[4], tr_off[2][2];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
-  {
-    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
-  }
+  const AttnFragOff fo = attn_frag_off(lane);
   int qrow = u_begin * 128 + wave * 32 + frow;
   bf16x8 qf[4];
-  char* const qst = Osm + 4 * 4096 + wave * 4096;                 // this wave's Q image, one unit ahead (as in xattn_fwd_kernel)
-  const TileSrc qsrc = tile_src(Qb, p.ldq, p.Sq, 0, lane);
-  auto stage_q = [&](int row0) {
-    stage_tile(qsrc, row0, qst, 0);
-    stage_tile(qsrc, row0 + 16, qst + 2048, 0);
-  };
-  if (u_begin < u_end) stage_q(u_begin * 128 + wave * 32);
+  const XattnQStage qs = {tile_src(Qb, p.ldq, p.Sq, 0, lane), Osm + 4 * 4096 + wave * 4096};
+  if (u_begin < u_end) qs.stage(u_begin * 128 + wave * 32);
   WAIT_VM0();
   __syncthreads();
   const float* const wb = p.w + (p.Bw == 1 ? 0 : (long long)b * p.R * p.Sq);
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int u = u_begin; u < u_end; ++u, qrow += 128) {
     const bool qvalid = qrow < p.Sq;
     WAIT_VM0();                                                  // this wave's Q image (and its stores of the last unit)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qst + rf_off[s]);
+    qs.load(qf, fo);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (u + 1 < u_end) stage_q((u + 1) * 128 + wave * 32);
+    if (u + 1 < u_end) qs.stage((u + 1) * 128 + wave * 32);
     float wv[4];                                                 // w[b][r][this lane's query]; 0 for a region that is not there
 #pragma unroll
     for (int r = 0; r < 4; ++r) wv[r] = r < p.R && qvalid ? wb[(long long)r * p.Sq + qrow] : 0.f;
-    f32x16 tot[2] = {zero16, zero16};
+    f32x16 tot[2] = {zero_f32x16(), zero_f32x16()};
     for (int r = 0; r < p.R; ++r) {
       const float wr = r == 0 ? wv[0] : r == 1 ? wv[1] : r == 2 ? wv[2] : wv[3];
       if (__builtin_amdgcn_ballot_w64(wr != 0.f) == 0) continue; // nobody in this wave weighs region r: skip both products
       const char* const Ksm = smem + r * RB;
-      const char* const Vsm = Ksm + KB * 4096;
       f32x16 sacc[KB];
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb) {
-        bf16x8 kfr[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) kfr[s] = *(const bf16x8*)(Ksm + rf_off[s] + kb * 4096);
-        sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[0], qf[0], zero16, 0, 0, 0);
-#pragma unroll
-        for (int s = 1; s < 4; ++s) sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[s], qf[s], sacc[kb], 0, 0, 0);
-      }
-      if (KB * 32 > p.Lr) {                                      // padding slots of the region's last block: -inf
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int key = (KB - 1) * 32 + (i & 3) + 8 * (i >> 2) + 4 * fh;
-          sacc[KB - 1][i] = key < p.Lr ? sacc[KB - 1][i] : -INFINITY;
-        }
-      }
-      float mx = sacc[0][0];
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int i = (kb == 0 ? 1 : 0); i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
-      mx = xhalf_max(mx);
-      const float mc = mx * c;
-      float ls = 0.f;
+      xattn_scores<KB>(Ksm, fo, qf, sacc);
+      xattn_mask_keys<KB, KB - 1>(sacc, p.Lr, fh);               // padding slots of the region's last block
+      float mx;
       bf16x8 pf[2 * KB];
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float e = fast_exp2(fmaf(sacc[kb][i], c, -mc));
-          ls += e;
-          pf[2 * kb + (i >> 3)][i & 7] = (bf16)e;
-        }
-      const float f = wr / xhalf_sum(ls);
+      const float f = wr / xattn_softmax_bf16<KB>(sacc, c, mx, pf);
       f32x16 oacc[2];
-#pragma unroll
-      for (int ks = 0; ks < 2 * KB; ++ks)
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-          const bf16x8 tf = read_transposed_frag_at(Vsm + tr_off[db][0] + ks * 2048, Vsm + tr_off[db][1] + ks * 2048);
-          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[ks], ks == 0 ? zero16 : oacc[db], 0, 0, 0);
-        }
+      xattn_pv<KB>(Ksm + KB * 4096, fo, pf, oacc);
 #pragma unroll
       for (int db = 0; db < 2; ++db)
 #pragma unroll
         for (int i = 0; i < 16; ++i) tot[db][i] = fmaf(oacc[db][i], f, tot[db][i]);
     }
-    char* const ost = Osm + wave * 4096;                         // O leaves through a per-wave LDS image, as in xattn_fwd_kernel;
-                                                                 // here XOR-swizzled at a 128-byte pitch instead of padded to 144
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16)tot[db][4 * g + j];
-        *(bf16x4*)(ost + frow * 128 + (((db * 4 + g) ^ swz_x(frow)) << 4) + fh * 8) = o;
-      }
-    {
-      const int r8 = lane >> 3, ch = lane & 7;
-      const int q0w = u * 128 + wave * 32;
-      bf16* Ob = p.O + (long long)b * p.Sq * p.ldo + head * 64 + ch * 8;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = i * 8 + r8;
-        const bf16x8 v = *(const bf16x8*)(ost + row * 128 + ((ch ^ swz_x(row)) << 4));
-        if (q0w + row < p.Sq) *(bf16x8*)(Ob + (long long)(q0w + row) * p.ldo) = v;
-      }
-    }
+    store_o_image_swz(Osm + wave * 4096, lane, [&](int db, int i) { return tot[db][i]; },
+                      p.O + (long long)b * p.Sq * p.ldo + head * 64, p.ldo, u * 128 + wave * 32, p.Sq);
   }
 }
 
@@ -1399,10 +1312,10 @@ __global__ __launch_bounds__(256, 2) void xattn_regions_fwd_kernel(const AttnReg
 // barrier in the loop.  There is no second slot: what hides a wave's fetch is the other wave of its SIMD.  The first form had four
 // waves with a ring two slots deep (the same LDS); one wave per SIMD then ran fetch wait, 12 MFMAs and ~300 vector instructions
 // per head back to back with nothing to overlap them: 8.03 / 10.46 us at the two SDXL shapes against 6.49 / 7.62 us in this form
-// (profiles/EXPERIMENTS.md section 9, f10).  Per head: S^T = K . Q^T (in the S^T accumulator layout one register index
-// is one key over 32 consecutive queries), padding keys and keys at or past kv_len[b] to -inf by the compare of
-// xattn_fwd_kernel, a one-shot softmax in fp32 -- e = exp2(c s - c max), p = e x (1 / sum), the reciprocal taken once per query;
-// P is never rounded to bf16 -- and one fmaf per element into the wave's fp32 partial sum.  q_prescaled: c = 1, as there.
+// (profiles/EXPERIMENTS.md section 9, f10).  Per head, of the building blocks: scores (in the S^T accumulator layout one register
+// index is one key over 32 consecutive queries), the mask (padding keys and keys at or past kv_len[b]) and the softmax that keeps
+// its exponentials in fp32; then p = e x (1 / sum), the reciprocal taken once per query -- P is never rounded to bf16 -- and one
+// fmaf per element into the wave's fp32 partial sum.
 // Reduction order (fixed, the same bits every run): within a wave its heads in ascending order; then the eight partial sums
 // meet in LDS (each wave's own, by now idle, slot: [KB x 32 keys][32 queries] fp32) and every element is summed in wave order,
 // ((((w0 + w1) + w2) + ...) + w7), and multiplied by 1 / H once.  A wave without a head contributes zeros.  The thread that owns an
@@ -1437,56 +1350,23 @@ __global__ __launch_bounds__(64 * MAPS_WAVES) void xattn_maps_kernel(const AttnM
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) stage_tile(tile_src(Qb + h * 64, p.ldq, qrows, hf, lane), 0, dst + KB * 4096, hf);
   };
-  int rf_off[4];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const AttnFragOff fo = attn_frag_off(lane);
   f32x16 macc[KB];
 #pragma unroll
-  for (int kb = 0; kb < KB; ++kb) macc[kb] = zero16;
+  for (int kb = 0; kb < KB; ++kb) macc[kb] = zero_f32x16();
   for (int h = wave; h < p.H; h += MAPS_WAVES) {
     char* const cur = my;
     stage_head(h, cur);                                          // (the slot's last reader: the iteration before, closed below)
     WAIT_VM0();                                                  // this head's rows have landed
     bf16x8 qf[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(cur + KB * 4096 + rf_off[s]);
-    // S^T[key][q] = K . Q^T over the KB key blocks
+    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(cur + KB * 4096 + fo.rf[s]);
     f32x16 sacc[KB];
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + kb * 4096 + rf_off[0]), qf[0], zero16, 0, 0, 0);
-#pragma unroll
-      for (int s = 1; s < 4; ++s)
-        sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + kb * 4096 + rf_off[s]), qf[s], sacc[kb], 0, 0, 0);
-    }
+    xattn_scores<KB>(cur, fo, qf, sacc);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // every read of `cur` is done before a later DMA may land in it
-    // padding keys / keys past this sample's count: -inf (only the blocks that hold any)
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-      if (kb * 32 + 32 > skv_b) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-          sacc[kb][r] = key < skv_b ? sacc[kb][r] : -INFINITY;
-        }
-      }
-    float mx = sacc[0][0];
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-      for (int r = (kb == 0 ? 1 : 0); r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
-    mx = xhalf_max(mx);
-    const float mc = mx * c;
-    float ls = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        sacc[kb][r] = fast_exp2(fmaf(sacc[kb][r], c, -mc));      // masked key: exp2(-inf) = 0
-        ls += sacc[kb][r];
-      }
-    const float inv = 1.f / xhalf_sum(ls);
+    xattn_mask_keys<KB>(sacc, skv_b, fh);                        // padding keys / keys past this sample's count
+    float mx;
+    const float inv = 1.f / xattn_softmax_f32<KB>(sacc, c, mx);
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
@@ -1522,7 +1402,7 @@ __global__ __launch_bounds__(64 * MAPS_WAVES) void xattn_maps_kernel(const AttnM
 //   P0 = softmax(scale Q[s] K[s]^T)   the source's probabilities at the same query positions,   P1 = softmax(scale Q[b] K[b]^T)
 //   A[q][j] = c[b][j] sum_k P0[q][k] Mt[b][j][k] + d[b][j] P1[q][j],   O[b] = A V[b]            (no renormalisation)
 // in ONE launch over the whole batch.  The branch is per workgroup: one of an unedited sample (src[b] < 0) stages its own K and V,
-// runs the arithmetic of xattn_fwd_kernel in its order (same bits) and reads no table; one of an edited sample stages K of the
+// runs the building blocks as xattn_fwd_kernel does (same bits) and reads no table; one of an edited sample stages K of the
 // source, its own K and V (KB = ceil(Skv / 32) half tiles of 32 keys each, through descriptors that end with the sample's last
 // row: padding slots arrive as zeros and score -inf), Mt[b] and c[b] / d[b], and every wave walks its 128-query units with the
 // Q fragments of both samples resident (two LDS-DMA images per wave, one unit ahead).
@@ -1538,8 +1418,8 @@ __global__ __launch_bounds__(64 * MAPS_WAVES) void xattn_maps_kernel(const AttnM
 // Units per workgroup differ: an edited unit is 54 MFMAs and two softmaxes where a plain one is 24 and one, and an edited workgroup
 // stages twice as much, so an edited sample's workgroups take upw_edit units and an unedited sample's upw_plain (attn_plan_edit
 // balances them: with one count for both, 28.6 - 34.9 us at 10 heads x 4096 queries against 19.2 with 8 and 3).
-// LDS: 3 KB 4096 (K, V, source K) + KB 32 (KB 64 + 16) (Mt) + KB 256 (c, d) + 4 x 4096 (O images, XOR-swizzled at a 128-byte
-// pitch as in xattn_regions_fwd_kernel) + 8 x 4096 (Q images): 106 752 bytes at three key blocks -- one workgroup per CU.
+// LDS: 3 KB 4096 (K, V, source K) + KB 32 (KB 64 + 16) (Mt) + KB 256 (c, d) + 4 x 4096 (O images, the swizzled form) +
+// 8 x 4096 (Q images): 106 752 bytes at three key blocks -- one workgroup per CU.
 template <int KB>
 __global__ __launch_bounds__(256, KB == 1 ? 2 : 1) void xattn_edit_fwd_kernel(const AttnEditP p, int upw_plain, int upw_edit) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1616,107 +1496,47 @@ __global__ __launch_bounds__(256, KB == 1 ? 2 : 1) void xattn_edit_fwd_kernel(co
       cdsm[idx] = key < p.Skv ? t[(long long)b * p.Skv + key] : 0.f;
     }
   }
-  int rf_off[4], tr_off[2][2];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
-  {
-    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
-  }
-  char* const qst1 = Osm + 4 * 4096 + wave * 8192;               // this wave's Q image, one unit ahead (as in xattn_fwd_kernel)
-  char* const qst0 = qst1 + 4096;                                // ... and the same rows of the source sample
-  const TileSrc qsrc1 = tile_src(p.Q + (long long)b * p.Sq * p.ldq + head * 64, p.ldq, p.Sq, 0, lane);
-  const TileSrc qsrc0 = tile_src(p.Q + (long long)(ed ? sb : b) * p.Sq * p.ldq + head * 64, p.ldq, p.Sq, 0, lane);
+  const AttnFragOff fo = attn_frag_off(lane);
+  // this wave's Q image, one unit ahead, and the same rows of the source sample
+  const XattnQStage qs1 = {tile_src(p.Q + (long long)b * p.Sq * p.ldq + head * 64, p.ldq, p.Sq, 0, lane), Osm + 4 * 4096 + wave * 8192};
+  const XattnQStage qs0 = {tile_src(p.Q + (long long)(ed ? sb : b) * p.Sq * p.ldq + head * 64, p.ldq, p.Sq, 0, lane), qs1.img + 4096};
   auto stage_q = [&](int row0) {
-    stage_tile(qsrc1, row0, qst1, 0);
-    stage_tile(qsrc1, row0 + 16, qst1 + 2048, 0);
-    if (ed) {
-      stage_tile(qsrc0, row0, qst0, 0);
-      stage_tile(qsrc0, row0 + 16, qst0 + 2048, 0);
-    }
+    qs1.stage(row0);
+    if (ed) qs0.stage(row0);
   };
   if (u_begin < u_end) stage_q(u_begin * 128 + wave * 32);
   WAIT_VM0();
   __syncthreads();
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  // S^T[key][q] = K . Q^T over the KB key blocks, padding slots of the last block -inf
-  auto scores = [&](const char* Ksm, const bf16x8 (&qf)[4], f32x16 (&sacc)[KB]) {
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      bf16x8 kfr[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) kfr[s] = *(const bf16x8*)(Ksm + rf_off[s] + kb * 4096);
-      sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[0], qf[0], zero16, 0, 0, 0);
-#pragma unroll
-      for (int s = 1; s < 4; ++s) sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[s], qf[s], sacc[kb], 0, 0, 0);
-    }
-    if (KB * 32 > p.Skv) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int key = (KB - 1) * 32 + (i & 3) + 8 * (i >> 2) + 4 * fh;
-        sacc[KB - 1][i] = key < p.Skv ? sacc[KB - 1][i] : -INFINITY;
-      }
-    }
-  };
-  // sacc <- exp2(sc (s - max)) in place, in the order xattn_fwd_kernel sums them; returns the sum over all keys
-  auto softmax = [&](f32x16 (&sacc)[KB]) -> float {
-    float mx = sacc[0][0];
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-      for (int i = (kb == 0 ? 1 : 0); i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
-    mx = xhalf_max(mx);
-    const float mc = mx * sc;
-    float ls = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float e = fast_exp2(fmaf(sacc[kb][i], sc, -mc));
-        ls += e;
-        sacc[kb][i] = e;
-      }
-    return xhalf_sum(ls);
-  };
   for (int u = u_begin; u < u_end; ++u) {
     WAIT_VM0();                                                  // this wave's Q images (and its stores of the last unit)
     bf16x8 qf1[4], qf0[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qf1[s] = *(const bf16x8*)(qst1 + rf_off[s]);
-    if (ed) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) qf0[s] = *(const bf16x8*)(qst0 + rf_off[s]);
-    }
+    qs1.load(qf1, fo);
+    if (ed) qs0.load(qf0, fo);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (u + 1 < u_end) stage_q((u + 1) * 128 + wave * 32);
     bf16x8 pf[2 * KB];
-    float l1;
+    float l1, mx;
     if (ed) {
       f32x16 mp[KB];                                             // (Mt P0^T)[j][q], P0 un-normalised
       float l0;
       {
         f32x16 s0[KB];
-        scores(K0sm, qf0, s0);
-        l0 = softmax(s0);
         bf16x8 pf0[2 * KB];
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) pf0[2 * kb + (i >> 3)][i & 7] = (bf16)s0[kb][i];
+        xattn_scores<KB>(K0sm, fo, qf0, s0);
+        xattn_mask_keys<KB, KB - 1>(s0, p.Skv, fh);              // padding slots of the last block
+        l0 = xattn_softmax_bf16<KB>(s0, sc, mx, pf0);
 #pragma unroll
         for (int jb = 0; jb < KB; ++jb)
 #pragma unroll
           for (int ks = 0; ks < 2 * KB; ++ks) {
             const bf16x8 mf = *(const bf16x8*)(Mtsm + (jb * 32 + frow) * MP + ks * 32 + fh * 16);
-            mp[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mf, pf0[ks], ks == 0 ? zero16 : mp[jb], 0, 0, 0);
+            mp[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mf, pf0[ks], ks == 0 ? zero_f32x16() : mp[jb], 0, 0, 0);
           }
       }
       f32x16 s1[KB];
-      scores(K1sm, qf1, s1);
-      l1 = softmax(s1);
+      xattn_scores<KB>(K1sm, fo, qf1, s1);
+      xattn_mask_keys<KB, KB - 1>(s1, p.Skv, fh);
+      l1 = xattn_softmax_f32<KB>(s1, sc, mx);
       const float ratio = l1 / l0;                               // P0 = e0 / sum0, and O is divided by sum1 at the end
 #pragma unroll
       for (int jb = 0; jb < KB; ++jb)
@@ -1732,44 +1552,15 @@ __global__ __launch_bounds__(256, KB == 1 ? 2 : 1) void xattn_edit_fwd_kernel(co
         }
     } else {
       f32x16 s1[KB];
-      scores(K1sm, qf1, s1);
-      l1 = softmax(s1);
-#pragma unroll
-      for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) pf[2 * kb + (i >> 3)][i & 7] = (bf16)s1[kb][i];
+      xattn_scores<KB>(K1sm, fo, qf1, s1);
+      xattn_mask_keys<KB, KB - 1>(s1, p.Skv, fh);
+      l1 = xattn_softmax_bf16<KB>(s1, sc, mx, pf);
     }
-    // O^T[d][q] = V^T[d][key] A^T[key][q]
-    f32x16 oacc[2];
-#pragma unroll
-    for (int ks = 0; ks < 2 * KB; ++ks)
-#pragma unroll
-      for (int db = 0; db < 2; ++db) {
-        const bf16x8 tf = read_transposed_frag_at(Vsm + tr_off[db][0] + ks * 2048, Vsm + tr_off[db][1] + ks * 2048);
-        oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[ks], ks == 0 ? zero16 : oacc[db], 0, 0, 0);
-      }
+    f32x16 oacc[2];                                              // O^T[d][q] = V^T[d][key] A^T[key][q]
+    xattn_pv<KB>(Vsm, fo, pf, oacc);
     const float inv = 1.f / l1;
-    char* const ost = Osm + wave * 4096;                         // O leaves through a per-wave LDS image, as in xattn_regions_fwd_kernel
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16)(oacc[db][4 * g + j] * inv);
-        *(bf16x4*)(ost + frow * 128 + (((db * 4 + g) ^ swz_x(frow)) << 4) + fh * 8) = o;
-      }
-    {
-      const int r8 = lane >> 3, ch = lane & 7;
-      const int q0w = u * 128 + wave * 32;
-      bf16* Ob = p.O + (long long)b * p.Sq * p.ldo + head * 64 + ch * 8;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = i * 8 + r8;
-        const bf16x8 v = *(const bf16x8*)(ost + row * 128 + ((ch ^ swz_x(row)) << 4));
-        if (q0w + row < p.Sq) *(bf16x8*)(Ob + (long long)(q0w + row) * p.ldo) = v;
-      }
-    }
+    store_o_image_swz(Osm + wave * 4096, lane, [&](int db, int i) { return oacc[db][i] * inv; },
+                      p.O + (long long)b * p.Sq * p.ldo + head * 64, p.ldo, u * 128 + wave * 32, p.Sq);
   }
 }
 
@@ -1820,21 +1611,12 @@ __global__ __launch_bounds__(256) void attn_fewq_kernel(const AttnP p) {
   if (wave < 2) stage_tile(tile_src(Qb, p.ldq, p.Sq, wave, lane), 0, Qsm, wave);
   int blk = wave;
   if (blk < nb) stage_blk(blk, my);
-  int rf_off[4], tr_off[2][2];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
-  {
-    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
-  }
+  const AttnFragOff fo = attn_frag_off(lane);
   WAIT_VM0();
   __syncthreads();                                               // the Q image (waves 0 / 1 staged it)
   bf16x8 qf[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(Qsm + rf_off[s]);
+  for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(Qsm + fo.rf[s]);
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;                          // log2 domain; l_run: this half's 16 keys of every block
   f32x16 oacc[2] = {zero16, zero16};
@@ -1845,9 +1627,9 @@ __global__ __launch_bounds__(256) void attn_fewq_kernel(const AttnP p) {
     const bool s2 = blk >= nb1;
     const int valid = (s2 ? p.Skv2 : p.Skv) - (s2 ? blk - nb1 : blk) * 32;     // >= 1; >= 32: a full block
     // S^T[key][q] = K . Q^T
-    f32x16 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + rf_off[0]), qf[0], zero16, 0, 0, 0);
+    f32x16 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + fo.rf[0]), qf[0], zero16, 0, 0, 0);
 #pragma unroll
-    for (int s = 1; s < 4; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + rf_off[s]), qf[s], sacc, 0, 0, 0);
+    for (int s = 1; s < 4; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(cur + fo.rf[s]), qf[s], sacc, 0, 0, 0);
     if (valid < 32) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) sacc[r] = (r & 3) + 8 * (r >> 2) + 4 * fh < valid ? sacc[r] : -INFINITY;
@@ -1875,7 +1657,7 @@ __global__ __launch_bounds__(256) void attn_fewq_kernel(const AttnP p) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
         oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            read_transposed_frag_at(cur + 4096 + tr_off[db][0] + ks * 2048, cur + 4096 + tr_off[db][1] + ks * 2048), pf[ks], oacc[db], 0, 0, 0);
+            read_transposed_frag_at(cur + 4096 + fo.tr[db][0] + ks * 2048, cur + 4096 + fo.tr[db][1] + ks * 2048), pf[ks], oacc[db], 0, 0, 0);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // every read of `cur` is done before a later DMA may land in it
   }
@@ -2374,32 +2156,8 @@ __global__ __launch_bounds__(256, 2) void xattn_bwd2_kernel(const AttnP p, int u
             oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfr[k2][db], pf[k2], oacc[db], 0, 0, 0);
       }
       // dQ^T[d][q] -> LDS image [q][d] -> whole rows, 16 bytes per lane
-      char* const ost = Ost + wave * (32 * 144);
-#pragma unroll
-      for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          bf16x4 o;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) o[j] = (bf16)(oacc[db][4 * g + j] * p.scale);
-          *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
-        }
-      const int r8 = lane >> 3, ch = lane & 7;
-      bf16* dQb = p.dQ + (long long)b * p.Sq * p.lddq + head * 64 + ch * 8;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = i * 8 + r8;
-        if (qg + row < p.Sq) {
-          bf16x8 v = *(const bf16x8*)(ost + row * 144 + ch * 16);
-          bf16* dst = dQb + (long long)(qg + row) * p.lddq;
-          if (p.accum_dq) {
-            const bf16x8 old = *(const bf16x8*)dst;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (bf16)((float)v[j] + (float)old[j]);
-          }
-          *(bf16x8*)dst = v;
-        }
-      }
+      store_o_image_144(Ost + wave * (32 * 144), lane, [&](int db, int i) { return oacc[db][i] * p.scale; },
+                        p.dQ + (long long)b * p.Sq * p.lddq + head * 64, p.lddq, qg, p.Sq, p.accum_dq != 0);
     }
     if (KB > 2) {                                                // the two barriers of the key waves' hand-over below
       __syncthreads();
@@ -3006,6 +2764,15 @@ extern "C" void pea_debug_set_attn_tr(int v) { g_attn_env.use_tr = v; }
 extern "C" void pea_debug_set_attn_xattn(int v) { g_attn_env.xattn = v; }
 extern "C" void pea_debug_set_attn_fused_bwd(int v) { g_attn_env.fused_bwd = v; }
 static bool xattn_v2_keys(int Skv, const AttnEnv& e) { return e.xattn_ver && Skv > 32 && Skv <= 96; }     // v2 OR v3: 64-query units
+// The resident-K/V kernels size their grids to ONE round of the workgroups the chip holds at once: 256 CUs x the workgroups
+// per CU that the kernel's LDS allows (160 KiB per CU, never more than two here).
+static int wgs_per_cu(int lds) { return 2 * lds <= 160 * 1024 ? 2 : 1; }
+static int wg_slots(int per_cu) { return 256 * per_cu; }
+// units per workgroup for that one round: `units` of work in all, `nu` of them per (batch, head)
+static int units_per_wg(long long units, int nu, int per_cu) {
+  const long long upw = (units + wg_slots(per_cu) - 1) / wg_slots(per_cu);
+  return (int)(upw < 1 ? 1 : (upw > nu ? nu : upw));
+}
 // query-range splitting of the cross-attention backward (few keys, many queries): a workgroup owns `u` consecutive
 // 128-query units of one (batch, head); pick the u that minimises (rounds of 512 workgroups: two per CU) x u, then the
 // split count (fp32 partials per split).  1024 tokens, B*H = 80: u = 2 -> 320 workgroups, 4 splits; 4096 tokens, 40:
@@ -3024,7 +2791,7 @@ static int attn_nsplit(int B, int H, int Sq, int Skv, const AttnEnv& e) {
   int best_ns = 1;
   for (int u = 1; u <= nu; ++u) {
     const int ns = (nu + u - 1) / u;
-    const long long rounds = (bh * ns + 511) / 512;
+    const long long rounds = (bh * ns + wg_slots(2) - 1) / wg_slots(2);
     const long long cost = rounds * (u + fixed) * (uq / 2) + ns;
     if (best < 0 || cost < best) { best = cost; best_ns = ns; }
   }
@@ -3044,8 +2811,7 @@ static int attn_decide_fwd(const AttnP& p, const AttnEnv& e, AttnPlan& plan) {
   if (p.K2 || (attn_resident_kv(p, e) && !p.causal && !p.bias && p.Sq >= 128)) {
     const int kb = cdiv(p.Skv, 32), kt = (kb + 1) / 2;
     const int lds = 2 * kt * TILE_BYTES + 4 * 32 * 144 + 4 * 4096 + (p.K2 ? 2 * 4096 : 0);
-    int upw = (int)(((long long)p.B * p.H * nu + 511) / 512);   // one round of two workgroups per CU (66 KB of LDS each, 74 KB with image keys)
-    upw = upw < 1 ? 1 : (upw > nu ? nu : upw);
+    const int upw = units_per_wg((long long)p.B * p.H * nu, nu, 2);   // two workgroups per CU (66 KB of LDS each, 74 KB with image keys)
     plan.add(AK_XFWD + 4 * (!p.K2 ? 0 : p.nset ? 2 : 1) + (kb - 1), dim3(cdiv(nu, upw), p.H, p.B), lds, upw);
     return PEA_OK;
   }
@@ -3168,18 +2934,19 @@ static int attn_plan(int dir, AttnP& p, const AttnEnv& e, AttnPlan& plan) {
   }
   return attn_decide_fwd(p, e, plan);
 }
-// hipFuncAttributeMaxDynamicSharedMemorySize of kernel K raised to `bytes`, once per process, then the launch: every
-// kernel of this file that takes dynamic LDS goes through here, so no list of instantiations has to be kept by hand.
-// The attribute call belongs to an instantiation's FIRST launch: if that launch is inside a stream capture, the call
-// happens during the capture (it is not a stream operation and is not recorded).
-template <auto K, typename... Args>
+// hipFuncAttributeMaxDynamicSharedMemorySize of kernel K raised once per process, then the launch with THREADS per workgroup:
+// every kernel of this file that takes dynamic LDS goes through here, so no list of instantiations has to be kept by hand.
+// The limit is raised to LIMIT bytes, the most any launch of K takes, or (LIMIT = 0: every launch of K takes the same) to the
+// first launch's.  The attribute call belongs to an instantiation's FIRST launch: if that launch is inside a stream capture,
+// the call happens during the capture (it is not a stream operation and is not recorded).
+template <auto K, int THREADS = 256, int LIMIT = 0, typename... Args>
 static int launch_lds(dim3 grid, int bytes, hipStream_t s, const Args&... args) {
   static bool raised = false;
   if (!raised) {
-    HIPCHK(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    HIPCHK(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, LIMIT ? LIMIT : bytes));
     raised = true;
   }
-  hipLaunchKernelGGL(K, grid, dim3(256), bytes, s, args...);
+  hipLaunchKernelGGL(K, grid, dim3(THREADS), bytes, s, args...);
   return PEA_OK;
 }
 // enumerator -> instantiation: the one place that names them
@@ -3268,10 +3035,40 @@ extern "C" int pea_debug_attn_dispatch(const int* q, int* out) {
   return PEA_OK;
 }
 
+// ============================================================================= host: what the feature launchers below share
+// The operand checks of a feature launch (regions, maps, edit, shared), in this order: every operand there, a finite positive
+// scale, Q / K / V rows that are multiples of 8 elements (16-byte loads, LDS-DMA) and hold all H heads of 64, the same for O
+// at the width it is stored with (o_bytes 16: ldo % 8; 8: ldo % 4; 0: no O), base addresses aligned to match.  f32: the fp32
+// operands (4-byte aligned), the first of which must be there where need_f32 says so.  A launch without V passes K in its place.
+struct AttnOperands { const bf16 *Q, *K, *V; int ldq, ldk, ldv; const bf16* O; int ldo, o_bytes; const void *f32, *f32_opt; bool need_f32; };
+static int attn_check_operands(const char* who, const AttnOperands& a, int H, float scale) {
+  SHAPECHK(a.Q && a.K && a.V && (a.O || !a.o_bytes) && (a.f32 || !a.need_f32), "%s: null operand", who);
+  SHAPECHK(scale > 0.f && scale <= 3.0e38f, "%s: a finite positive scale (%g)", who, (double)scale);
+  const int C = 64 * H;
+  SHAPECHK(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldq >= C && a.ldk >= C && a.ldv >= C,
+           "%s: leading dimensions ldq / ldk / ldv must be multiples of 8 and hold every head (%d %d %d)", who, a.ldq, a.ldk, a.ldv);
+  SHAPECHK(!a.o_bytes || (a.ldo % (a.o_bytes / 2) == 0 && a.ldo >= C),
+           "%s: leading dimension ldo must be a multiple of %d and hold every head (ldo=%d)", who, a.o_bytes / 2, a.ldo);
+  const unsigned long long in_bits = (unsigned long long)a.Q | (unsigned long long)a.K | (unsigned long long)a.V;
+  SHAPECHK(in_bits % 16 == 0 && (!a.o_bytes || (unsigned long long)a.O % a.o_bytes == 0) &&
+               ((unsigned long long)a.f32 | (unsigned long long)a.f32_opt) % 4 == 0,
+           "%s: Q / K / V 16-byte, O %d-byte, fp32 operands 4-byte aligned", who, a.o_bytes);
+  return PEA_OK;
+}
+// the plain attention over a feature's operands: what its unedited / plain samples compute, on the host and on the device
+template <class P>
+__host__ __device__ static inline AttnP attn_plain_p(const P& p) {
+  AttnP a = AttnP();
+  a.Q = p.Q; a.K = p.K; a.V = p.V; a.ldq = p.ldq; a.ldk = p.ldk; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
+  a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
+  return a;
+}
+
 // ============================================================================= host: regional text prompts
 // A launcher of its own beside the decision table above (which, with AK_COUNT, attn_plan and pea_debug_attn_dispatch, does not
-// know it): the shape checks, the LDS and grid rule, the launch.  Units per workgroup are sized as attn_decide_fwd sizes them,
-// one round of the workgroups the LDS lets a CU hold: two up to 80 KiB (two regions of 77 keys: 81 920 bytes exactly), one above.
+// know it): the shape checks, the LDS and grid rule, the launch.  Units per workgroup as attn_decide_fwd sizes them
+// (units_per_wg): two workgroups per CU up to 80 KiB (two regions of 77 keys: 81 920 bytes exactly), one above.
+constexpr int regions_lds(int R, int kb) { return R * kb * 2 * 4096 + 4 * 4096 + 4 * 4096; }   // K and V blocks, O images, Q images
 struct AttnRegionsPlan { int kb, lds, upw; dim3 grid; };
 static int attn_plan_regions(AttnRegionsP& p, AttnRegionsPlan& plan) {
   if (p.nd == 0) p.nd = 1;
@@ -3280,34 +3077,13 @@ static int attn_plan_regions(AttnRegionsP& p, AttnRegionsPlan& plan) {
   SHAPECHK(p.R >= 1 && p.R <= 4, "attention_regions: 1..4 regions (R=%d)", p.R);
   SHAPECHK(p.Lr >= 1 && p.Lr <= 96, "attention_regions: 1..96 keys per region (Lr=%d)", p.Lr);
   SHAPECHK(p.Bw == 1 || p.Bw == p.B, "attention_regions: Bw=%d (1, or the batch %d)", p.Bw, p.B);
-  SHAPECHK(p.Q && p.K && p.V && p.O && p.w, "attention_regions: null operand");
-  SHAPECHK(p.scale > 0.f && p.scale <= 3.0e38f, "attention_regions: a finite positive scale (%g)", (double)p.scale);
-  const int C = 64 * p.H;
-  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldq >= C && p.ldk >= C && p.ldv >= C,
-           "attention_regions: ldq / ldk / ldv must be multiples of 8 and hold every head (%d %d %d)", p.ldq, p.ldk, p.ldv);
-  SHAPECHK(p.ldo % 4 == 0 && p.ldo >= C, "attention_regions: ldo %% 4, ldo >= 64 H (ldo=%d)", p.ldo);
-  const unsigned long long in_bits = (unsigned long long)p.Q | (unsigned long long)p.K | (unsigned long long)p.V;
-  SHAPECHK(in_bits % 16 == 0 && (unsigned long long)p.O % 8 == 0 && (unsigned long long)p.w % 4 == 0,
-           "attention_regions: Q / K / V 16-byte, O 8-byte, w 4-byte aligned");
+  if (int rc = attn_check_operands("attention_regions", {p.Q, p.K, p.V, p.ldq, p.ldk, p.ldv, p.O, p.ldo, 8, p.w, nullptr, true}, p.H, p.scale)) return rc;
   SHAPECHK((long long)p.R * p.Sq * (p.Bw == 1 ? 1 : p.B) < (1ll << 40), "attention_regions: weight table too large");
   plan.kb = cdiv(p.Lr, 32);
-  plan.lds = p.R * plan.kb * 2 * 4096 + 4 * 4096 + 4 * 4096;
-  const int nu = cdiv(p.Sq, 128), per_cu = 2 * plan.lds <= 160 * 1024 ? 2 : 1;
-  long long upw = ((long long)p.B * p.H * nu + 256 * per_cu - 1) / (256 * per_cu);
-  plan.upw = (int)(upw < 1 ? 1 : (upw > nu ? nu : upw));
+  plan.lds = regions_lds(p.R, plan.kb);
+  const int nu = cdiv(p.Sq, 128);
+  plan.upw = units_per_wg((long long)p.B * p.H * nu, nu, wgs_per_cu(plan.lds));
   plan.grid = dim3(cdiv(nu, plan.upw), p.H, p.B);
-  return PEA_OK;
-}
-// an instantiation's LDS grows with R: its limit is raised once, to what four regions take (launch_lds raises to the first launch's bytes)
-template <int KB>
-static int launch_regions(const AttnRegionsPlan& plan, const AttnRegionsP& p, hipStream_t s) {
-  static bool raised = false;
-  if (!raised) {
-    HIPCHK(hipFuncSetAttribute((const void*)xattn_regions_fwd_kernel<KB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               4 * KB * 2 * 4096 + 4 * 4096 + 4 * 4096));
-    raised = true;
-  }
-  hipLaunchKernelGGL(xattn_regions_fwd_kernel<KB>, plan.grid, dim3(256), plan.lds, s, p, plan.upw);
   return PEA_OK;
 }
 int launch_attention_fwd_regions(const AttnRegionsP& p0, hipStream_t s) {
@@ -3319,10 +3095,11 @@ int launch_attention_fwd_regions(const AttnRegionsP& p0, hipStream_t s) {
   if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.R * p.Lr; g_prof_tag[3] = 1; }
   PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * keys * 64, 2.0 * p.B * p.H * 64 * (2.0 * p.Sq + 2.0 * keys), s);
   int lrc = PEA_OK;
+  // an instantiation's LDS grows with R: its limit is raised to what four regions take
   switch (plan.kb) {
-    case 1: lrc = launch_regions<1>(plan, p, s); break;
-    case 2: lrc = launch_regions<2>(plan, p, s); break;
-    default: lrc = launch_regions<3>(plan, p, s); break;
+    case 1: lrc = launch_lds<xattn_regions_fwd_kernel<1>, 256, regions_lds(4, 1)>(plan.grid, plan.lds, s, p, plan.upw); break;
+    case 2: lrc = launch_lds<xattn_regions_fwd_kernel<2>, 256, regions_lds(4, 2)>(plan.grid, plan.lds, s, p, plan.upw); break;
+    default: lrc = launch_lds<xattn_regions_fwd_kernel<3>, 256, regions_lds(4, 3)>(plan.grid, plan.lds, s, p, plan.upw); break;
   }
   PROF_END(s);
   if (lrc) return lrc;
@@ -3358,30 +3135,12 @@ static int attn_plan_maps(AttnMapsP& p, AttnMapsPlan& plan) {
   SHAPECHK(p.B > 0 && p.B <= 65535 && p.H > 0 && p.H <= 65535 && p.Sq >= 1, "attention_maps: empty problem (B=%d H=%d Sq=%d)", p.B, p.H, p.Sq);
   SHAPECHK(p.nd == 1, "attention_maps: head_dim 64 only (nd=%d)", p.nd);
   SHAPECHK(p.Skv >= 1 && p.Skv <= 128, "attention_maps: 1..128 keys (Skv=%d)", p.Skv);
-  SHAPECHK(p.Q && p.K && p.maps, "attention_maps: null operand");
-  SHAPECHK(p.scale > 0.f && p.scale <= 3.0e38f, "attention_maps: a finite positive scale (%g)", (double)p.scale);
-  const int C = 64 * p.H;
-  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldq >= C && p.ldk >= C,
-           "attention_maps: ldq / ldk must be multiples of 8 and hold every head (%d %d)", p.ldq, p.ldk);
-  SHAPECHK(((unsigned long long)p.Q | (unsigned long long)p.K) % 16 == 0 && (unsigned long long)p.maps % 4 == 0 &&
-               (unsigned long long)p.kv_len % 4 == 0,
-           "attention_maps: Q / K 16-byte, maps / kv_len 4-byte aligned");
+  if (int rc = attn_check_operands("attention_maps", {p.Q, p.K, p.K, p.ldq, p.ldk, p.ldk, nullptr, 0, 0, p.maps, p.kv_len, true}, p.H, p.scale)) return rc;
   SHAPECHK((long long)p.ldq * 64 < (1ll << 30) && (long long)p.ldk * 64 < (1ll << 30), "attention_maps: leading dimension too large");
   plan.kb = cdiv(p.Skv, 32);
   plan.lds = MAPS_WAVES * (plan.kb + 1) * 4096;
   plan.upw = 1;
   plan.grid = dim3(cdiv(p.Sq, 32), p.B, 1);
-  return PEA_OK;
-}
-// (launch_lds launches 256 threads; this kernel's workgroup is eight waves)
-template <int KB>
-static int launch_maps(const AttnMapsPlan& plan, const AttnMapsP& p, hipStream_t s) {
-  static bool raised = false;
-  if (!raised) {
-    HIPCHK(hipFuncSetAttribute((const void*)xattn_maps_kernel<KB>, hipFuncAttributeMaxDynamicSharedMemorySize, plan.lds));
-    raised = true;
-  }
-  hipLaunchKernelGGL(xattn_maps_kernel<KB>, plan.grid, dim3(64 * MAPS_WAVES), plan.lds, s, p);
   return PEA_OK;
 }
 int launch_attention_maps(const AttnMapsP& p0, hipStream_t s) {
@@ -3393,11 +3152,11 @@ int launch_attention_maps(const AttnMapsP& p0, hipStream_t s) {
   PROF_BEGIN(2, 2.0 * p.B * p.H * (double)p.Sq * p.Skv * 64,
              2.0 * p.B * p.H * 64 * ((double)p.Sq + p.Skv) + (p.accumulate ? 8.0 : 4.0) * p.B * (double)p.Sq * p.Skv, s);
   int lrc = PEA_OK;
-  switch (plan.kb) {
-    case 1: lrc = launch_maps<1>(plan, p, s); break;
-    case 2: lrc = launch_maps<2>(plan, p, s); break;
-    case 3: lrc = launch_maps<3>(plan, p, s); break;
-    default: lrc = launch_maps<4>(plan, p, s); break;
+  switch (plan.kb) {                                               // (this kernel's workgroup is eight waves)
+    case 1: lrc = launch_lds<xattn_maps_kernel<1>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p); break;
+    case 2: lrc = launch_lds<xattn_maps_kernel<2>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p); break;
+    case 3: lrc = launch_lds<xattn_maps_kernel<3>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p); break;
+    default: lrc = launch_lds<xattn_maps_kernel<4>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p); break;
   }
   PROF_END(s);
   if (lrc) return lrc;
@@ -3442,14 +3201,7 @@ static int attn_plan_edit(AttnEditP& p, AttnEditPlan& plan) {
   SHAPECHK(p.B <= 32, "attention_edit: at most 32 samples, src travels in the kernel arguments (B=%d)", p.B);
   SHAPECHK(p.nd == 1, "attention_edit: head_dim 64 only (nd=%d)", p.nd);
   SHAPECHK(p.Skv <= 96, "attention_edit: 1..96 keys (Skv=%d)", p.Skv);
-  SHAPECHK(p.Q && p.K && p.V && p.O, "attention_edit: null operand");
-  SHAPECHK(p.scale > 0.f && p.scale <= 3.0e38f, "attention_edit: a finite positive scale (%g)", (double)p.scale);
-  const int C = 64 * p.H;
-  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldq >= C && p.ldk >= C && p.ldv >= C,
-           "attention_edit: leading dimensions ldq / ldk / ldv must be multiples of 8 and hold every head (%d %d %d)", p.ldq, p.ldk, p.ldv);
-  SHAPECHK(p.ldo % 4 == 0 && p.ldo >= C, "attention_edit: ldo %% 4, ldo >= 64 H (ldo=%d)", p.ldo);
-  const unsigned long long in_bits = (unsigned long long)p.Q | (unsigned long long)p.K | (unsigned long long)p.V;
-  SHAPECHK(in_bits % 16 == 0 && (unsigned long long)p.O % 8 == 0, "attention_edit: Q / K / V 16-byte, O 8-byte aligned");
+  if (int rc = attn_check_operands("attention_edit", {p.Q, p.K, p.V, p.ldq, p.ldk, p.ldv, p.O, p.ldo, 8, nullptr, nullptr, false}, p.H, p.scale)) return rc;
   plan.n_edited = 0;
   for (int b = 0; b < p.B; ++b)
     if (p.src[b] == b) p.src[b] = -1;                              // its own source: not edited
@@ -3468,13 +3220,9 @@ static int attn_plan_edit(AttnEditP& p, AttnEditPlan& plan) {
   }
   plan.kb = cdiv(p.Skv, 32);
   plan.lds = 3 * plan.kb * 4096 + plan.kb * 32 * (plan.kb * 64 + 16) + plan.kb * 256 + 4 * 4096 + 8 * 4096;
-  AttnP& a = plan.plain;
-  a = AttnP();
-  a.Q = p.Q; a.ldq = p.ldq; a.K = p.K; a.ldk = p.ldk; a.V = p.V; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
-  a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
+  plan.plain = attn_plain_p(p);
   plan.pplan = AttnPlan();
-  const int rc = attn_plan(0, a, g_attn_env, plan.pplan);
-  if (rc) return rc;
+  if (int rc = attn_plan(0, plan.plain, g_attn_env, plan.pplan)) return rc;
   const int k0 = plan.pplan.l[0].kernel;
   plan.plain_first = !(plan.pplan.n == 1 && k0 >= AK_XFWD && k0 < AK_XFWD + 4);
   // Units per workgroup, one count for the unedited samples' workgroups and one for the edited ones': ONE round of the
@@ -3483,7 +3231,7 @@ static int attn_plan_edit(AttnEditP& p, AttnEditPlan& plan) {
   // the one whose longest workgroup is shortest by the times measured at 77 keys (profiles/EXPERIMENTS.md section 9, f11): an edited
   // workgroup of u units 6.4 + 3.7 u us, a plain one 3.0 + 2.0 u.  Where not even one workgroup per (sample, head) fits in a
   // round, each takes all units of its head.  The grid is 1-D and holds exactly the workgroups that have work.
-  const int nu = cdiv(p.Sq, 128), slots = 256 * (2 * plan.lds <= 160 * 1024 ? 2 : 1);
+  const int nu = cdiv(p.Sq, 128), slots = wg_slots(wgs_per_cu(plan.lds));
   const long long n_ed = plan.n_edited, n_un = plan.plain_first ? 0 : p.B - n_ed;    // (plain first: the grid holds the edited samples only)
   plan.upw = plan.upw_edit = nu;
   long long best = -1;
@@ -3748,16 +3496,7 @@ __device__ __forceinline__ void attn_shared_body(const AttnSharedP& p, char* sme
   WAIT_VM0();
   __syncthreads();
 
-  int rf_off[4], tr_off[2][2];                                   // per-lane LDS byte offsets (attn_q_body)
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) rf_off[s4] = frow * 128 + (((2 * s4 + fh) ^ swz_x(frow)) << 4);
-  {
-    const int i16 = lane & 15, rr = 4 * fh + (i16 >> 2), cc = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) tr_off[db][hl] = swz_rc(rr + 8 * hl, db * 32 + cc);
-  }
+  const AttnFragOff fo = attn_frag_off(lane);
 
   for (int t = 0; t < 2 * nt; ++t) {
     const int cur = t & 1;
@@ -3781,11 +3520,11 @@ __device__ __forceinline__ void attn_shared_body(const AttnSharedP& p, char* sme
     {
       const int sb = cur * STG, tb = sb + TILE_BYTES;
 #pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) rfc[s4] = rf_off[s4] + sb;
+      for (int s4 = 0; s4 < 4; ++s4) rfc[s4] = fo.rf[s4] + sb;
 #pragma unroll
       for (int db = 0; db < 2; ++db)
 #pragma unroll
-        for (int hl = 0; hl < 2; ++hl) trc[db][hl] = tr_off[db][hl] + tb;
+        for (int hl = 0; hl < 2; ++hl) trc[db][hl] = fo.tr[db][hl] + tb;
     }
     f32x16 sacc[2];
     {
@@ -3877,23 +3616,8 @@ __device__ __forceinline__ void attn_shared_body(const AttnSharedP& p, char* sme
   float la = l_run, lb = l_run;
   swap_halves32(la, lb);
   const float inv = 1.f / (la + lb);
-  char* const ost = smem + wave * (32 * 144);
-  const int r8 = lane >> 3, ch = lane & 7;
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      bf16x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = (bf16)(oacc[db][4 * g + j] * inv);
-      *(bf16x4*)(ost + frow * 144 + (db * 32 + 8 * g + 4 * fh) * 2) = o;
-    }
-  bf16* Ob = p.O + (long long)b * S * p.ldo + head * 64 + ch * 8;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = i * 8 + r8;
-    if (q0 + row < S) *(bf16x8*)(Ob + (long long)(q0 + row) * p.ldo) = *(const bf16x8*)(ost + row * 144 + ch * 16);
-  }
+  store_o_image_144(smem + wave * (32 * 144), lane, [&](int db, int i) { return oacc[db][i] * inv; },
+                    p.O + (long long)b * S * p.ldo + head * 64, p.ldo, q0, S);
 }
 
 // attn_block_coords' rule on a 1-D range of `total` workgroups: dispatch position -> position in an order where each XCD runs
@@ -3917,10 +3641,7 @@ __global__ __launch_bounds__(256, 3) void attn_shared_kernel(const AttnSharedP p
   if (tgt) {
     attn_shared_body(p, smem, blk, head, b, p.ref[b]);
   } else {
-    AttnP a = AttnP();
-    a.Q = p.Q; a.K = p.K; a.V = p.V; a.ldq = p.ldq; a.ldk = p.ldk; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
-    a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
-    attn_q_body<0, true, 1, false, true>(a, smem, blk, head, b);
+    attn_q_body<0, true, 1, false, true>(attn_plain_p(p), smem, blk, head, b);
   }
 }
 
@@ -3936,14 +3657,7 @@ static int attn_plan_shared(AttnSharedP& p, AttnSharedPlan& plan) {
   SHAPECHK(p.B <= 32, "attention_shared: at most 32 samples, ref travels in the kernel arguments (B=%d)", p.B);
   SHAPECHK(p.nd == 1, "attention_shared: head_dim 64 only (nd=%d)", p.nd);
   SHAPECHK(p.Sq == p.Skv, "attention_shared: self-attention only, Sq == Skv (Sq=%d Skv=%d)", p.Sq, p.Skv);
-  SHAPECHK(p.Q && p.K && p.V && p.O, "attention_shared: null operand");
-  SHAPECHK(p.scale > 0.f && p.scale <= 3.0e38f, "attention_shared: a finite positive scale (%g)", (double)p.scale);
-  const int C = 64 * p.H;
-  SHAPECHK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldq >= C && p.ldk >= C && p.ldv >= C,
-           "attention_shared: leading dimensions ldq / ldk / ldv must be multiples of 8 and hold every head (%d %d %d)", p.ldq, p.ldk, p.ldv);
-  SHAPECHK(p.ldo % 8 == 0 && p.ldo >= C, "attention_shared: leading dimension ldo must be a multiple of 8 and hold every head (ldo=%d)", p.ldo);
-  const unsigned long long bits = (unsigned long long)p.Q | (unsigned long long)p.K | (unsigned long long)p.V | (unsigned long long)p.O;
-  SHAPECHK(bits % 16 == 0, "attention_shared: Q / K / V / O 16-byte aligned");
+  if (int rc = attn_check_operands("attention_shared", {p.Q, p.K, p.V, p.ldq, p.ldk, p.ldv, p.O, p.ldo, 16, nullptr, nullptr, false}, p.H, p.scale)) return rc;
   unsigned targets = 0, used = 0;
   if (int rc = shared_ref_check("attention_shared", p.ref, p.B, targets, used)) return rc;
   plan.n_tgt = __builtin_popcount(targets);
@@ -3957,12 +3671,9 @@ static int attn_plan_shared(AttnSharedP& p, AttnSharedPlan& plan) {
              "attention_shared: finite shared_score_scale / shared_score_shift (%g %g)", (double)p.share_scale, (double)p.share_shift);
   }
   plan.lds = 2 * 2 * TILE_BYTES;
-  AttnP& a = plan.plain;
-  a = AttnP();
-  a.Q = p.Q; a.ldq = p.ldq; a.K = p.K; a.ldk = p.ldk; a.V = p.V; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
-  a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
+  plan.plain = attn_plain_p(p);
   plan.pplan = AttnPlan();
-  if (int rc = attn_plan(0, a, g_attn_env, plan.pplan)) return rc;
+  if (int rc = attn_plan(0, plan.plain, g_attn_env, plan.pplan)) return rc;
   plan.plain_first = !(plan.pplan.n == 1 && plan.pplan.l[0].kernel == AK_Q + 3);
   const int nu = cdiv(p.Sq, 128);
   int n = 0;
