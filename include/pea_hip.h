@@ -977,6 +977,60 @@ int pea_unet_num_self_attention_layers(void* unet);      /* a count, or a negati
  * ceil(S / 128) workgroups per sample, the targets' first; y = z = 1.  LDS = 2 stages x (K tile + V tile) x 8192 bytes. */
 int pea_debug_attn_shared_dispatch(const int* q, int* out);
 
+/* ---- self-attention guidance (Hong et al. 2023, "Improving Sample Quality of Diffusion Models Using Self-Attention Guidance"): a
+ * second guidance term from the model's own self-attention, no training, no weights.  A restatement from the paper and the public
+ * pipelines (unpinned).
+ * pea_op_attention_colsum: the probability mass each key receives from all queries, head_dim 64, ONE launch, no V / O:
+ *   part[b][g][k] = (1 / H) sum_{h in group g} sum_q exp(scale Q[b, q, h, :] . K[b, k, h, :] - lse[b][h][q])
+ * Q [B][Sq][ldq], K [B][Skv][ldk] bf16 holding all H heads; lse device fp32 [B][H][Sq], natural log, as pea_op_attention_fwd writes
+ * it; part device fp32 [B][G][Skv], G = pea_op_attention_colsum_groups(B, H, Sq, Skv) groups of consecutive heads (a positive
+ * count, or PEA_E_SHAPE for an empty problem).  The column sum of the head-mean softmax is part[b][0][k] + part[b][1][k] + ... in
+ * ascending g, which the consumer adds (pea_op_sag_degrade does): no reduce launch, no atomics.  q_prescaled: Q arrives multiplied
+ * by scale * log2(e); otherwise that factor multiplies the fp32 score, and no bf16 operand is rounded a second time.  The
+ * probabilities stay fp32.  Keys on the lane: a workgroup is 128 keys of one (sample, head group) and streams the Q tiles of its
+ * heads; sums run over a lane's queries, then tiles, then heads in ascending order, then the two halves of the wave: the same bits
+ * every run.  Query rows at or past Sq and key rows at or past Skv of an over-allocated buffer are never used.  Any Sq >= 1, Skv >= 1;
+ * B <= 65535 (grid z), H <= 65535; ldq / ldk multiples of 8 holding every head, Q / K 16-byte aligned; one sample's Q or K below
+ * 2 GiB.  Every refusal is PEA_E_SHAPE before any launch: an empty problem, a null operand, a null lse, a leading dimension that is
+ * no multiple of 8. */
+int pea_op_attention_colsum_groups(int B, int H, int Sq, int Skv);
+int pea_op_attention_colsum(const void* Q, int ldq, const void* K, int ldk, const float* lse, float* part, int B, int H, int Sq, int Skv,
+                            float scale, int q_prescaled, void* stream);
+/* Test aid, needs no device: what pea_op_attention_colsum launches (shape checks included).  q[8] = { B, H, Sq, Skv, nd, ldq (<= 0:
+ * 64 H), ldk (<= 0: 64 H), flags (1: q_prescaled, 2: null lse) }.  Returns PEA_OK and out[6] = { G, grid x / y / z, dynamic LDS
+ * bytes, heads per group }, or the error code of a refused problem.  grid = ceil(Skv / 128) x G x B, workgroups of 256 threads;
+ * LDS = 2 stages x 4 x (8192-byte Q tile + 256 bytes of row constants).  G: the fewest groups that give 512 workgroups, at most H, made
+ * even: heads per group = ceil(H / that), G = ceil(H / heads per group). */
+int pea_debug_attn_colsum_dispatch(const int* q, int* out);
+/* pea_op_sag_degrade: mask, blur and degraded model input in ONE launch.  latents, eps, out: fp32 [B][C][H][W]; part: fp32
+ * [B][G][map_h map_w] from pea_op_attention_colsum (any G >= 1); iy int[H], ix int[W] device tables: latent row / column -> map row /
+ * column (nearest: min(floor(dst * (float)in / out), in - 1), built on the host).
+ *   A = part[b][0][k] + part[b][1][k] + ...  (ascending g, fp32),  m = A > 1.0f at k = iy[y] map_w + ix[x], shared by every channel
+ *   x0 = c_x x + c_e eps;  x0_blur: 9 x 9 Gaussian of x0, taps exp(-i^2 / 2) / sum, separable (rows, then columns), reflect padding of
+ *   4 without edge repeat;  out = o_b (m ? x0_blur : x0) + o_e eps
+ * Where m is false the result is o_b (c_x x + c_e eps) + o_e eps evaluated in that order, every product and sum rounded once.
+ * PEA_E_SHAPE before any launch: H < 5 or W < 5, G < 1, a null operand, an empty problem. */
+int pea_op_sag_degrade(const float* latents, const float* eps, const float* part, int G, int map_h, int map_w, const int* iy,
+                       const int* ix, float* out, int B, int C, int H, int W, float c_x, float c_e, float o_b, float o_e, void* stream);
+/* pea_op_cfg_sag_combine: cfg != 0: eps fp32 [2B][per] (unconditional half first), out[B][per] = u + g (t - u) + s (u - eps_deg);
+ * sag_scale = 0 gives the bits of pea_op_cfg_combine at guidance_rescale 0.  cfg == 0: eps [B][per], out = eps + s (eps - eps_deg).
+ * eps_deg fp32 [B][per]: the prediction on the degraded input. */
+int pea_op_cfg_sag_combine(const float* eps, const float* eps_deg, float* out, int B, long long per, int cfg, float guidance_scale,
+                           float sag_scale, void* stream);
+/* The capture in a UNet context (graph 0, inference), a runtime state like regions, maps, edits and StyleAligned: the tape, the plans
+ * and the arenas do not change.  layer: an index into the self-attention layers in the order of pea_unet_num_self_attention_layers.
+ * While enabled, that layer's ordinary launch is handed an lse buffer of the state's own (fp32 [B][H][S], outside the arenas) and is
+ * followed by ONE pea_op_attention_colsum over samples first_sample .. first_sample + n_samples - 1; the ordinary launch, its
+ * dispatch decision and its O do not change: a forward gives the bits it gives without capture.  pea_unet_sag_colsum: the
+ * partials of the last forward, device fp32 [n_samples][G][S], with G and S.  Refused (PEA_E_STATE / PEA_E_SHAPE; by a forward too,
+ * before its first launch): a PEA_UNET_GRAD context, a layer whose head_dim is not 64, live prompt editing, StyleAligned switched
+ * on for that same layer (both rewrite or replace that launch), a layer or sample range outside the context.  Image prompts,
+ * regions, heat maps, FreeU, ControlNet residuals and inpainting combine freely.  pea_unet_disable_sag synchronises the device
+ * and frees the buffers; after it a forward gives the bits it gave before. */
+int pea_unet_enable_sag(void* unet, int layer, int first_sample, int n_samples);
+int pea_unet_disable_sag(void* unet);
+int pea_unet_sag_colsum(void* unet, float** part, int* G, int* S);
+
 #ifdef __cplusplus
 }
 #endif

@@ -838,6 +838,57 @@ int pea_unet_clear_style_aligned(void* h) {
   u->style = nullptr;
   return PEA_OK;
 }
+// ------------------------------------------------------------------------------ self-attention guidance
+int pea_unet_enable_sag(void* h, int layer, int first_sample, int n_samples) {
+  NOTNULL(h, "pea_unet_enable_sag");
+  Tape* u = (Tape*)h;
+  if (u->graph != 0) { pea_set_error("pea_unet_enable_sag: not a UNet handle (graph %d)", u->graph); return PEA_E_INVALID; }
+  std::map<int, int> layer_of_op;
+  const int want = self_attn_layers(*u, &layer_of_op);
+  SHAPECHK(layer >= 0 && layer < want, "pea_unet_enable_sag: layer %d, this UNet has %d self-attention layers", layer, want);
+  SHAPECHK(first_sample >= 0 && n_samples >= 1 && first_sample + n_samples <= u->B,
+           "pea_unet_enable_sag: samples %d .. %d of a batch of %d", first_sample, first_sample + n_samples - 1, u->B);
+  Tape::SagState* st = new Tape::SagState();
+  std::unique_ptr<Tape::SagState> guard(st);
+  for (const auto& lo : layer_of_op)
+    if (lo.second == layer) st->op = lo.first;
+  const Op& o = u->ops[st->op];
+  const int head_dim = (int)lroundf(1.f / (o.f0 * o.f0));           // (the softmax scale is head_dim^-1/2; padded heads keep their own)
+  SHAPECHK(o.p3 == 1 && head_dim == 64, "pea_unet_enable_sag: self-attention layer %d has head_dim %d (stored as %d); the column-sum "
+           "kernel is built for 64", layer, head_dim, 64 * o.p3);
+  st->layer = layer; st->first = first_sample; st->n = n_samples; st->H = o.p0; st->S = o.p1;
+  st->G = attention_colsum_groups(n_samples, o.p0, o.p1, o.p2);
+  if (st->G < 1) return PEA_E_SHAPE;
+  RCX(pea_unet_disable_sag(h));
+  u->sag = st;                                                      // (the checks read the state they judge)
+  const int rc = u->sag_check(false);
+  u->sag = nullptr;
+  if (rc) return rc;
+  hipError_t err = hipMalloc((void**)&st->lse, sizeof(float) * (size_t)u->B * o.p0 * o.p1);
+  if (err == hipSuccess) err = hipMalloc((void**)&st->part, sizeof(float) * (size_t)n_samples * st->G * o.p2);
+  if (err == hipSuccess) err = hipMemset(st->part, 0, sizeof(float) * (size_t)n_samples * st->G * o.p2);
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  if (err != hipSuccess) { pea_set_error("pea_unet_enable_sag: %s", hipGetErrorString(err)); return PEA_E_HIP; }
+  u->sag = guard.release();
+  return PEA_OK;
+}
+int pea_unet_disable_sag(void* h) {
+  NOTNULL(h, "pea_unet_disable_sag");
+  Tape* u = (Tape*)h;
+  if (u->sag) HIPCHK(hipDeviceSynchronize());        // a queued forward may still write the buffers
+  delete u->sag;
+  u->sag = nullptr;
+  return PEA_OK;
+}
+int pea_unet_sag_colsum(void* h, float** part, int* G, int* S) {
+  NOTNULL(h, "pea_unet_sag_colsum");
+  Tape* u = (Tape*)h;
+  if (!u->sag) { pea_set_error("pea_unet_sag_colsum: call pea_unet_enable_sag first"); return PEA_E_STATE; }
+  if (part) *part = u->sag->part;
+  if (G) *G = u->sag->G;
+  if (S) *S = u->sag->S;
+  return PEA_OK;
+}
 // ------------------------------------------------------------------------------ cross-attention heat maps
 int pea_unet_enable_attention_maps(void* h, const float* layer_on, int n_layers) {
   NOTNULL(h, "pea_unet_enable_attention_maps");

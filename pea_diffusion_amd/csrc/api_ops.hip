@@ -470,6 +470,23 @@ int pea_op_euler_update(float* sample, const float* eps, const float* noise, flo
                         float k_n, float k_s, void* stream) {
   return launch_euler_update(sample, eps, noise, model_in, n, dup, k_e, k_n, k_s, (hipStream_t)stream);
 }
+// ---- self-attention guidance (attention.hip: the column sums; sampler.hip: degrade and combine)
+int pea_op_attention_colsum_groups(int B, int H, int Sq, int Skv) { return attention_colsum_groups(B, H, Sq, Skv); }
+int pea_op_attention_colsum(const void* Q, int ldq, const void* K, int ldk, const float* lse, float* part, int B, int H, int Sq, int Skv,
+                            float scale, int q_prescaled, void* stream) {
+  AttnColsumP p = AttnColsumP();
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.ldq = ldq; p.ldk = ldk; p.lse = lse; p.part = part;
+  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.q_prescaled = q_prescaled; p.nd = 1;
+  return launch_attention_colsum(p, (hipStream_t)stream);
+}
+int pea_op_sag_degrade(const float* latents, const float* eps, const float* part, int G, int map_h, int map_w, const int* iy,
+                       const int* ix, float* out, int B, int C, int H, int W, float c_x, float c_e, float o_b, float o_e, void* stream) {
+  return launch_sag_degrade(latents, eps, part, G, map_h, map_w, iy, ix, out, B, C, H, W, c_x, c_e, o_b, o_e, (hipStream_t)stream);
+}
+int pea_op_cfg_sag_combine(const float* eps, const float* eps_deg, float* out, int B, long long per, int cfg, float guidance_scale,
+                           float sag_scale, void* stream) {
+  return launch_cfg_sag_combine(eps, eps_deg, out, B, per, cfg, guidance_scale, sag_scale, (hipStream_t)stream);
+}
 // ---- LoRA weight composition (lora.hip)
 int pea_op_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank, float scale,
                         void* stream) {

@@ -1397,6 +1397,126 @@ __global__ __launch_bounds__(64 * MAPS_WAVES) void xattn_maps_kernel(const AttnM
   }
 }
 
+// ============================================================================= self-attention column sums
+// Self-attention guidance: part[b][g][key] = (1 / H) sum_{h in group g} sum_q softmax(scale Q_h K_h^T)[q][key], the probability
+// mass a key receives from all queries, at any key count (the maps kernel above needs its keys resident: <= 128).  The score half
+// of the dK / dV role with an in-lane sum: a workgroup = 4 waves = 128 keys of one (sample, head group), a wave owns 32 keys (key
+// on the lane); the Q tiles of the group's heads stream through the 2-deep LDS-DMA ring, four to a stage, with the softmax's row
+// constant lse[q] beside them; S^T leaves the MFMA with a query per register.  PRE (a prescaled Q): the constant -lse log2(e) is the accumulator
+// operand and p = exp2(acc).  Otherwise scale log2(e) multiplies the fp32 score -- no bf16 operand is rounded a second time -- so
+// both forms see the same scores to fp32 rounding.  p stays fp32: no V, no O, no second product.
+// Order of the sum (the same bits every run): a lane adds the 32 queries of a tile that it holds (16 per 32-query block: four
+// chains over j, ((j0 + j1) + (j2 + j3)), block 0 then block 1), adds tile sums in ascending tile order, heads in ascending order;
+// after the last head the two halves of the wave (queries 8 g + 0..3 and 8 g + 4..7) are added, then x 1 / H.
+// Queries at or past Sq of the last tile: their rows read as zeros (buffer bounds) and their p is replaced by 0, not multiplied.
+// Keys at or past Skv of the last block: the lane computes on the last stored row and stores nothing.
+#define COLSUM_NT 4                                            // 64-query tiles per stage of the ring: one for each wave's row constants
+#define COLSUM_STG (COLSUM_NT * (TILE_BYTES + 256))            // a stage: four Q tiles and their 4 x 64 row constants
+// A stage is 256 queries, not 64: a quarter of the barriers, and a step's work stays above the DMA's latency with one wave per
+// SIMD.  At SDXL's mid block it measures the same as one tile per stage (profiles/EXPERIMENTS.md section 9, f13: the stage depth
+// is not what bounds this launch).
+template <bool PRE>
+__global__ __launch_bounds__(256, 2) void attn_colsum_kernel(const AttnColsumP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int kblk, grp, b;
+  attn_block_coords(kblk, grp, b);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int frow = lane & 31, fh = lane >> 5;
+  const int k0 = kblk * 128 + wave * 32;
+  const bool wave_active = k0 < p.Skv;                 // wave-uniform
+  const bool kstored = k0 + frow < p.Skv;
+  const int krow = kstored ? k0 + frow : p.Skv - 1;
+  const int h0 = grp * p.hpg, h1 = min(p.H, h0 + p.hpg);
+  const int nt = (p.Sq + 63) / 64, ns = (nt + COLSUM_NT - 1) / COLSUM_NT, nit = (h1 - h0) * ns;
+  const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq;
+  const bf16* Kr = p.K + ((long long)b * p.Skv + krow) * p.ldk;
+  const float* lseb = p.lse + (long long)b * p.H * p.Sq;
+  const float c = p.scale * LOG2E;
+
+  auto stage = [&](char* dst, int h, int t0) {           // tiles t0 .. t0 + 3 of head h, those that exist
+    const TileSrc q = tile_src(Qb + h * 64, p.ldq, p.Sq, wave, lane);
+#pragma unroll
+    for (int j = 0; j < COLSUM_NT; ++j)
+      if (t0 + j < nt) stage_tile(q, (t0 + j) * 64, dst + j * TILE_BYTES, wave);
+    if (t0 + wave < nt) {                                // wave w brings the row constants of tile t0 + w
+      const int r = min((t0 + wave) * 64 + lane, p.Sq - 1);
+      lds_dma4(lseb + (long long)h * p.Sq + r, dst + COLSUM_NT * TILE_BYTES + wave * 256);
+    }
+  };
+  if (nit > 0) stage(smem, h0, 0);
+  WAIT_VM0();
+  __syncthreads();
+
+  float col = 0.f;
+  bf16x8 kf[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) kf[s] = bf16x8{};
+  int h = h0, st = 0;
+  for (int it = 0; it < nit; ++it) {
+    const int cur = it & 1;
+    int hn = h, sn = st + 1;
+    if (sn == ns) { sn = 0; ++hn; }
+    if (it + 1 < nit) stage(smem + (cur ^ 1) * COLSUM_STG, hn, sn * COLSUM_NT);
+    if (wave_active) {
+      if (st == 0) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) kf[s] = *(const bf16x8*)(Kr + h * 64 + 16 * s + 8 * fh);
+      }
+      for (int j = 0; j < COLSUM_NT; ++j) {
+        const int t = st * COLSUM_NT + j;
+        if (t >= nt) break;                              // uniform
+        const char* Qs = smem + cur * COLSUM_STG + j * TILE_BYTES;
+        const float* rc = (const float*)(smem + cur * COLSUM_STG + COLSUM_NT * TILE_BYTES + j * 256);
+        f32x16 acc[2], nl[2];
+        bf16x8 rq[2][4];
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s) rq[qb][s] = read_row_frag(Qs, qb * 32 + frow, s, fh);
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const f32x4 l4 = *(const f32x4*)(rc + qb * 32 + 8 * g + 4 * fh);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              nl[qb][4 * g + e] = -l4[e] * LOG2E;
+              acc[qb][4 * g + e] = PRE ? nl[qb][4 * g + e] : 0.f;
+            }
+          }
+        }
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+          for (int s = 0; s < 4; ++s) acc[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rq[qb][s], kf[s], acc[qb], 0, 0, 0);
+        const bool ragged = t * 64 + 64 > p.Sq;        // uniform: the last tile of a head only
+        float ts = 0.f;
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+          float sj[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int r = 4 * g + e;
+              float pr = fast_exp2(PRE ? acc[qb][r] : fmaf(acc[qb][r], c, nl[qb][r]));
+              if (ragged) pr = t * 64 + qb * 32 + 8 * g + 4 * fh + e < p.Sq ? pr : 0.f;
+              sj[e] += pr;
+            }
+          ts += (sj[0] + sj[1]) + (sj[2] + sj[3]);
+        }
+        col += ts;
+      }
+    }
+    WAIT_VM0();
+    __syncthreads();
+    h = hn;
+    st = sn;
+  }
+  const float other = __shfl_xor(col, 32);
+  if (wave_active && kstored && fh == 0)
+    p.part[((long long)b * p.G + grp) * p.Skv + k0 + frow] = (col + other) * (1.f / (float)p.H);
+}
+
 // ============================================================================= prompt-to-prompt editing
 // A batch of prompts denoised from the same latents; sample b with s = src[b] >= 0 is "edited": per head
 //   P0 = softmax(scale Q[s] K[s]^T)   the source's probabilities at the same query positions,   P1 = softmax(scale Q[b] K[b]^T)
@@ -3176,6 +3296,74 @@ extern "C" int pea_debug_attn_maps_dispatch(const int* q, int* out) {
   const int rc = attn_plan_maps(p, plan);
   if (rc) return rc;
   out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
+  return PEA_OK;
+}
+
+// ============================================================================= host: self-attention column sums
+// A launcher of its own, like the maps' above; the decision table does not know it.  The grid rule, in this one function: a
+// workgroup is 128 keys of one (sample, head group), grid = ceil(Skv / 128) x G x B.  The heads are cut into the fewest groups that
+// put at least one round of workgroups (wg_slots(2): the kernel takes 66 KiB of LDS, two workgroups a CU) on the
+// chip, never more than H: heads per group = ceil(H / that), G = ceil(H / heads per group), so no group is empty.  SDXL's mid
+// block (B = 2, H = 20, 1024 tokens: 16 key blocks x samples) gets G = 20, one head per group, 320 workgroups; at B = 64 of the
+// same layer the key blocks alone fill the chip and G = 1.  A sum over heads inside a workgroup costs nothing but parallelism;
+// one across workgroups is the consumer's G fp32 adds per key (no atomics, no reduce launch).
+struct AttnColsumPlan { int G, hpg, lds; dim3 grid; };
+static void colsum_groups(int B, int H, int Skv, int& G, int& hpg) {
+  const long long base = (long long)B * cdiv(Skv, 128);
+  long long g = (wg_slots(2) + base - 1) / base;
+  g = g < 1 ? 1 : (g > H ? H : g);
+  hpg = cdiv(H, (int)g);
+  G = cdiv(H, hpg);
+}
+static int attn_plan_colsum(AttnColsumP& p, AttnColsumPlan& plan) {
+  if (p.nd == 0) p.nd = 1;
+  SHAPECHK(p.B > 0 && p.B <= 65535 && p.H > 0 && p.H <= 65535 && p.Sq >= 1 && p.Skv >= 1,
+           "attention_colsum: empty problem (B=%d H=%d Sq=%d Skv=%d; B, H <= 65535)", p.B, p.H, p.Sq, p.Skv);
+  SHAPECHK(p.nd == 1, "attention_colsum: head_dim 64 only (nd=%d)", p.nd);
+  if (int rc = attn_check_operands("attention_colsum", {p.Q, p.K, p.K, p.ldq, p.ldk, p.ldk, nullptr, 0, 0, p.part, p.lse, true}, p.H, p.scale)) return rc;
+  SHAPECHK(p.lse != nullptr, "attention_colsum: null lse (fp32 [B][H][Sq], as pea_op_attention_fwd writes it)");
+  SHAPECHK((long long)p.Sq * p.ldq < (1ll << 30) && (long long)p.Skv * p.ldk < (1ll << 30),
+           "attention_colsum: a sample's Q or K takes 2 GiB or more (Sq=%d ldq=%d Skv=%d ldk=%d)", p.Sq, p.ldq, p.Skv, p.ldk);
+  colsum_groups(p.B, p.H, p.Skv, plan.G, plan.hpg);
+  p.G = plan.G; p.hpg = plan.hpg;
+  plan.lds = 2 * COLSUM_STG;
+  plan.grid = dim3(cdiv(p.Skv, 128), plan.G, p.B);
+  return PEA_OK;
+}
+int attention_colsum_groups(int B, int H, int Sq, int Skv) {
+  SHAPECHK(B > 0 && B <= 65535 && H > 0 && H <= 65535 && Sq >= 1 && Skv >= 1, "attention_colsum_groups: empty problem (B=%d H=%d Sq=%d Skv=%d)", B, H, Sq, Skv);
+  int G, hpg;
+  colsum_groups(B, H, Skv, G, hpg);
+  return G;
+}
+int launch_attention_colsum(const AttnColsumP& p0, hipStream_t s) {
+  AttnColsumP p = p0;
+  AttnColsumPlan plan;
+  const int rc = attn_plan_colsum(p, plan);
+  if (rc) return rc;
+  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = 1; }
+  PROF_BEGIN(2, 2.0 * p.B * p.H * (double)p.Sq * p.Skv * 64,
+             2.0 * p.B * p.H * 64 * ((double)p.Sq * cdiv(p.Skv, 128) + p.Skv) + 4.0 * p.B * ((double)p.H * p.Sq + (double)plan.G * p.Skv), s);
+  const int lrc = p.q_prescaled ? launch_lds<attn_colsum_kernel<true>>(plan.grid, plan.lds, s, p)
+                                : launch_lds<attn_colsum_kernel<false>>(plan.grid, plan.lds, s, p);
+  PROF_END(s);
+  if (lrc) return lrc;
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+extern "C" int pea_debug_attn_colsum_dispatch(const int* q, int* out) {
+  static float page[64];
+  AttnColsumP p = AttnColsumP();
+  p.Q = p.K = (const bf16*)page; p.part = page; p.lse = q[7] & 2 ? nullptr : page; p.scale = 0.125f;
+  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.Skv = q[3]; p.nd = q[4];
+  p.ldq = q[5] > 0 ? q[5] : 64 * p.H;
+  p.ldk = q[6] > 0 ? q[6] : 64 * p.H;
+  p.q_prescaled = q[7] & 1;
+  AttnColsumPlan plan;
+  const int rc = attn_plan_colsum(p, plan);
+  if (rc) return rc;
+  out[0] = plan.G; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.hpg;
   return PEA_OK;
 }
 

@@ -296,6 +296,22 @@ struct Tape {
   StyleState* style = nullptr;
   bool is_self_attn(const Op& o) const { return graph == 0 && o.kind == OP_ATTN && o.b != t_kvall && !o.mask && o.p1 == o.p2; }
   int style_check(bool forward) const;         // what a context must be to share self-attention (tape.hip)
+  // Self-attention guidance (graph 0, inference only; api_model.hip: pea_unet_enable_sag): while this is set, the ordinary launch
+  // of ONE self-attention op (index `op` in `ops`) is handed the state's own lse buffer and is followed by ONE
+  // launch_attention_colsum over samples first .. first + n of its Q, K and lse.  The ordinary launch's decision and its O do not
+  // change (the forward kernels store lse beside O; the plan does not read the pointer).  The tape, the plans, the arenas and the
+  // attention census do not change.  Outside the arenas: release_acts keeps the buffers.
+  struct SagState {
+    int layer = 0, op = -1, first = 0, n = 0, G = 0, S = 0, H = 0;
+    float* lse = nullptr;                      // device fp32 [B][H][S]
+    float* part = nullptr;                     // device fp32 [n][G][S]
+    ~SagState() {
+      if (lse) (void)hipFree(lse);
+      if (part) (void)hipFree(part);
+    }
+  };
+  SagState* sag = nullptr;
+  int sag_check(bool forward) const;           // what a context must be to capture column sums (tape.hip)
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

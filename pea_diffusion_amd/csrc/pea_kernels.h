@@ -211,6 +211,22 @@ struct AttnMapsP {
   int nd;                          // padded head_dim / 64 (0 is read as 1); anything but 1 is refused
 };
 int launch_attention_maps(const AttnMapsP& p, hipStream_t s);
+// Self-attention column sums (self-attention guidance), head_dim 64, any Sq, Skv >= 1: the probability mass each key receives,
+//   part[b][g][k] = (1 / H) sum_{h in group g} sum_q exp(scale q_h . k_h - lse[b][h][q]),  fp32 [B][G][Skv],
+// G = attention_colsum_groups(B, H, Sq, Skv) head groups; the consumer adds the G partials in ascending g (attn_colsum_kernel:
+// keys on the lane, Q tiles streamed; no V, no O, probabilities never rounded to bf16, no atomics).  lse: fp32 [B][H][Sq],
+// natural log, as the forward kernels write it.  Its own launcher and grid rule, like the maps': the decision table does not know it.
+struct AttnColsumP {
+  const bf16 *Q, *K; int ldq, ldk;
+  const float* lse;
+  float* part;
+  int B, H, Sq, Skv;
+  float scale; int q_prescaled;
+  int nd;                          // padded head_dim / 64 (0 is read as 1); anything but 1 is refused
+  int G, hpg;                      // head groups and heads per group: filled in by the launcher
+};
+int attention_colsum_groups(int B, int H, int Sq, int Skv);      // G, or PEA_E_SHAPE for an empty problem
+int launch_attention_colsum(const AttnColsumP& p, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise.hip
 int launch_geglu_fwd(const bf16* hg, bf16* y, long long rows, int inner, hipStream_t s);   // hg [rows][2*inner]
@@ -330,6 +346,11 @@ int launch_lcm_update(float* sample, const float* eps, const float* noise, float
 int launch_euler_update(float* sample, const float* eps, const float* noise, float* model_in, long long n, int dup, float k_e,
                         float k_n, float k_s, hipStream_t s);
 int launch_residual_import(const void* src, int dtype, bf16* dst, int B, int C, long long HW, float scale, hipStream_t s);
+// self-attention guidance: the masked Gaussian degrade of the data prediction, and the guidance combine (include/pea_hip.h)
+int launch_sag_degrade(const float* latents, const float* eps, const float* part, int G, int mh, int mw, const int* iy, const int* ix,
+                       float* out, int B, int C, int H, int W, float c_x, float c_e, float o_b, float o_e, hipStream_t s);
+int launch_cfg_sag_combine(const float* eps, const float* eps_deg, float* out, int B, long long per, int cfg, float g, float sag,
+                           hipStream_t s);
 // lora.hip: out[M][Kf] = acc + scale * up[M][rank] . down[rank][Kf], fp32 (acc may be out)
 int launch_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank,
                         float scale, hipStream_t s);

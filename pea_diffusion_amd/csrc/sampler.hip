@@ -209,6 +209,117 @@ int launch_euler_update(float* sample, const float* eps, const float* noise, flo
   return PEA_OK;
 }
 
+// Self-attention guidance (Hong et al. 2023), steps 2 and 3 of a denoising step in ONE launch: the mask from the column sums of a
+// self-attention layer, the data prediction, its 9 x 9 Gaussian blur, the select, and the degraded model input.
+//   A[b][k] = part[b][0][k] + part[b][1][k] + ...   (ascending g, plain fp32 adds),   m = A[b][iy[y] * mw + ix[x]] > 1.0f
+//   x0 = c_x x + c_e eps;  x0_blur = reflect-padded separable blur of x0 (taps exp(-i^2 / 2) / sum, i = -4..4; rows, then columns)
+//   out = o_b (m ? x0_blur : x0) + o_e eps
+// A workgroup is one 32 x 32 tile of one (sample, channel): x0 over the tile and its 4-pixel halo goes into LDS (reflect indexing
+// of the source pixel: F.pad(mode="reflect"), no edge repeat), the row pass writes 40 x 32 sums, the column pass reads nine of them.
+// Contraction is off in here: where the mask is false the result is the written formula, each product and sum rounded once.
+#define SAG_T 32
+#define SAG_R 4
+struct SagTaps { float w[SAG_R + 1]; };                  // w[|i|], symmetric
+__device__ __forceinline__ int sag_reflect(int i, int n) {
+  i = i < 0 ? -i : i;
+  i = i >= n ? 2 * n - 2 - i : i;
+  return i < 0 ? 0 : (i >= n ? n - 1 : i);               // (only pixels of a ragged tile that are never stored get here out of range)
+}
+__global__ __launch_bounds__(256) void sag_degrade_kernel(const float* __restrict__ lat, const float* __restrict__ eps,
+                                                          const float* __restrict__ part, int G, int mhw, int mw,
+                                                          const int* __restrict__ iy, const int* __restrict__ ix,
+                                                          float* __restrict__ out, int C, int H, int W, int tiles_x, float c_x,
+                                                          float c_e, float o_b, float o_e, SagTaps taps) {
+#pragma clang fp contract(off)
+  constexpr int E = SAG_T + 2 * SAG_R;
+  __shared__ float x0s[E][E + 1];
+  __shared__ float rows[E][SAG_T + 1];
+  const int b = blockIdx.z, ch = blockIdx.y;
+  const int ty0 = (blockIdx.x / tiles_x) * SAG_T, tx0 = (blockIdx.x % tiles_x) * SAG_T;
+  const long long plane = ((long long)b * C + ch) * H * W;
+  for (int i = threadIdx.x; i < E * E; i += 256) {
+    const int ly = i / E, lx = i - ly * E;
+    const long long src = plane + (long long)sag_reflect(ty0 - SAG_R + ly, H) * W + sag_reflect(tx0 - SAG_R + lx, W);
+    const float a = c_x * lat[src], e = c_e * eps[src];
+    x0s[ly][lx] = a + e;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < E * SAG_T; i += 256) {
+    const int ly = i / SAG_T, lx = i - ly * SAG_T;
+    float s = taps.w[SAG_R] * x0s[ly][lx];
+#pragma unroll
+    for (int k = 1; k <= 2 * SAG_R; ++k) {
+      const float v = taps.w[k < SAG_R ? SAG_R - k : k - SAG_R] * x0s[ly][lx + k];
+      s = s + v;
+    }
+    rows[ly][lx] = s;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < SAG_T * SAG_T; i += 256) {
+    const int ly = i / SAG_T, lx = i - ly * SAG_T;
+    const int y = ty0 + ly, x = tx0 + lx;
+    if (y >= H || x >= W) continue;
+    const int my = min(max(iy[y], 0), mhw / mw - 1), mx = min(max(ix[x], 0), mw - 1);   // (a table entry off the map reads its edge)
+    const float* pk = part + (long long)b * G * mhw + my * mw + mx;
+    float A = pk[0];
+    for (int g = 1; g < G; ++g) A = A + pk[(long long)g * mhw];
+    float v = x0s[ly + SAG_R][lx + SAG_R];
+    if (A > 1.0f) {
+      float s = taps.w[SAG_R] * rows[ly][lx];
+#pragma unroll
+      for (int k = 1; k <= 2 * SAG_R; ++k) {
+        const float u = taps.w[k < SAG_R ? SAG_R - k : k - SAG_R] * rows[ly + k][lx];
+        s = s + u;
+      }
+      v = s;
+    }
+    const long long o = plane + (long long)y * W + x;
+    const float a = o_b * v, e = o_e * eps[o];
+    out[o] = a + e;
+  }
+}
+int launch_sag_degrade(const float* latents, const float* eps, const float* part, int G, int mh, int mw, const int* iy, const int* ix,
+                       float* out, int B, int C, int H, int W, float c_x, float c_e, float o_b, float o_e, hipStream_t s) {
+  SHAPECHK(latents && eps && part && iy && ix && out, "sag_degrade: null operand");
+  SHAPECHK(G >= 1, "sag_degrade: G=%d partial column sums (at least 1)", G);
+  SHAPECHK(B > 0 && B <= 65535 && C > 0 && C <= 65535 && mh > 0 && mw > 0, "sag_degrade: B=%d C=%d, a %d x %d map (B, C <= 65535)", B, C, mh, mw);
+  SHAPECHK(H >= SAG_R + 1 && W >= SAG_R + 1, "sag_degrade: a %d x %d latent; reflect padding of %d needs at least %d x %d", H, W, SAG_R, SAG_R + 1, SAG_R + 1);
+  SHAPECHK((long long)mh * mw < (1ll << 30) && (long long)H * W < (1ll << 30), "sag_degrade: map or latent too large");
+  SagTaps taps;
+  double w[SAG_R + 1], sum = 0.0;
+  for (int i = 0; i <= SAG_R; ++i) { w[i] = exp(-0.5 * i * i); sum += (i ? 2.0 : 1.0) * w[i]; }
+  for (int i = 0; i <= SAG_R; ++i) taps.w[i] = (float)(w[i] / sum);
+  const int tx = cdiv(W, SAG_T), ty = cdiv(H, SAG_T);
+  hipLaunchKernelGGL(sag_degrade_kernel, dim3(tx * ty, C, B), dim3(256), 0, s, latents, eps, part, G, mh * mw, mw, iy, ix, out, C, H, W,
+                     tx, c_x, c_e, o_b, o_e, taps);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
+// Self-attention guidance, step 5.  cfg: eps = [uncond (B samples) | text (B samples)], out = u + g (t - u) + s (u - d), the first
+// two terms as cfg_combine_kernel writes them (s = 0: its bits); otherwise eps holds B samples, out = e + s (e - d).
+__global__ void cfg_sag_combine_kernel(const float* __restrict__ eps, const float* __restrict__ deg, float* __restrict__ out,
+                                       long long n, int cfg, float g, float sg) {
+  SM_LOOP(i, n) {
+    const float u = eps[i];
+    float base = u;
+    if (cfg) {
+      const float t = eps[n + i];
+      base = u + g * (t - u);
+    }
+    out[i] = sg != 0.f ? base + sg * (u - deg[i]) : base;
+  }
+}
+int launch_cfg_sag_combine(const float* eps, const float* eps_deg, float* out, int B, long long per, int cfg, float g, float sag,
+                           hipStream_t s) {
+  SHAPECHK(eps && eps_deg && out, "cfg_sag_combine: null operand");
+  SHAPECHK(B > 0 && per > 0, "cfg_sag_combine: B=%d per=%lld", B, per);
+  const long long n = (long long)B * per;
+  hipLaunchKernelGGL(cfg_sag_combine_kernel, dim3(sm_grid(n)), dim3(256), 0, s, eps, eps_deg, out, n, cfg != 0, g, sag);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
 // Inpainting inputs (tests/test_sdxl_zh_inpaint.py: VaeImageProcessor.preprocess of image and mask, the masking of __call__ and
 // the nearest-mode resize of prepare_mask_latents): per pixel of image [N][3][H][W] and mask [N][1][H][W], both in [0, 1],
 //   init = 2 image - 1,  masked = init * (mask < 0.5),  latent_mask[n][0][y/8][x/8] = (mask >= 0.5) at y % 8 == x % 8 == 0.

@@ -272,6 +272,7 @@ Tape::~Tape() {
   delete maps;
   delete edit;
   delete style;
+  delete sag;
 }
 
 int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s) {
@@ -632,6 +633,31 @@ int Tape::style_check(bool forward) const {
   return PEA_OK;
 }
 
+// Self-attention guidance capture: what the context must be.  Checked when the state is set and again (forward) before the first
+// launch of a forward: a prompt edit or a StyleAligned state may have arrived in between.  Both rewrite or replace the chosen
+// launch.  Image prompts, regions, heat maps, FreeU and ControlNet residuals are welcome.
+int Tape::sag_check(bool forward) const {
+  const char* const who = forward ? "pea_unet_forward" : "pea_unet_enable_sag";
+  if (needs_grad) {
+    pea_set_error("%s: self-attention guidance is an inference feature; this context was created with PEA_UNET_GRAD", who);
+    return PEA_E_STATE;
+  }
+  if (edit) {
+    pea_set_error("%s: self-attention guidance cannot be combined with prompt editing, whose self-attention rule rewrites the captured "
+                  "launch (pea_unet_clear_prompt_edit or pea_unet_disable_sag)", who);
+    return PEA_E_STATE;
+  }
+  if (sag && style && style->n_targets) {
+    const auto it = style->layer_of_op.find(sag->op);
+    if (it != style->layer_of_op.end() && style->on[it->second]) {
+      pea_set_error("%s: self-attention layer %d is shared by StyleAligned, which replaces the launch self-attention guidance captures "
+                    "(switch that layer off in pea_unet_set_style_aligned, or pea_unet_disable_sag)", who, sag->layer);
+      return PEA_E_STATE;
+    }
+  }
+  return PEA_OK;
+}
+
 int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype, const void* text, int text_dtype,
                   const float* time_ids, float* eps, hipStream_t s) {
   std::string miss;
@@ -648,6 +674,7 @@ int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype
   }
   if (edit) RC(edit_check(true));
   if (style) RC(style_check(true));
+  if (sag) RC(sag_check(true));
   RC(ensure_acts());
   RC(ensure_folded(s));
   x_in = x; t_in = t; tid_in = time_ids; eps_out = eps;
@@ -896,7 +923,16 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
           RC(launch_attention_fwd_shared(e, s));
           break;
         }
+        const bool sag_here = sag && sag->op == (int)oi;           // self-attention guidance: this launch also stores its lse
+        if (sag_here) p.lse = sag->lse;
         RC(launch_attention_fwd(p, s));
+        if (sag_here) {                                             // ... and its column sums follow (sag_check has passed)
+          AttnColsumP c = AttnColsumP();
+          c.Q = p.Q + (size_t)sag->first * p.Sq * p.ldq; c.ldq = p.ldq; c.K = p.K + (size_t)sag->first * p.Skv * p.ldk; c.ldk = p.ldk;
+          c.lse = sag->lse + (size_t)sag->first * o.p0 * o.p1; c.part = sag->part;
+          c.B = sag->n; c.H = o.p0; c.Sq = o.p1; c.Skv = o.p2; c.scale = o.f0; c.q_prescaled = o.pre; c.nd = o.p3;
+          RC(launch_attention_colsum(c, s));
+        }
         if (edit && graph == 0 && o.b != t_kvall && !o.mask && o.p1 == o.p2 && o.p1 <= edit->self_max_tokens && edit->step < edit->self_until) {
           // prompt editing, self-attention: O[b] = softmax(Q[s] K[s]^T) V[b], one B = 1 launch per edited sample behind the
           // ordinary one (unedited samples keep their bits by construction)

@@ -636,6 +636,73 @@ def cfg_combine(noise_pred2, guidance_scale, guidance_rescale=0.0):
     return out
 
 
+# ---- self-attention guidance (Hong et al. 2023; pea_diffusion_amd/sag.py is the loop)
+def attention_colsum_groups(B, heads, Sq, Skv):
+    """G of `attention_colsum`: how many head groups its launch cuts the heads into (pea_op_attention_colsum_groups)"""
+    g = int(lib().pea_op_attention_colsum_groups(int(B), int(heads), int(Sq), int(Skv)))
+    if g < 1:
+        check(g)
+    return g
+
+
+def attention_colsum(q, k, lse, heads, scale=None, q_prescaled=False, out=None):
+    """Column sums of a softmax in one launch (pea_op_attention_colsum), head_dim 64, no V / O, probabilities fp32 throughout:
+    part[b, g, key] = (1 / H) sum_{h in group g} sum_q exp(scale q_h . k_h - lse[b, h, q]).  q [B,Sq,H*64], k [B,Skv,>=H*64] bf16;
+    lse fp32 [B,H,Sq] (natural log, as `attention_fwd(..., want_lse=True)` returns it).  out: a contiguous fp32 buffer of at least
+    B*G*Skv elements.  -> fp32 [B, G, Skv] with G = attention_colsum_groups(B, heads, Sq, Skv); the column sum of the head-mean
+    softmax is `part.sum(1)` in ascending g (what `sag_degrade` adds itself).  The same bits every run."""
+    B, Sq, C = q.shape
+    Skv = k.shape[1]
+    if C != heads * 64:
+        raise PeaError(f"attention_colsum: head_dim {C // max(heads, 1)} (the kernel is built for 64)")
+    if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != (B, heads, Sq) or not lse.is_contiguous()):
+        raise PeaError(f"attention_colsum: lse {tuple(lse.shape)} {lse.dtype}, expected contiguous fp32 [{B}, {heads}, {Sq}]")
+    scale = float(scale) if scale is not None else 64 ** -0.5
+    G = attention_colsum_groups(B, heads, Sq, Skv)
+    n = B * G * Skv
+    if out is None:
+        out = torch.empty(n, device=q.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n or out.device != q.device:
+        raise PeaError(f"attention_colsum: out {tuple(out.shape)} {out.dtype}, expected contiguous fp32 with at least {n} elements")
+    check(lib().pea_op_attention_colsum(ptr(q), q.stride(1), ptr(k), k.stride(1), ptr(lse), ptr(out), B, heads, Sq, Skv, scale,
+                                        int(q_prescaled), stream_ptr()))
+    return out.view(-1)[:n].view(B, G, Skv)
+
+
+def sag_degrade(latents, eps, part, map_hw, iy, ix, c_x, c_e, o_b, o_e):
+    """Mask, blur and degraded model input of self-attention guidance in one launch (pea_op_sag_degrade).  latents, eps fp32
+    [B,C,H,W]; part fp32 [B,G,h*w] (`attention_colsum` / `HipUNet.sag_colsum`), map_hw = (h, w); iy int32 [H], ix int32 [W]
+    (`sag.nearest_tables`, on the device).  m = (part summed over g in ascending order) > 1 at (iy[y], ix[x]);
+    x0 = c_x x + c_e eps; -> o_b (m ? gaussian9x9_reflect(x0) : x0) + o_e eps, fp32 [B,C,H,W]."""
+    B, C, H, W = latents.shape
+    h, w = int(map_hw[0]), int(map_hw[1])
+    for t in (latents, eps, part):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise PeaError("sag_degrade: latents, eps and part are contiguous fp32 tensors")
+    if eps.shape != latents.shape or part.dim() != 3 or part.shape[0] != B or part.shape[2] != h * w:
+        raise PeaError(f"sag_degrade: eps {tuple(eps.shape)}, part {tuple(part.shape)} for latents {tuple(latents.shape)} and a {h} x {w} map")
+    if iy.dtype != torch.int32 or ix.dtype != torch.int32 or iy.numel() != H or ix.numel() != W:
+        raise PeaError(f"sag_degrade: index tables int32 [{H}] and [{W}]")
+    out = torch.empty_like(latents)
+    check(lib().pea_op_sag_degrade(ptr(latents), ptr(eps), ptr(part), part.shape[1], h, w, ptr(iy.contiguous()), ptr(ix.contiguous()),
+                                   ptr(out), B, C, H, W, float(c_x), float(c_e), float(o_b), float(o_e), stream_ptr()))
+    return out
+
+
+def cfg_sag_combine(noise_pred, noise_pred_deg, guidance_scale, sag_scale, do_cfg=True):
+    """The guidance combine of self-attention guidance (pea_op_cfg_sag_combine).  do_cfg: noise_pred fp32 [2B, ...],
+    unconditional half first -> u + g (t - u) + s (u - d), at s = 0 the bits of `cfg_combine`.  Otherwise noise_pred [B, ...]
+    -> e + s (e - d).  noise_pred_deg (d): fp32 [B, ...], the prediction on the degraded input."""
+    x, d = noise_pred.contiguous(), noise_pred_deg.contiguous()
+    B = d.shape[0]
+    if x.dtype != torch.float32 or d.dtype != torch.float32 or x.shape[0] != (2 * B if do_cfg else B) or x.shape[1:] != d.shape[1:]:
+        raise PeaError(f"cfg_sag_combine: noise_pred {tuple(x.shape)} {x.dtype}, degraded {tuple(d.shape)} {d.dtype}, do_cfg={do_cfg}")
+    out = torch.empty_like(d)
+    check(lib().pea_op_cfg_sag_combine(ptr(x), ptr(d), ptr(out), B, d[0].numel(), int(bool(do_cfg)), float(guidance_scale),
+                                       float(sag_scale), stream_ptr()))
+    return out
+
+
 def dpm_update_(sample, eps, x0_prev, alpha_s, sigma_s, c_s, c_0, c_1):
     """In place: x0 = (sample - sigma_s*eps)/alpha_s; sample <- c_s*sample + c_0*x0 + c_1*x0_prev; x0_prev <- x0."""
     for t in (sample, eps, x0_prev):

@@ -523,6 +523,41 @@ class HipUNet(HipTape):
         """back to plain self-attention; a forward then gives the bits it gave before"""
         check(lib().pea_unet_clear_style_aligned(self._h))
 
+    def enable_sag(self, layer=None, samples=None):
+        """Self-attention guidance capture (Hong et al. 2023; `sag.denoise_sag` is the loop): while enabled, one self-attention
+        layer's launch also stores its lse and is followed by one column-sum launch, `sag_colsum()`.  layer: an index or a name
+        of `style_aligned.layer_names(self)`; None = the mid block's first transformer block (a UNet without mid-block attention
+        needs an index).  samples: (first, count) of the batch to capture; None = all (under CFG `(0, B // 2)` is the
+        unconditional half).  A forward's output does not change.  Holds until `disable_sag()`."""
+        from . import style_aligned as sa
+        names = sa.layer_names(self)
+        if layer is None:
+            mid = [i for i, n in enumerate(names) if n.startswith("mid_block.")]
+            if not mid:
+                raise PeaError("enable_sag: this UNet has no mid-block attention; name a self-attention layer by index "
+                               f"(0..{len(names) - 1}, style_aligned.layer_names)")
+            layer = mid[0]
+        elif isinstance(layer, str):
+            if layer not in names:
+                raise PeaError(f"enable_sag: '{layer}' names no self-attention layer of this UNet")
+            layer = names.index(layer)
+        first, count = (0, self.B) if samples is None else (int(samples[0]), int(samples[1]))
+        check(lib().pea_unet_enable_sag(self._h, int(layer), first, count))
+        self._sag = (int(layer), first, count)
+
+    def disable_sag(self):
+        """stop capturing and free the buffers; a forward then gives the bits it gave before"""
+        check(lib().pea_unet_disable_sag(self._h))
+        self._sag = None
+
+    def sag_colsum(self):
+        """-> fp32 [n_samples, G, S]: the partial column sums of the captured layer's last forward (`part.sum(1)` in ascending g
+        is the mass every key received); a copy made on the current stream"""
+        p, G, S = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        check(lib().pea_unet_sag_colsum(self._h, ctypes.byref(p), ctypes.byref(G), ctypes.byref(S)))
+        n = self._sag[2]
+        return torch.as_tensor(_DeviceF32(p.value, (n, G.value, S.value)), device=self.device).clone()
+
     def clear_ip_tokens(self, index=None):
         """back to plain cross-attention launches (index: for that adapter alone); the adapters' weights stay loaded"""
         if index is None:
