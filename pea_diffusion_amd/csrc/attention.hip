@@ -32,7 +32,10 @@
 // make the per-channel coefficients it reads.  Their launchers, too, stand beside the decision table.
 // The four forward kernels with resident keys (xattn_fwd / _regions_fwd / _maps / _edit_fwd) are sequences of one set of building
 // blocks that stands above xattn_fwd_kernel (Q stager, scores, key mask, one-shot softmax, value product, O image): one copy of
-// the arithmetic whose bits the tests compare between them.
+// the arithmetic whose bits the tests compare between them.  The kernels that stream keys through the ring with the query on the
+// lane (attn_q_body as forward and as dQ role, attn_shared_body) are sequences of a second set that stands above attn_q_body (ring
+// offsets, row-fragment product, tail mask, online-softmax step, P pack, transposed-fragment product, forward exit); the two with
+// the key on the lane (attn_dkv_body, attn_colsum_kernel) share their preamble and row-constant DMA.
 // The three backward cross-attention kernels take their per-workgroup context (unit range, operand rows of the head, key
 // count, score factor) from xattn_ctx.  They still repeat, as text: K / V staging, the unit stage (stage_unit / fetch_o /
 // unit_head), the key-on-the-lane task, the query-on-the-lane key-block step, and the dQ and dK / dV exits -- so a fix to
@@ -274,15 +277,160 @@ __device__ __forceinline__ void store_o_image_swz(char* ost, int lane, Val val, 
 // query blocks of one head -- which all stream that head's K and V (or Q and dO) -- would land on 8 different L2s and
 // every XCD would see every head: a working set of all heads per 4-MB L2.  Remapped, XCD x runs a contiguous range of
 // (batch, head, block) triples, i.e. whole heads, and a head's operands are read into one L2 once.
+// xcd_contiguous: the rule on a range of `total` workgroups -- dispatch position -> position in an order where each XCD runs one
+// contiguous stretch (positions are dealt to the 8 XCDs round-robin).
+__device__ __forceinline__ unsigned xcd_contiguous(unsigned lin, unsigned total) {
+  const unsigned q = total >> 3, r = total & 7, xcd = lin & 7, j = lin >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
 __device__ __forceinline__ void attn_block_coords(int& bx, int& by, int& bz) {
   const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z;
-  unsigned lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  const unsigned total = gx * gy * gz, q = total >> 3, r = total & 7, xcd = lin & 7, j = lin >> 3;
-  lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+  const unsigned lin = xcd_contiguous(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gz);
   bx = (int)(lin % gx);
   const unsigned t = lin / gx;
   by = (int)(t % gy);
   bz = (int)(t / gy);
+}
+
+// ----------------------------------------------------------------------------- streamed-key building blocks, query on the lane
+// What attn_q_body (forward and dQ role) and attn_shared_body are made of: a wave's 32 queries (query lane & 31 on the lane, both
+// half-waves) against the 64-row tile in the current stage of the LDS-DMA ring.  One copy of the arithmetic, so that the bit-equality
+// the tests assert between these kernels holds by construction.  In an accumulator of the first product slot r of half-wave fh of
+// block kb is tile row kb * 32 + (r & 3) + 8 (r >> 2) + 4 fh.
+// The fragment offsets of one stage: row fragments from ring byte sb on (the stage), transposed fragments from ring byte tb on (the
+// first sub-tile that the second product reads).
+__device__ __forceinline__ AttnFragOff attn_ring_off(const AttnFragOff& fo, int sb, int tb) {
+  AttnFragOff o;
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) o.rf[s4] = fo.rf[s4] + sb;
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int hl = 0; hl < 2; ++hl) o.tr[db][hl] = fo.tr[db][hl] + tb;
+  return o;
+}
+// First product: acc^T[row][q] = c0 + T . B^T, summed over the ND 64 x 64 sub-tiles that begin `sub` bytes into the stage, bf[nd]
+// the resident B fragments of sub-tile nd (S^T = K . Q^T; dP^T = V . dO^T).  All row fragments of a sub-tile are requested before
+// its first MFMA: read-wait-MFMA per fragment (what the compiler emits for the fused loop under a 128-register budget) exposes one
+// LDS latency per MFMA, i.e. the matrix pipe runs at a quarter of its rate in this phase.
+template <int ND>
+__device__ __forceinline__ void attn_rows_product(const char* smem, const AttnFragOff& ro, int sub, const bf16x8 (*bf)[4], const f32x16& c0,
+                                                  f32x16 (&acc)[2]) {
+#pragma unroll
+  for (int nd = 0; nd < ND; ++nd) {
+    bf16x8 fr[2][4];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) fr[kb][s] = *(const bf16x8*)(smem + ro.rf[s] + (sub + nd * TILE_BYTES + kb * 4096));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+        acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[kb][s], bf[nd][s], (nd == 0 && s == 0) ? c0 : acc[kb], 0, 0, 0);
+  }
+}
+// keys at or past kmax of the tile that begins at key kv0 score -inf (P = exp2(-inf) = 0); the caller asks only for a tile that holds one
+__device__ __forceinline__ void attn_mask_tail(f32x16 (&sacc)[2], int kv0, int kmax, int fh) {
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = kv0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+      sacc[kb][r] = key < kmax ? sacc[kb][r] : -INFINITY;
+    }
+}
+// One tile's step of the online softmax in the log2 domain.  sacc holds (scaled score - m_run): the offset came in through the MFMA's
+// C operand, so p = exp2(sacc) as it stands.  Only when some query's tile maximum exceeds its offset by more than ATTN_MOVE_THR
+// (always in the first tile) does the wave take the rescale branch (exact for any threshold).  The ORDER is the contract between the
+// kernels:
+//   the maximum starts at max(sacc[0][0], sacc[1][0]) and takes max(max(mx, sacc[0][r]), sacc[1][r]) for r = 1 .. 15 (one v_max3 per
+//   pair of scores); the half-wave combine (xhalf_max) comes last;
+//   moved = (first || mx > ATTN_MOVE_THR), FINITE: and mx > -inf.  If any lane moved: mrel = moved ? mx : 0; sacc -= mrel;
+//   alpha = first ? 0 : exp2(-mrel) (O and l are still zero before the first valid key); l_run *= alpha; every oacc *= alpha;
+//   m_run += mrel; rowc = rowc_of(m_run) in all 16 slots -- the kernel's C operand of the next score product;
+//   e = exp2(sacc) in place; their sum starts at 0 and adds in (kb, r) order; l_run += that sum.
+// first: this lane's query has not seen a valid key yet.  FINITE (the text instance, where whole tiles can be masked): a tile whose
+// maximum is -inf moves nothing -- with m_run = -inf the next tile's scores would be absorbed by the C operand.  Returns mx.
+template <bool FINITE, int NACC, class RowC>
+__device__ __forceinline__ float attn_online_softmax(f32x16 (&sacc)[2], bool first, float& m_run, float& l_run, f32x16 (&oacc)[NACC],
+                                                     f32x16& rowc, RowC rowc_of) {
+  float mx = fmaxf(sacc[0][0], sacc[1][0]);
+#pragma unroll
+  for (int r = 1; r < 16; ++r) mx = fmaxf(fmaxf(mx, sacc[0][r]), sacc[1][r]);
+  mx = xhalf_max(mx);
+  const bool moved = (first || mx > ATTN_MOVE_THR) && (!FINITE || mx > -INFINITY);
+  if (__any(moved)) {
+    const float mrel = moved ? mx : 0.f;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sacc[kb][r] -= mrel;
+    const float alpha = first ? 0.f : fast_exp2(-mrel);
+    l_run *= alpha;
+#pragma unroll
+    for (int i = 0; i < NACC; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
+    m_run += mrel;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rowc[r] = rowc_of(m_run);
+  }
+  float ls = 0.f;
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float e = fast_exp2(sacc[kb][r]);
+      sacc[kb][r] = e;
+      ls += e;
+    }
+  l_run += ls;
+  return mx;
+}
+// P^T (forward) or dS^T (dQ role) rounded to bf16, as the B-operand fragments of the second product (k-permuted)
+__device__ __forceinline__ void attn_pack_p(const f32x16 (&sacc)[2], bf16x8 (&pf)[4]) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pf[ks][j] = (bf16)sacc[ks >> 1][8 * (ks & 1) + j];
+}
+// Second product: acc^T[d][q] += T^T[d][row] P^T[row][q] for one 64 x 64 sub-tile, `sub` bytes past the stage's transposed-fragment
+// base (O^T += V^T P^T; dQ^T += K^T dS^T).  All eight transposed fragments first (the score registers are free by now), then the
+// MFMAs.  The gathering instances (USE_TR = false) read the same fragments element by element from the tile at Ts.
+template <bool USE_TR>
+__device__ __forceinline__ void attn_cols_product(const char* smem, const AttnFragOff& ro, int sub, const char* Ts, int lane,
+                                                  const bf16x8 (&pf)[4], f32x16* acc) {
+  bf16x8 tfr[4][2];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+    for (int db = 0; db < 2; ++db) {
+      if constexpr (USE_TR)
+        tfr[ks][db] = read_transposed_frag_at(smem + ro.tr[db][0] + (sub + ks * 2048), smem + ro.tr[db][1] + (sub + ks * 2048));
+      else tfr[ks][db] = read_transposed_frag<false>(Ts, ks * 16, db * 32, lane);
+    }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+    for (int db = 0; db < 2; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfr[ks][db], pf[ks], acc[db], 0, 0, 0);
+}
+// Forward exit: l over both half-waves (without an LDS round trip), the row's lse where the caller wants it (lse non-null, and
+// lse_lane on the one lane that writes), and the NO chunks of O = oacc / l through the wave's LDS image `ost` as whole 128-byte rows.
+// oacc[2 * no + db][4g + j] = O^T[d = no * 64 + db * 32 + 8g + 4 fh + j][q = lane & 31]
+template <int NO>
+__device__ __forceinline__ void attn_fwd_exit(const f32x16 (&oacc)[2 * NO], float m_run, float l_run, float* lse, long long lse_i,
+                                              bool lse_lane, char* ost, int lane, bf16* Ob, int ldo, int q0, int Sq) {
+  float la = l_run, lb = l_run;
+  swap_halves32(la, lb);
+  const float l_tot = la + lb;
+  const float inv = 1.f / l_tot;
+  if (lse && lse_lane) lse[lse_i] = (m_run + log2f(l_tot)) * 0.6931471805599453f;
+#pragma unroll
+  for (int no = 0; no < NO; ++no)
+    store_o_image_144(ost, lane, [&](int db, int i) { return oacc[2 * no + db][i] * inv; }, Ob + no * 64, ldo, q0, Sq);
 }
 
 // ============================================================================= forward / dQ
@@ -409,39 +557,14 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
     if (t + 1 < nt) stage_kv(smem + (cur ^ 1) * STG, (t + 1) * 64);
     const char* Ks = smem + cur * STG;
     const char* Vs = Ks + ND * TILE_BYTES;
-    int rfc[4], trc[2][2];
-    {
-      const int sb = cur * STG;
-      const int tb = sb + (MODE == 0 ? ND * TILE_BYTES : chunk * TILE_BYTES);   // fwd: V sub-tiles; dQ: this chunk's K sub-tile
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) rfc[s4] = fo.rf[s4] + sb;
-#pragma unroll
-      for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int hl = 0; hl < 2; ++hl) trc[db][hl] = fo.tr[db][hl] + tb;
-    }
+    const int sb = cur * STG;                  // transposed fragments -- fwd: the V sub-tiles; dQ: this chunk's K sub-tile
+    const AttnFragOff ro = attn_ring_off(fo, sb, sb + (MODE == 0 ? ND * TILE_BYTES : chunk * TILE_BYTES));
 
-    // S^T[key][q] = K . Q^T  (sum over the ND sub-tiles of the head dimension).  All K fragments of a sub-tile are requested
-    // before the first MFMA: read-wait-MFMA per fragment (what the compiler emits for the fused loop under a 128-register
-    // budget) exposes one LDS latency per MFMA, i.e. the matrix pipe runs at a quarter of its rate in this phase.
+    // S^T[key][q] = K . Q^T  (sum over the ND sub-tiles of the head dimension)
     f32x16 sacc[2];
-#pragma unroll
-    for (int nd = 0; nd < ND; ++nd) {
-      bf16x8 kfr[2][4];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) kfr[kb][s] = *(const bf16x8*)(smem + rfc[s] + (nd * TILE_BYTES + kb * 4096));
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-          sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][s], qf[nd][s], (nd == 0 && s == 0) ? rowc : sacc[kb], 0, 0, 0);
-    }
+    attn_rows_product<ND>(smem, ro, 0, qf, rowc, sacc);
     const int kv0 = t * 64;
-    bf16x8 pf[4];   // P^T (fwd) or dS^T (dQ) as B-operand fragments, k-permuted
-    if (MODE == 0) {
+    if constexpr (MODE == 0) {
       // keys beyond Skv are masked only in the tile that contains them.
       // TXT (text encoders, inference): causal mask and / or a per-sample key count (padding) -- a separate instance
       // so the UNet's kernel keeps its register budget
@@ -470,82 +593,22 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
       if (boundary) {
         int kmax = skv_b;
         if constexpr (TXT) kmax = p.causal ? min(skv_b, qrow + 1) : skv_b;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = kv0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-            sacc[kb][r] = key < kmax ? sacc[kb][r] : -INFINITY;
-          }
+        attn_mask_tail(sacc, kv0, kmax, fh);
       }
-      // online softmax in the log2 domain.  sacc holds (scaled score - m_run): the offset came in through the MFMA's C
-      // operand, so p = exp2(sacc) as it stands.  Only when some query's tile maximum exceeds its offset by more than
-      // ATTN_MOVE_THR (always in the first tile) does the wave take the rescale branch (exact for any threshold).
-      float mx = fmaxf(sacc[0][0], sacc[1][0]);
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx = fmaxf(fmaxf(mx, sacc[0][r]), sacc[1][r]);     // one v_max3 per pair of scores
-      mx = xhalf_max(mx);
       // "first" = this query has not seen a valid key yet.  The UNet instance always has one in tile 0 (Skv >= 1, checked on the
       // host).  TXT: a per-sample key count of 0 (or a padded context shorter than a tile boundary) leaves whole tiles at -inf;
-      // the offset then stays 0 -- with m_run = -1e30 the next tile's scores would be absorbed by the C operand and every key
+      // the offset then stays 0 -- with m_run = -inf the next tile's scores would be absorbed by the C operand and every key
       // would come out with weight 1 -- and is set by the first tile with a finite maximum (a row without any key ends as 0 / 0).
-      bool first = t == 0;
-      if constexpr (TXT) first = !seen;
-      const bool moved = (first || mx > ATTN_MOVE_THR) && (!TXT || mx > -INFINITY);
+      const float mx = attn_online_softmax<TXT>(sacc, TXT ? !seen : t == 0, m_run, l_run, oacc, rowc,
+                                                [&](float m) { return TXT ? -m * inv_qs : -m; });
       if constexpr (TXT) seen = seen || mx > -INFINITY;
-      if (__any(moved)) {
-        const float mrel = moved ? mx : 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc[kb][r] -= mrel;
-        const float alpha = first ? 0.f : fast_exp2(-mrel);      // O and l are still zero before the first valid key
-        l_run *= alpha;
-#pragma unroll
-        for (int i = 0; i < 2 * NO; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
-        m_run += mrel;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rowc[r] = TXT ? -m_run * inv_qs : -m_run;
-      }
-      float ls = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = fast_exp2(sacc[kb][r]);
-          sacc[kb][r] = e;
-          ls += e;
-        }
-      l_run += ls;
     } else {
       // P^T = exp2(S^T) (scale in Q, -lse2[q] in the C operand);  dP^T = V . dO^T;  dS^T = P^T (dP^T - delta[q]) scale
       const int skv_b = skv_all;                                 // per-sample valid keys (padded contexts)
       f32x16 dpacc[2];
-#pragma unroll
-      for (int nd = 0; nd < ND; ++nd) {
-        bf16x8 vfr[2][4];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int s = 0; s < 4; ++s) vfr[kb][s] = *(const bf16x8*)(smem + rfc[s] + ((ND + nd) * TILE_BYTES + kb * 4096));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-            dpacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[kb][s], dof[MODE == 1 ? nd : 0][s],
-                                                                (nd == 0 && s == 0) ? negd : dpacc[kb], 0, 0, 0);
-      }
+      attn_rows_product<ND>(smem, ro, ND * TILE_BYTES, dof, negd, dpacc);
       if (kv0 + 64 > skv_b) {                                    // uniform: only the tile that holds masked keys
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = kv0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-            sacc[kb][r] = key < skv_b ? sacc[kb][r] : -INFINITY;   // P = exp2(-inf) = 0
-          }
+        attn_mask_tail(sacc, kv0, skv_b, fh);
         __builtin_amdgcn_sched_barrier(0);                         // (keeps the compiler from if-converting the block into 64 selects per tile)
       }
 #pragma unroll
@@ -556,55 +619,24 @@ __device__ __forceinline__ void attn_q_body(const AttnP& p, char* smem, int blk_
           sacc[kb][r] = pr * dpacc[kb][r];                         // = P (dP - delta); x scale in the epilogue
         }
     }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pf[ks][j] = (bf16)sacc[ks >> 1][8 * (ks & 1) + j];
-
+    bf16x8 pf[4];   // P^T (fwd) or dS^T (dQ) as B-operand fragments, k-permuted
+    attn_pack_p(sacc, pf);
     // fwd: O^T[d][q] += V^T[d][key] P^T[key][q]  (all chunks);   dQ: dQ^T[d][q] += K^T[d][key] dS^T[key][q]  (one chunk)
 #pragma unroll
-    for (int no = 0; no < NO; ++no) {
-      const char* Ts = MODE == 0 ? Vs + no * TILE_BYTES : Ks + chunk * TILE_BYTES;
-      bf16x8 tfr[4][2];                        // all eight transposed fragments first (the score registers are free by now)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-          if constexpr (USE_TR)
-            tfr[ks][db] = read_transposed_frag_at(smem + trc[db][0] + (no * TILE_BYTES + ks * 2048),
-                                                  smem + trc[db][1] + (no * TILE_BYTES + ks * 2048));
-          else tfr[ks][db] = read_transposed_frag<false>(Ts, ks * 16, db * 32, lane);
-        }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-          oacc[2 * no + db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfr[ks][db], pf[ks], oacc[2 * no + db], 0, 0, 0);
-    }
+    for (int no = 0; no < NO; ++no)
+      attn_cols_product<USE_TR>(smem, ro, no * TILE_BYTES, MODE == 0 ? Vs + no * TILE_BYTES : Ks + chunk * TILE_BYTES, lane, pf, oacc + 2 * no);
     WAIT_VM0();
     __syncthreads();
   }
 
-  // epilogue: oacc[2*no+db][4g+j] = X^T[d = no*64 + db*32 + 8g + 4h + j][q = lane&31]
-  float inv = MODE == 1 ? p.scale : 1.f;
-  if (MODE == 0) {
-    float la = l_run, lb = l_run;
-    swap_halves32(la, lb);                                     // (l_run + its partner half, without an LDS round trip)
-    const float l_tot = la + lb;
-    inv = 1.f / l_tot;
-    if (p.lse && qvalid && fh == 0)
-      p.lse[((long long)b * p.H + head) * p.Sq + qrow] = (m_run + log2f(l_tot)) * 0.6931471805599453f;
-  }
   // the wave's image: its own 4.5 KiB of the K / V ring, which every wave has left behind the loop's last barrier
-  const bool accum = MODE == 1 && p.accum_dq;
   char* const ost = smem + wave * (32 * 144);
-#pragma unroll
-  for (int no = 0; no < NO; ++no) {
-    bf16* Ob = MODE == 0 ? p.O + (long long)b * p.Sq * p.ldo + head * 64 * ND + no * 64
-                         : p.dQ + (long long)b * p.Sq * p.lddq + head * 64 * ND + chunk * 64;
-    store_o_image_144(ost, lane, [&](int db, int i) { return oacc[2 * no + db][i] * inv; }, Ob, MODE == 0 ? p.ldo : p.lddq, q0, p.Sq, accum);
-  }
+  if constexpr (MODE == 0)
+    attn_fwd_exit<NO>(oacc, m_run, l_run, p.lse, ((long long)b * p.H + head) * p.Sq + qrow, qvalid && fh == 0, ost, lane,
+                      p.O + (long long)b * p.Sq * p.ldo + head * 64 * ND, p.ldo, q0, p.Sq);
+  else   // the softmax scale is applied once, to the finished dQ^T
+    store_o_image_144(ost, lane, [&](int db, int i) { return oacc[db][i] * p.scale; }, p.dQ + (long long)b * p.Sq * p.lddq + head * 64 * ND + chunk * 64,
+                      p.lddq, q0, p.Sq, p.accum_dq != 0);
 }
 
 template <int MODE, bool USE_TR, int ND, bool TXT = false>
@@ -615,14 +647,28 @@ __global__ __launch_bounds__(256, (ND == 1 ? (MODE == 0 ? 3 : 2) : 1)) void attn
   attn_q_body<MODE, USE_TR, ND, TXT, true>(p, smem, blk_x, head, b);
 }
 
-// per-row constants of a 64-query tile (lse, delta) -> LDS, 4 bytes per lane, issued by wave 0 only
-__device__ __forceinline__ void stage_rowconst(const float* lse, const float* dlt, int r0, int rmax, char* dst,
-                                               int wave, int lane) {
-  if (wave != 0) return;
+// ----------------------------------------------------------------------------- streamed-query building blocks, key on the lane
+// What attn_dkv_body and attn_colsum_kernel share: a workgroup = 4 waves = 128 keys, a wave owns 32 (key lane & 31 on the lane, both
+// half-waves); 64-query tiles stream through the ring with their per-row constants beside them.  (The resident key fragments and
+// the row fragments + C operand of a 32-query block stay each kernel's own text: as blocks they moved attn_dkv_body's register
+// counts -- profiles/EXPERIMENTS.md, "Streamed-key attention: one tile loop".)
+// A lane's key: k0 the wave's first; kstored: the lane's row exists in K / V -- a lane past the end computes on the last stored
+// row (krow) and stores nothing; wave_active: the wave holds any key at all (wave-uniform).
+struct AttnKeyLane { int k0, krow; bool kstored, wave_active; };
+__device__ __forceinline__ AttnKeyLane attn_key_lane(int kblk, int wave, int frow, int Skv) {
+  AttnKeyLane k;
+  k.k0 = kblk * 128 + wave * 32;
+  k.kstored = k.k0 + frow < Skv;
+  k.krow = k.kstored ? k.k0 + frow : Skv - 1;
+  k.wave_active = k.k0 < Skv;
+  return k;
+}
+// the 64 per-row constants of the query tile at row r0 (src[r0 .. r0 + 63]; rows at or past rmax repeat row rmax - 1) -> dst[0..255]
+// by LDS-DMA, 4 bytes per lane of the calling wave
+__device__ __forceinline__ void stage_rowconst(const float* src, int r0, int rmax, char* dst, int lane) {
   int r = r0 + lane;
   r = r < rmax ? r : rmax - 1;
-  lds_dma4(lse + r, dst);
-  lds_dma4(dlt + r, dst + 256);
+  lds_dma4(src + r, dst);
 }
 
 // ============================================================================= dK / dV
@@ -640,8 +686,8 @@ __device__ __forceinline__ void attn_dkv_body(const AttnP& p, char* smem, int bl
   const int chunk = blk_x % ND;
   const int bx = blk_x / ND;
   const int kblk = bx / nsplit, split = bx - kblk * nsplit;
-  const int k0 = kblk * 128 + wave * 32;
   const int frow = lane & 31, fh = lane >> 5;
+  const auto [k0, krow, kstored, wave_active] = attn_key_lane(kblk, wave, frow, p.Skv);
   const float c = p.scale * LOG2E;
 
   const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq + head * 64 * ND;
@@ -652,12 +698,8 @@ __device__ __forceinline__ void attn_dkv_body(const AttnP& p, char* smem, int bl
   const float* dltb = p.delta + ((long long)b * p.H + head) * p.Sq;
   const float* lseb = dltb + (long long)p.B * p.H * p.Sq;
 
-  int krow = k0 + frow;
-  const bool kstored = krow < p.Skv;          // the row exists in K / V / dK / dV
   const int skv_b = p.kv_len ? p.kv_len[b] : p.Skv;   // keys >= skv_b are padding: P = 0, so their dK = dV = 0
-  const bool kvalid = krow < skv_b;
-  krow = kstored ? krow : p.Skv - 1;
-  const bool wave_active = k0 < p.Skv;       // wave-uniform
+  const bool kvalid = k0 + frow < skv_b;
   bf16x8 kf[ND][4], vf[ND][4];
 #pragma unroll
   for (int nd = 0; nd < ND; ++nd)
@@ -687,7 +729,10 @@ __device__ __forceinline__ void attn_dkv_body(const AttnP& p, char* smem, int bl
       stage_tile(qsrc[nd], r0, dst + nd * TILE_BYTES, wave);
       stage_tile(dosrc[nd], r0, dst + (ND + nd) * TILE_BYTES, wave);
     }
-    stage_rowconst(lseb, dltb, r0, p.Sq, dst + 2 * ND * TILE_BYTES, wave, lane);
+    if (wave == 0) {                                     // the tile's row constants: lse, then delta
+      stage_rowconst(lseb, r0, p.Sq, dst + 2 * ND * TILE_BYTES, lane);
+      stage_rowconst(dltb, r0, p.Sq, dst + 2 * ND * TILE_BYTES + 256, lane);
+    }
   };
   const int nt_all = (p.Sq + 63) / 64;
   const int tps = (nt_all + nsplit - 1) / nsplit;            // query tiles per split
@@ -882,8 +927,7 @@ __global__ __launch_bounds__(256, (ND == 1 ? 2 : 1)) void attn_dkv_kernel(const 
 template <bool USE_TR, int ND>
 __global__ __launch_bounds__(256, (ND == 1 ? 2 : 1)) void attn_bwd_fused_kernel(const AttnP p, int n_dq, int n_dkv) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const unsigned total = gridDim.x, q = total >> 3, r = total & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const unsigned lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+  const unsigned lin = xcd_contiguous(blockIdx.x, gridDim.x);
   const int per_head = n_dq + n_dkv;
   const int bh = (int)(lin / per_head), rem = (int)(lin - (unsigned)bh * per_head);
   const int b = bh / p.H, head = bh - b * p.H;
@@ -1423,10 +1467,7 @@ __global__ __launch_bounds__(256, 2) void attn_colsum_kernel(const AttnColsumP p
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 31, fh = lane >> 5;
-  const int k0 = kblk * 128 + wave * 32;
-  const bool wave_active = k0 < p.Skv;                 // wave-uniform
-  const bool kstored = k0 + frow < p.Skv;
-  const int krow = kstored ? k0 + frow : p.Skv - 1;
+  const auto [k0, krow, kstored, wave_active] = attn_key_lane(kblk, wave, frow, p.Skv);
   const int h0 = grp * p.hpg, h1 = min(p.H, h0 + p.hpg);
   const int nt = (p.Sq + 63) / 64, ns = (nt + COLSUM_NT - 1) / COLSUM_NT, nit = (h1 - h0) * ns;
   const bf16* Qb = p.Q + (long long)b * p.Sq * p.ldq;
@@ -1439,10 +1480,8 @@ __global__ __launch_bounds__(256, 2) void attn_colsum_kernel(const AttnColsumP p
 #pragma unroll
     for (int j = 0; j < COLSUM_NT; ++j)
       if (t0 + j < nt) stage_tile(q, (t0 + j) * 64, dst + j * TILE_BYTES, wave);
-    if (t0 + wave < nt) {                                // wave w brings the row constants of tile t0 + w
-      const int r = min((t0 + wave) * 64 + lane, p.Sq - 1);
-      lds_dma4(lseb + (long long)h * p.Sq + r, dst + COLSUM_NT * TILE_BYTES + wave * 256);
-    }
+    // wave w brings the row constants of tile t0 + w
+    if (t0 + wave < nt) stage_rowconst(lseb + (long long)h * p.Sq, (t0 + wave) * 64, p.Sq, dst + COLSUM_NT * TILE_BYTES + wave * 256, lane);
   };
   if (nit > 0) stage(smem, h0, 0);
   WAIT_VM0();
@@ -3619,10 +3658,10 @@ int launch_attn_adain_coef(const bf16* Q, int ldq, const bf16* K, int ldk, int B
   return PEA_OK;
 }
 
-// ---- the forward.  A target's workgroup is attn_q_body's forward loop (same tiles, same fragment addresses, same online softmax)
-// run over 2 ceil(S / 64) key tiles: first the sample's own, then the reference's.  `segc` is the segment's score constant in the
-// log2 domain (q' . s_k, then share_shift log2 e): rowc = segc - m_run, rebuilt where the loop changes segment and in the rescale
-// branch.  Each segment's last tile is masked at S.
+// ---- the forward.  A target's workgroup is attn_q_body's forward loop -- the same calls into the streamed-key building blocks --
+// run over 2 ceil(S / 64) key tiles: first the sample's own, then the reference's.  Its own: the two resident Q fragment sets, the
+// two-segment tile source, and `segc`, the segment's score constant in the log2 domain (q' . s_k, then share_shift log2 e):
+// rowc = segc - m_run, rebuilt where the loop changes segment and in the rescale branch.  Each segment's last tile is masked at S.
 __device__ __forceinline__ void attn_shared_body(const AttnSharedP& p, char* smem, int blk_x, int head, int b, int r) {
   constexpr int STG = 2 * TILE_BYTES;                            // smem: [2 stages][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -3704,119 +3743,25 @@ __device__ __forceinline__ void attn_shared_body(const AttnSharedP& p, char* sme
 #pragma unroll
       for (int i = 0; i < 16; ++i) rowc[i] = segc - m_run;
     }
-    int rfc[4], trc[2][2];
-    {
-      const int sb = cur * STG, tb = sb + TILE_BYTES;
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) rfc[s4] = fo.rf[s4] + sb;
-#pragma unroll
-      for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int hl = 0; hl < 2; ++hl) trc[db][hl] = fo.tr[db][hl] + tb;
-    }
+    const AttnFragOff ro = attn_ring_off(fo, cur * STG, cur * STG + TILE_BYTES);
     f32x16 sacc[2];
-    {
-      bf16x8 kfr[2][4];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) kfr[kb][s] = *(const bf16x8*)(smem + rfc[s] + kb * 4096);
-      __builtin_amdgcn_sched_barrier(0);
-      if (own) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-            sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][s], qo[s], s == 0 ? rowc : sacc[kb], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-            sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kb][s], qr[s], s == 0 ? rowc : sacc[kb], 0, 0, 0);
-      }
-    }
+    if (own) attn_rows_product<1>(smem, ro, 0, &qo, rowc, sacc);
+    else attn_rows_product<1>(smem, ro, 0, &qr, rowc, sacc);
     const int kv0 = (own ? t : t - nt) * 64;                     // key index inside the segment
-    if (kv0 + 64 > S) {                                          // the segment's last tile, where it is ragged
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int key = kv0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * fh;
-          sacc[kb][i] = key < S ? sacc[kb][i] : -INFINITY;
-        }
-    }
-    float mx = fmaxf(sacc[0][0], sacc[1][0]);
-#pragma unroll
-    for (int i = 1; i < 16; ++i) mx = fmaxf(fmaxf(mx, sacc[0][i]), sacc[1][i]);
-    mx = xhalf_max(mx);
-    const bool first = t == 0;
-    const bool moved = first || mx > ATTN_MOVE_THR;
-    if (__any(moved)) {
-      const float mrel = moved ? mx : 0.f;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sacc[kb][i] -= mrel;
-      const float alpha = first ? 0.f : fast_exp2(-mrel);
-      l_run *= alpha;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int i2 = 0; i2 < 16; ++i2) oacc[i][i2] *= alpha;
-      m_run += mrel;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) rowc[i] = segc - m_run;
-    }
-    float ls = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float e = fast_exp2(sacc[kb][i]);
-        sacc[kb][i] = e;
-        ls += e;
-      }
-    l_run += ls;
+    if (kv0 + 64 > S) attn_mask_tail(sacc, kv0, S, fh);          // the segment's last tile, where it is ragged
+    attn_online_softmax<false>(sacc, t == 0, m_run, l_run, oacc, rowc, [&](float m) { return segc - m; });
     bf16x8 pf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pf[ks][j] = (bf16)sacc[ks >> 1][8 * (ks & 1) + j];
-    {
-      bf16x8 tfr[4][2];
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-          tfr[ks][db] = read_transposed_frag_at(smem + trc[db][0] + ks * 2048, smem + trc[db][1] + ks * 2048);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int db = 0; db < 2; ++db) oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tfr[ks][db], pf[ks], oacc[db], 0, 0, 0);
-    }
+    attn_pack_p(sacc, pf);
+    attn_cols_product<true>(smem, ro, 0, nullptr, lane, pf, oacc);   // transpose read: V by ro / sub; Ts and lane serve the gather only
     WAIT_VM0();
     __syncthreads();
   }
-
-  // epilogue (attn_q_body): normalise, through a per-wave LDS image, whole 128-byte rows out
-  float la = l_run, lb = l_run;
-  swap_halves32(la, lb);
-  const float inv = 1.f / (la + lb);
-  store_o_image_144(smem + wave * (32 * 144), lane, [&](int db, int i) { return oacc[db][i] * inv; },
-                    p.O + (long long)b * S * p.ldo + head * 64, p.ldo, q0, S);
+  attn_fwd_exit<1>(oacc, m_run, l_run, nullptr, 0, false, smem + wave * (32 * 144), lane, p.O + (long long)b * S * p.ldo + head * 64, p.ldo, q0, S);
 }
 
-// attn_block_coords' rule on a 1-D range of `total` workgroups: dispatch position -> position in an order where each XCD runs
-// one contiguous stretch (positions are dealt to the 8 XCDs round-robin)
-__device__ __forceinline__ unsigned xcd_contiguous(unsigned lin, unsigned total) {
-  const unsigned q = total >> 3, r = total & 7, xcd = lin & 7, j = lin >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
 // One launch over the batch, 1-D grid: the n_tgt_wg workgroups of the target samples come FIRST in dispatch order (they run twice
 // the key tiles of a plain one, so the tail of the launch is made of short workgroups), then those of the plain samples.  Inside
-// each of the two ranges the XCD rule above holds, so the query blocks of a (sample, head) -- which stream the same K and V, for a
+// each of the two ranges the XCD rule (xcd_contiguous) holds, so the query blocks of a (sample, head) -- which stream the same K and V, for a
 // target its reference's too -- share an L2.  order[]: the samples in that order.  A plain workgroup is attn_q_body itself on an
 // AttnP made of the same operands: the bits of attn_q_kernel<0, true, 1>.
 __global__ __launch_bounds__(256, 3) void attn_shared_kernel(const AttnSharedP p, int n_tgt_wg) {
