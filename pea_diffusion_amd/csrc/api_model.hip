@@ -12,14 +12,6 @@
     int rc__ = (x);                   \
     if (rc__ != PEA_OK) return rc__;  \
   } while (0)
-#define NOTNULL(p, what)                         \
-  do {                                           \
-    if (!(p)) {                                  \
-      pea_set_error("%s: null handle", what);    \
-      return PEA_E_INVALID;                      \
-    }                                            \
-  } while (0)
-
 static_assert(sizeof(pea_unet_config) == sizeof(PeaUnetCfg), "config struct mismatch");
 
 // shared tail of every pea_*_create: build the graph, plan and allocate the weights
@@ -459,549 +451,6 @@ int pea_unet_clear_freeu(void* h) {
   NOTNULL(h, "pea_unet_clear_freeu");
   ((Tape*)h)->fu_on = false;
   return PEA_OK;
-}
-// ------------------------------------------------------------------------------ image prompt (IP-Adapter)
-// what a graph must be to take one; on success *kv_op is the stacked text K|V projection
-static int ip_check(const Tape& u, int n_tokens, const Op** kv_op) {
-  if (u.graph != 0 || u.t_kvall < 0) { pea_set_error("pea_unet_ip: not a UNet handle (ControlNet graphs get no image prompt)"); return PEA_E_INVALID; }
-  if (u.needs_grad) {
-    pea_set_error("pea_unet_ip: this context was created with PEA_UNET_GRAD; there is no backward through the image branch");
-    return PEA_E_STATE;
-  }
-  SHAPECHK(n_tokens >= 1 && n_tokens <= 32, "pea_unet_ip: n_tokens=%d (1..32 image tokens)", n_tokens);
-  SHAPECHK(u.L <= 128, "pea_unet_ip: context length %d (the decoupled attention takes at most 128 text keys)", u.L);
-  *kv_op = nullptr;
-  for (const Op& o : u.ops)
-    if (o.out == u.t_kvall && o.fused >= 0) *kv_op = &o;
-  if (!*kv_op) { pea_set_error("pea_unet_ip: stacked K|V projection not found"); return PEA_E_STATE; }
-  for (const WSlot& s : u.slots)
-    if (s.fused_parent == (*kv_op)->fused && s.pad_mode) {
-      pea_set_error("pea_unet_ip: '%s' has padded heads (head_dim %d); the decoupled attention is built for head_dim 64", s.name.c_str(), s.pad_d);
-      return PEA_E_SHAPE;
-    }
-  return PEA_OK;
-}
-// K column of every cross-attention layer in the stacked K|V projection `fused` -> the layer's index in the order of
-// ip_adapter.layer_keys: every down block, then every up block, then the mid block; inside a group the order of the modules,
-// which is the order of the slots
-static void xattn_layer_order(const Tape& u, int fused, std::map<int, int>& layer_of_col) {
-  for (int group = 0; group < 3; ++group)
-    for (const WSlot& s : u.slots) {
-      const std::string& n = s.name;
-      if (s.fused_parent != fused || s.kind != W_LINEAR || n.size() < 12 || n.compare(n.size() - 12, 12, ".to_k.weight")) continue;
-      if ((n.rfind("down_blocks.", 0) == 0 ? 0 : n.rfind("up_blocks.", 0) == 0 ? 1 : 2) != group) continue;
-      const int idx = (int)layer_of_col.size();
-      layer_of_col[s.row_off] = idx;
-    }
-}
-#define IP_HANDLE(h, what)                                                                     \
-  NOTNULL(h, what);                                                                            \
-  Tape* u = (Tape*)h;                                                                          \
-  if (!u->ip) { pea_set_error("%s: call pea_unet_ip_create first", what); return PEA_E_STATE; }
-int pea_unet_ip_plan(const pea_unet_config* cfg, int n_tokens, int* n_layers, int* cols, long long* n_params) {
-  NOTNULL(cfg, "pea_unet_ip_plan");
-  Tape u;
-  memcpy(&u.cfg, cfg, sizeof(PeaUnetCfg));
-  // layers, stack width and parameters depend on the config alone: any batch / size / context length plans them.  The context
-  // length is therefore NOT validated here (ip_check's L <= 128 cannot fire); pea_unet_ip_create checks the real context
-  u.B = 1; u.H = 64; u.W = 64; u.L = 77; u.needs_grad = false;
-  u.plan_only = true;
-  int rc = u.build();
-  if (rc == PEA_OK) rc = u.alloc();
-  if (rc != PEA_OK) return rc;
-  const Op* kv = nullptr;
-  RCX(ip_check(u, n_tokens, &kv));
-  int members = 0;
-  for (const WSlot& s : u.slots) members += s.fused_parent == kv->fused && s.kind == W_LINEAR;
-  if (n_layers) *n_layers = members / 2;
-  if (cols) *cols = u.kvall_total;
-  if (n_params) *n_params = (long long)u.kvall_total * u.cfg.cross_dim;
-  return PEA_OK;
-}
-#define IP_SET(h, set, what)                                                                   \
-  IP_HANDLE(h, what);                                                                          \
-  SHAPECHK(set >= 0 && set < u->ip->nsets, "%s: set %d of %d", what, set, u->ip->nsets);      \
-  Tape::IpSet& e = u->ip->set[set];
-int pea_unet_ip_create_sets(void* h, int n_sets, const int* n_tokens) {
-  NOTNULL(h, "pea_unet_ip_create_sets");
-  NOTNULL(n_tokens, "pea_unet_ip_create_sets");
-  Tape* u = (Tape*)h;
-  SHAPECHK(n_sets >= 1 && n_sets <= 4, "pea_unet_ip_create_sets: %d adapters (1..4)", n_sets);
-  const Op* kv = nullptr;
-  int total = 0;
-  for (int j = 0; j < n_sets; ++j) {
-    RCX(ip_check(*u, n_tokens[j], &kv));
-    total += n_tokens[j];
-  }
-  SHAPECHK(total <= 32, "pea_unet_ip_create_sets: %d image tokens over all adapters (one launch takes at most 32)", total);
-  RCX(pea_unet_ip_destroy(h));                       // adapters already loaded: replaced, behind whatever still reads them
-  Tape::IpState* ip = new Tape::IpState();
-  ip->nsets = n_sets; ip->total = total; ip->cols = u->kvall_total; ip->fused = kv->fused;
-  // the file's layer order (ip_adapter.layer_keys): every down block, then every up block, then the mid block; inside a group
-  // the order of the modules, which is the order of the slots
-  xattn_layer_order(*u, kv->fused, ip->layer_of_col);
-  const size_t B = (size_t)u->B, K = (size_t)u->cfg.cross_dim;
-  bool ok = hipMalloc((void**)&ip->kv, B * total * ip->cols * 2) == hipSuccess &&
-            hipMemset(ip->kv, 0, B * total * ip->cols * 2) == hipSuccess;
-  for (int j = 0, off = 0; j < n_sets && ok; off += n_tokens[j++]) {
-    Tape::IpSet& e = ip->set[j];
-    e.n = n_tokens[j]; e.off = off;
-    for (const WSlot& s : u->slots) e.loaded.push_back(!(s.fused_parent == kv->fused && s.kind == W_LINEAR));
-    ok = hipMalloc((void**)&e.w, (size_t)ip->cols * K * 2) == hipSuccess && hipMalloc((void**)&e.tok, B * e.n * K * 2) == hipSuccess;
-  }
-  if (!ok) {
-    pea_set_error("pea_unet_ip_create: out of device memory (%zu bytes of weights per adapter)", (size_t)ip->cols * K * 2);
-    delete ip;
-    return PEA_E_HIP;
-  }
-  u->ip = ip;
-  return PEA_OK;
-}
-int pea_unet_ip_create(void* h, int n_tokens) { return pea_unet_ip_create_sets(h, 1, &n_tokens); }
-int pea_unet_ip_load_weight_set(void* h, int set, const char* key, const float* src, long long numel, void* stream) {
-  IP_SET(h, set, "pea_unet_ip_load_weight");
-  NOTNULL(key, "pea_unet_ip_load_weight");
-  NOTNULL(src, "pea_unet_ip_load_weight");
-  std::string name(key);
-  const size_t at = name.rfind("_ip.weight");
-  int slot = -1;
-  if (at != std::string::npos && at + 10 == name.size()) {
-    auto it = u->slot_by_name.find(name.substr(0, at) + ".weight");      // to_k_ip -> the text stack's to_k of the same layer
-    if (it != u->slot_by_name.end() && u->slots[it->second].fused_parent == u->ip->fused) slot = it->second;
-  }
-  if (slot < 0) { pea_set_error("pea_unet_ip_load_weight: '%s' is no to_k_ip / to_v_ip weight of this UNet", key); return PEA_E_NOTFOUND; }
-  const WSlot& w = u->slots[slot];
-  SHAPECHK(numel == w.numel, "pea_unet_ip_load_weight: '%s' has %lld elements, expected %lld ([%d][%d])", key, numel, w.numel, w.d0, w.d1);
-  RCX(launch_cast_f32_bf16(src, e.w + (size_t)w.row_off * w.d1, numel, (hipStream_t)stream));
-  e.loaded[slot] = 1;
-  return PEA_OK;
-}
-int pea_unet_ip_load_weight(void* h, const char* key, const float* src, long long numel, void* stream) {
-  return pea_unet_ip_load_weight_set(h, 0, key, src, numel, stream);
-}
-int pea_unet_ip_set_tokens_set(void* h, int set, const float* tokens, void* stream) {
-  IP_SET(h, set, "pea_unet_ip_set_tokens");
-  NOTNULL(tokens, "pea_unet_ip_set_tokens");
-  Tape::IpState& ip = *u->ip;
-  for (size_t i = 0; i < e.loaded.size(); ++i)
-    if (!e.loaded[i]) {
-      const std::string& n = u->slots[i].name;
-      pea_set_error("pea_unet_ip_set_tokens: '%s_ip.weight' was never loaded", n.substr(0, n.size() - 7).c_str());
-      return PEA_E_STATE;
-    }
-  hipStream_t s = (hipStream_t)stream;
-  const int rows = u->B * e.n, K = u->cfg.cross_dim;
-  RCX(launch_cast_f32_bf16(tokens, e.tok, (long long)rows * K, s));
-  // one adapter: ONE GEMM over all samples.  Several: the set's rows of a sample are not adjacent to those of the next, so one
-  // GEMM per sample straight into its rows of the packed buffer (once per image, B is the CFG batch)
-  const int launches = ip.nsets == 1 ? 1 : u->B, m = rows / launches;
-  for (int b = 0; b < launches; ++b) {
-    GemmP p; fill_gemm(p);
-    p.A = e.tok + (size_t)b * m * K; p.lda = K; p.M = m; p.K = K; p.N = ip.cols; p.W = e.w; p.ldw = K;
-    p.C = ip.kv + ((size_t)b * ip.total + e.off) * ip.cols; p.ldc = ip.cols;
-    RCX(launch_gemm(p, s));
-  }
-  e.live = true;
-  return PEA_OK;
-}
-int pea_unet_ip_set_tokens(void* h, const float* tokens, void* stream) { return pea_unet_ip_set_tokens_set(h, 0, tokens, stream); }
-int pea_unet_ip_set_scale_set(void* h, int set, float scale) {
-  IP_SET(h, set, "pea_unet_ip_set_scale");
-  e.scale = scale;
-  return PEA_OK;
-}
-int pea_unet_ip_set_scale(void* h, float scale) { return pea_unet_ip_set_scale_set(h, 0, scale); }
-int pea_unet_ip_set_layer_scales(void* h, int set, const float* scales, int n_layers) {
-  IP_SET(h, set, "pea_unet_ip_set_layer_scales");
-  if (!scales) {                                     // back to 1 in every layer
-    e.layer_scale.clear();
-    return PEA_OK;
-  }
-  const int want = (int)u->ip->layer_of_col.size();
-  SHAPECHK(n_layers == want, "pea_unet_ip_set_layer_scales: %d scales, this UNet has %d cross-attention layers", n_layers, want);
-  e.layer_scale.assign(scales, scales + n_layers);
-  return PEA_OK;
-}
-static void ip_query_counts(const Tape& u, std::vector<int>& out) {
-  for (const Op& o : u.ops)
-    if (o.kind == OP_ATTN && o.b == u.t_kvall && std::find(out.begin(), out.end(), o.p1) == out.end()) out.push_back(o.p1);
-}
-int pea_unet_ip_query_counts(void* h, int* counts, int cap, int* n) {
-  NOTNULL(h, "pea_unet_ip_query_counts");
-  std::vector<int> c;
-  ip_query_counts(*(Tape*)h, c);
-  if (n) *n = (int)c.size();
-  for (int i = 0; counts && i < cap && i < (int)c.size(); ++i) counts[i] = c[i];
-  return PEA_OK;
-}
-int pea_unet_ip_set_mask(void* h, int set, int Sq, const float* mask, int Bm, void* stream) {
-  IP_SET(h, set, "pea_unet_ip_set_mask");
-  if (!mask) {                                       // drop the mask of that count, or (Sq == 0) all of them
-    HIPCHK(hipDeviceSynchronize());                  // a queued forward may still read them
-    for (auto it = e.mask.begin(); it != e.mask.end();)
-      if (Sq == 0 || it->first == Sq) { (void)hipFree(it->second.first); it = e.mask.erase(it); } else ++it;
-    return PEA_OK;
-  }
-  std::vector<int> c;
-  ip_query_counts(*u, c);
-  if (std::find(c.begin(), c.end(), Sq) == c.end()) {
-    pea_set_error("pea_unet_ip_set_mask: no cross-attention layer of this context has %d queries (pea_unet_ip_query_counts)", Sq);
-    return PEA_E_SHAPE;
-  }
-  SHAPECHK(Bm == 1 || Bm == u->B, "pea_unet_ip_set_mask: Bm=%d (1, or the context's batch %d)", Bm, u->B);
-  auto it = e.mask.find(Sq);
-  if (it != e.mask.end() && it->second.second != Bm) {
-    HIPCHK(hipDeviceSynchronize());
-    (void)hipFree(it->second.first);
-    e.mask.erase(it);
-    it = e.mask.end();
-  }
-  if (it == e.mask.end()) {
-    float* buf = nullptr;
-    HIPCHK(hipMalloc((void**)&buf, (size_t)Bm * Sq * sizeof(float)));
-    it = e.mask.emplace(Sq, std::make_pair(buf, Bm)).first;
-  }
-  HIPCHK(hipMemcpyAsync(it->second.first, mask, (size_t)Bm * Sq * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return PEA_OK;
-}
-// ------------------------------------------------------------------------------ regional text prompts
-int pea_unet_set_prompt_regions(void* h, int R, int Sq, const float* w, int Bw, void* stream) {
-  NOTNULL(h, "pea_unet_set_prompt_regions");
-  Tape* u = (Tape*)h;
-  if (u->graph != 0 || u->t_kvall < 0) { pea_set_error("pea_unet_set_prompt_regions: not a UNet handle (ControlNet graphs keep one prompt)"); return PEA_E_INVALID; }
-  if (!w) { pea_set_error("pea_unet_set_prompt_regions: null weights"); return PEA_E_INVALID; }
-  RCX(u->regions_check(R, false));
-  SHAPECHK(!u->regions || u->regions->R == R, "pea_unet_set_prompt_regions: R=%d, but weights for %d regions are set (pea_unet_clear_prompt_regions)",
-           R, u->regions ? u->regions->R : 0);
-  std::vector<int> c;
-  ip_query_counts(*u, c);
-  if (std::find(c.begin(), c.end(), Sq) == c.end()) {
-    pea_set_error("pea_unet_set_prompt_regions: no cross-attention layer of this context has %d queries (pea_unet_ip_query_counts)", Sq);
-    return PEA_E_SHAPE;
-  }
-  SHAPECHK(Bw == 1 || Bw == u->B, "pea_unet_set_prompt_regions: Bw=%d (1, or the context's batch %d)", Bw, u->B);
-  if (!u->regions) { u->regions = new Tape::RegionState(); u->regions->R = R; }
-  auto& tab = u->regions->w;
-  auto it = tab.find(Sq);
-  if (it != tab.end() && it->second.second != Bw) {
-    HIPCHK(hipDeviceSynchronize());                  // a queued forward may still read it
-    (void)hipFree(it->second.first);
-    tab.erase(it);
-    it = tab.end();
-  }
-  const size_t bytes = (size_t)Bw * R * Sq * sizeof(float);
-  if (it == tab.end()) {
-    float* buf = nullptr;
-    HIPCHK(hipMalloc((void**)&buf, bytes));
-    it = tab.emplace(Sq, std::make_pair(buf, Bw)).first;
-  }
-  HIPCHK(hipMemcpyAsync(it->second.first, w, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return PEA_OK;
-}
-int pea_unet_clear_prompt_regions(void* h) {
-  NOTNULL(h, "pea_unet_clear_prompt_regions");
-  Tape* u = (Tape*)h;
-  if (u->regions) HIPCHK(hipDeviceSynchronize());    // a queued forward may still read the weights
-  delete u->regions;
-  u->regions = nullptr;
-  return PEA_OK;
-}
-// ------------------------------------------------------------------------------ prompt-to-prompt editing
-int pea_unet_set_prompt_edit(void* h, const int* src, const void* Mt, const float* cd, int T, int self_until, int self_max_tokens,
-                             void* stream) {
-  NOTNULL(h, "pea_unet_set_prompt_edit");
-  Tape* u = (Tape*)h;
-  if (u->graph != 0 || u->t_kvall < 0) { pea_set_error("pea_unet_set_prompt_edit: not a UNet handle (graph %d has no text cross-attention to edit)", u->graph); return PEA_E_INVALID; }
-  if (!src || !Mt || !cd) { pea_set_error("pea_unet_set_prompt_edit: null src, Mt or cd"); return PEA_E_INVALID; }
-  RCX(u->edit_check(false));
-  const int B = u->B, L = u->L;
-  SHAPECHK(T >= 1 && T <= (1 << 20), "pea_unet_set_prompt_edit: T=%d steps", T);
-  SHAPECHK(self_until >= 0 && self_max_tokens >= 0, "pea_unet_set_prompt_edit: self_until=%d, self_max_tokens=%d (>= 0)", self_until, self_max_tokens);
-  int n_edited = 0;
-  for (int b = 0; b < B; ++b) {
-    if (src[b] < 0 || src[b] == b) continue;                       // (its own source: not edited)
-    SHAPECHK(src[b] < B, "pea_unet_set_prompt_edit: src[%d]=%d is out of range (batch %d)", b, src[b], B);
-    SHAPECHK(src[src[b]] < 0 || src[src[b]] == src[b], "pea_unet_set_prompt_edit: src[%d]=%d names a source that is itself edited", b, src[b]);
-    ++n_edited;
-  }
-  RCX(pea_unet_clear_prompt_edit(h));
-  Tape::EditState* e = new Tape::EditState();
-  for (int b = 0; b < 32; ++b) e->src[b] = b < B && src[b] != b ? src[b] : -1;
-  e->n_edited = n_edited; e->T = T; e->self_until = self_until; e->self_max_tokens = self_max_tokens; e->ldm = (L + 7) / 8 * 8;
-  const size_t cd_elems = (size_t)T * 2 * B * L;
-  std::vector<float> host(cd_elems);
-  hipError_t err = hipMalloc((void**)&e->Mt, (size_t)B * L * e->ldm * sizeof(bf16));
-  if (err == hipSuccess) err = hipMalloc((void**)&e->cd, cd_elems * sizeof(float));
-  if (err == hipSuccess) err = hipMemsetAsync(e->Mt, 0, (size_t)B * L * e->ldm * sizeof(bf16), (hipStream_t)stream);
-  if (err == hipSuccess) err = hipMemcpy2DAsync(e->Mt, (size_t)e->ldm * sizeof(bf16), Mt, (size_t)L * sizeof(bf16), (size_t)L * sizeof(bf16),
-                                                (size_t)B * L, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(e->cd, cd, cd_elems * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(host.data(), cd, cd_elems * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream);
-  if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t)stream);
-  if (err != hipSuccess) {
-    pea_set_error("pea_unet_set_prompt_edit: %s", hipGetErrorString(err));
-    delete e;
-    return PEA_E_HIP;
-  }
-  e->cd_live.assign(T, 0);
-  for (int t = 0; t < T; ++t)
-    for (int b = 0; b < B && !e->cd_live[t]; ++b) {
-      if (e->src[b] < 0) continue;
-      const float* c = host.data() + ((size_t)t * 2 * B + b) * L;
-      const float* d = c + (size_t)B * L;
-      for (int j = 0; j < L; ++j)
-        if (c[j] != 0.f || d[j] != 1.f) { e->cd_live[t] = 1; break; }
-    }
-  u->edit = e;
-  return PEA_OK;
-}
-int pea_unet_set_prompt_edit_step(void* h, int step) {
-  NOTNULL(h, "pea_unet_set_prompt_edit_step");
-  Tape* u = (Tape*)h;
-  if (!u->edit) { pea_set_error("pea_unet_set_prompt_edit_step: call pea_unet_set_prompt_edit first"); return PEA_E_STATE; }
-  u->edit->step = step;                               // (a step outside 0..T-1 is refused by the forward that would use it)
-  return PEA_OK;
-}
-int pea_unet_clear_prompt_edit(void* h) {
-  NOTNULL(h, "pea_unet_clear_prompt_edit");
-  Tape* u = (Tape*)h;
-  if (u->edit) HIPCHK(hipDeviceSynchronize());        // a queued forward may still read the tables
-  delete u->edit;
-  u->edit = nullptr;
-  return PEA_OK;
-}
-// ------------------------------------------------------------------------------ StyleAligned generation
-static int self_attn_layers(const Tape& u, std::map<int, int>* layer_of_op) {
-  int n = 0;
-  for (size_t i = 0; i < u.ops.size(); ++i)
-    if (u.is_self_attn(u.ops[i])) {
-      if (layer_of_op) (*layer_of_op)[(int)i] = n;
-      ++n;
-    }
-  return n;
-}
-int pea_unet_num_self_attention_layers(void* h) {
-  NOTNULL(h, "pea_unet_num_self_attention_layers");
-  return self_attn_layers(*(Tape*)h, nullptr);
-}
-int pea_unet_set_style_aligned(void* h, const int* ref, const float* layer_on, int n_layers, int adain_queries, int adain_keys,
-                               float shared_score_scale, float shared_score_shift, void* stream) {
-  NOTNULL(h, "pea_unet_set_style_aligned");
-  Tape* u = (Tape*)h;
-  if (u->graph != 0) { pea_set_error("pea_unet_set_style_aligned: not a UNet handle (graph %d)", u->graph); return PEA_E_INVALID; }
-  if (!ref) { pea_set_error("pea_unet_set_style_aligned: null ref (a host int[B]; negative entries for plain samples)"); return PEA_E_INVALID; }
-  RCX(u->style_check(false));
-  const int B = u->B;
-  SHAPECHK(shared_score_scale == shared_score_scale && shared_score_shift == shared_score_shift && fabsf(shared_score_scale) <= 3.0e38f &&
-               fabsf(shared_score_shift) <= 1.0e30f,
-           "pea_unet_set_style_aligned: finite shared_score_scale / shared_score_shift (%g %g)", (double)shared_score_scale, (double)shared_score_shift);
-  Tape::StyleState* st = new Tape::StyleState();
-  std::unique_ptr<Tape::StyleState> guard(st);
-  for (int b = 0; b < 32; ++b) st->ref[b] = -1;
-  for (int b = 0; b < B; ++b) {
-    if (ref[b] < 0 || ref[b] == b) continue;                       // (its own reference: plain)
-    SHAPECHK(ref[b] < B, "pea_unet_set_style_aligned: ref[%d]=%d is out of range (batch %d)", b, ref[b], B);
-    SHAPECHK(ref[ref[b]] < 0 || ref[ref[b]] == ref[b], "pea_unet_set_style_aligned: ref[%d]=%d names a reference that is itself a target", b, ref[b]);
-    st->ref[b] = ref[b];
-    ++st->n_targets;
-  }
-  const int want = self_attn_layers(*u, &st->layer_of_op);
-  if (layer_on && n_layers != want) {
-    pea_set_error("pea_unet_set_style_aligned: %d layer switches, this UNet has %d self-attention layers", n_layers, want);
-    return PEA_E_SHAPE;
-  }
-  st->on.assign(want, 1);
-  for (int i = 0; layer_on && i < want; ++i) st->on[i] = layer_on[i] != 0.f;
-  st->adain_q = adain_queries != 0; st->adain_k = adain_keys != 0;
-  st->share_scale = shared_score_scale; st->share_shift = shared_score_shift;
-  size_t coef_bytes = 0, scratch_bytes = 0;
-  for (const Op& o : u->ops) {
-    if (!u->is_self_attn(o)) continue;
-    coef_bytes = std::max(coef_bytes, sizeof(float) * (size_t)B * 4 * 64 * o.p0);
-    scratch_bytes = std::max(scratch_bytes, attn_adain_scratch_bytes(B, o.p0, o.p1));
-  }
-  RCX(pea_unet_clear_style_aligned(h));
-  if (st->n_targets && coef_bytes) {
-    hipError_t err = hipMalloc((void**)&st->coef, coef_bytes);
-    if (err == hipSuccess) err = hipMalloc((void**)&st->scratch, std::max(scratch_bytes, (size_t)16));
-    if (err != hipSuccess) { pea_set_error("pea_unet_set_style_aligned: %s", hipGetErrorString(err)); return PEA_E_HIP; }
-  }
-  (void)stream;                                                     // nothing is transferred: ref is a host table
-  u->style = guard.release();
-  return PEA_OK;
-}
-int pea_unet_clear_style_aligned(void* h) {
-  NOTNULL(h, "pea_unet_clear_style_aligned");
-  Tape* u = (Tape*)h;
-  if (u->style && u->style->coef) HIPCHK(hipDeviceSynchronize());   // a queued forward may still use the buffers
-  delete u->style;
-  u->style = nullptr;
-  return PEA_OK;
-}
-// ------------------------------------------------------------------------------ self-attention guidance
-int pea_unet_enable_sag(void* h, int layer, int first_sample, int n_samples) {
-  NOTNULL(h, "pea_unet_enable_sag");
-  Tape* u = (Tape*)h;
-  if (u->graph != 0) { pea_set_error("pea_unet_enable_sag: not a UNet handle (graph %d)", u->graph); return PEA_E_INVALID; }
-  std::map<int, int> layer_of_op;
-  const int want = self_attn_layers(*u, &layer_of_op);
-  SHAPECHK(layer >= 0 && layer < want, "pea_unet_enable_sag: layer %d, this UNet has %d self-attention layers", layer, want);
-  SHAPECHK(first_sample >= 0 && n_samples >= 1 && first_sample + n_samples <= u->B,
-           "pea_unet_enable_sag: samples %d .. %d of a batch of %d", first_sample, first_sample + n_samples - 1, u->B);
-  Tape::SagState* st = new Tape::SagState();
-  std::unique_ptr<Tape::SagState> guard(st);
-  for (const auto& lo : layer_of_op)
-    if (lo.second == layer) st->op = lo.first;
-  const Op& o = u->ops[st->op];
-  const int head_dim = (int)lroundf(1.f / (o.f0 * o.f0));           // (the softmax scale is head_dim^-1/2; padded heads keep their own)
-  SHAPECHK(o.p3 == 1 && head_dim == 64, "pea_unet_enable_sag: self-attention layer %d has head_dim %d (stored as %d); the column-sum "
-           "kernel is built for 64", layer, head_dim, 64 * o.p3);
-  st->layer = layer; st->first = first_sample; st->n = n_samples; st->H = o.p0; st->S = o.p1;
-  st->G = attention_colsum_groups(n_samples, o.p0, o.p1, o.p2);
-  if (st->G < 1) return PEA_E_SHAPE;
-  RCX(pea_unet_disable_sag(h));
-  u->sag = st;                                                      // (the checks read the state they judge)
-  const int rc = u->sag_check(false);
-  u->sag = nullptr;
-  if (rc) return rc;
-  hipError_t err = hipMalloc((void**)&st->lse, sizeof(float) * (size_t)u->B * o.p0 * o.p1);
-  if (err == hipSuccess) err = hipMalloc((void**)&st->part, sizeof(float) * (size_t)n_samples * st->G * o.p2);
-  if (err == hipSuccess) err = hipMemset(st->part, 0, sizeof(float) * (size_t)n_samples * st->G * o.p2);
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  if (err != hipSuccess) { pea_set_error("pea_unet_enable_sag: %s", hipGetErrorString(err)); return PEA_E_HIP; }
-  u->sag = guard.release();
-  return PEA_OK;
-}
-int pea_unet_disable_sag(void* h) {
-  NOTNULL(h, "pea_unet_disable_sag");
-  Tape* u = (Tape*)h;
-  if (u->sag) HIPCHK(hipDeviceSynchronize());        // a queued forward may still write the buffers
-  delete u->sag;
-  u->sag = nullptr;
-  return PEA_OK;
-}
-int pea_unet_sag_colsum(void* h, float** part, int* G, int* S) {
-  NOTNULL(h, "pea_unet_sag_colsum");
-  Tape* u = (Tape*)h;
-  if (!u->sag) { pea_set_error("pea_unet_sag_colsum: call pea_unet_enable_sag first"); return PEA_E_STATE; }
-  if (part) *part = u->sag->part;
-  if (G) *G = u->sag->G;
-  if (S) *S = u->sag->S;
-  return PEA_OK;
-}
-// ------------------------------------------------------------------------------ cross-attention heat maps
-int pea_unet_enable_attention_maps(void* h, const float* layer_on, int n_layers) {
-  NOTNULL(h, "pea_unet_enable_attention_maps");
-  Tape* u = (Tape*)h;
-  if (u->graph != 0 || u->t_kvall < 0) {
-    pea_set_error("pea_unet_enable_attention_maps: not a UNet handle (graph %d has no text cross-attention to map)", u->graph);
-    return PEA_E_INVALID;
-  }
-  if (u->needs_grad) {
-    pea_set_error("pea_unet_enable_attention_maps: heat maps are an inference feature; this context was created with PEA_UNET_GRAD");
-    return PEA_E_STATE;
-  }
-  SHAPECHK(u->L >= 1 && u->L <= 128, "pea_unet_enable_attention_maps: context length %d (the maps kernel takes 1..128 keys)", u->L);
-  const Op* kv = nullptr;
-  for (const Op& o : u->ops)
-    if (o.out == u->t_kvall && o.fused >= 0) kv = &o;
-  if (!kv) { pea_set_error("pea_unet_enable_attention_maps: stacked K|V projection not found"); return PEA_E_STATE; }
-  for (const WSlot& s : u->slots)
-    SHAPECHK(!(s.fused_parent == kv->fused && s.pad_mode), "pea_unet_enable_attention_maps: '%s' has padded heads (head_dim %d); the maps "
-             "kernel is built for head_dim 64", s.name.c_str(), s.pad_d);
-  for (const Op& o : u->ops)
-    if (o.kind == OP_ATTN && o.b == u->t_kvall)
-      SHAPECHK(o.p3 == 1 && o.p2 == u->L, "pea_unet_enable_attention_maps: head_dim 64 cross-attention over the whole context (nd=%d, %d keys)", o.p3, o.p2);
-  Tape::MapState* m = new Tape::MapState();
-  xattn_layer_order(*u, kv->fused, m->layer_of_col);
-  const int want = (int)m->layer_of_col.size();
-  if (layer_on && n_layers != want) {
-    delete m;
-    pea_set_error("pea_unet_enable_attention_maps: %d layer switches, this UNet has %d cross-attention layers", n_layers, want);
-    return PEA_E_SHAPE;
-  }
-  m->on.assign(want, 1);
-  for (int i = 0; layer_on && i < want; ++i) m->on[i] = layer_on[i] != 0.f;
-  int rc = pea_unet_disable_attention_maps(h);        // accumulators already there: replaced, behind whatever still adds to them
-  std::vector<int> c;
-  ip_query_counts(*u, c);
-  for (size_t i = 0; i < c.size() && rc == PEA_OK; ++i) {
-    const size_t bytes = (size_t)u->B * u->L * c[i] * sizeof(float);
-    float* buf = nullptr;
-    if (hipMalloc((void**)&buf, bytes) != hipSuccess || (m->acc[c[i]] = buf, hipMemset(buf, 0, bytes)) != hipSuccess) {
-      pea_set_error("pea_unet_enable_attention_maps: out of device memory (%zu bytes for the %d-query level)", bytes, c[i]);
-      rc = PEA_E_HIP;
-    }
-    m->count[c[i]] = 0;
-  }
-  if (rc == PEA_OK && hipDeviceSynchronize() != hipSuccess) {  // the zeros are there before a forward on any stream adds to them
-    pea_set_error("pea_unet_enable_attention_maps: device synchronisation failed");
-    rc = PEA_E_HIP;
-  }
-  if (rc != PEA_OK) { delete m; return rc; }
-  u->maps = m;
-  return PEA_OK;
-}
-int pea_unet_reset_attention_maps(void* h, void* stream) {
-  NOTNULL(h, "pea_unet_reset_attention_maps");
-  Tape* u = (Tape*)h;
-  if (!u->maps) { pea_set_error("pea_unet_reset_attention_maps: call pea_unet_enable_attention_maps first"); return PEA_E_STATE; }
-  for (auto& a : u->maps->acc) {
-    HIPCHK(hipMemsetAsync(a.second, 0, (size_t)u->B * u->L * a.first * sizeof(float), (hipStream_t)stream));
-    u->maps->count[a.first] = 0;
-  }
-  return PEA_OK;
-}
-int pea_unet_disable_attention_maps(void* h) {
-  NOTNULL(h, "pea_unet_disable_attention_maps");
-  Tape* u = (Tape*)h;
-  if (u->maps) HIPCHK(hipDeviceSynchronize());       // a queued forward may still add to the accumulators
-  delete u->maps;
-  u->maps = nullptr;
-  return PEA_OK;
-}
-int pea_unet_attention_maps(void* h, int Sq, float** maps, long long* n_accumulated) {
-  NOTNULL(h, "pea_unet_attention_maps");
-  Tape* u = (Tape*)h;
-  if (!u->maps) { pea_set_error("pea_unet_attention_maps: call pea_unet_enable_attention_maps first"); return PEA_E_STATE; }
-  const auto it = u->maps->acc.find(Sq);
-  if (it == u->maps->acc.end()) {
-    pea_set_error("pea_unet_attention_maps: no cross-attention layer of this context has %d queries (pea_unet_ip_query_counts)", Sq);
-    return PEA_E_SHAPE;
-  }
-  if (maps) *maps = it->second;
-  if (n_accumulated) *n_accumulated = u->maps->count[Sq];
-  return PEA_OK;
-}
-int pea_unet_ip_clear_set(void* h, int set) {
-  IP_SET(h, set, "pea_unet_ip_clear");
-  e.live = false;
-  return PEA_OK;
-}
-int pea_unet_ip_clear(void* h) {
-  NOTNULL(h, "pea_unet_ip_clear");
-  if (((Tape*)h)->ip)
-    for (Tape::IpSet& e : ((Tape*)h)->ip->set) e.live = false;
-  return PEA_OK;
-}
-int pea_unet_ip_destroy(void* h) {
-  NOTNULL(h, "pea_unet_ip_destroy");
-  Tape* u = (Tape*)h;
-  if (u->ip) HIPCHK(hipDeviceSynchronize());       // a queued forward may still read the buffers
-  delete u->ip;
-  u->ip = nullptr;
-  return PEA_OK;
-}
-int pea_unet_ip_export_kv(void* h, float* out, long long* rows, int* cols, void* stream) {
-  IP_HANDLE(h, "pea_unet_ip_export_kv");
-  const long long r = (long long)u->B * u->ip->total;
-  if (rows) *rows = r;
-  if (cols) *cols = u->ip->cols;
-  if (!out) return PEA_OK;
-  bool live = false;
-  for (const Tape::IpSet& e : u->ip->set) live = live || e.live;
-  if (!live) { pea_set_error("pea_unet_ip_export_kv: no tokens set"); return PEA_E_STATE; }
-  return launch_cast_bf16_f32(u->ip->kv, out, r * u->ip->cols, (hipStream_t)stream);
 }
 int pea_unet_num_weights(void* h) { return h ? (int)((Tape*)h)->slots.size() : 0; }
 int pea_unet_weight_info(void* h, int i, char* name, int name_len, long long* numel, int* kind, int* d0, int* d1) {

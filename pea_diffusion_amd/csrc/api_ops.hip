@@ -23,22 +23,23 @@ int pea_zero_page(const bf16** out) {
   return PEA_OK;
 }
 
-// what every attention entry point starts from: a zeroed AttnP with Q / K / V / O, lse, the shape, the scale and nd set
-static AttnP attn_operands(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O, int ldo,
-                           const float* lse, int B, int H, int Sq, int Skv, float scale, int nd) {
+// what every attention entry point starts from: a zeroed P -- AttnP, or a feature's struct with the operands it shares with
+// AttnP (pea_kernels.h: attn_feature_p) -- with Q / K / V / O, lse, the shape, the scale, nd and the Q convention set
+template <class P = AttnP>
+static P attn_operands(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O, int ldo,
+                       const float* lse, int B, int H, int Sq, int Skv, float scale, int nd, int q_prescaled = 0) {
   AttnP p;
   memset(&p, 0, sizeof(p));
   p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
   p.O = (bf16*)O; p.ldo = ldo; p.lse = (float*)lse; p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.nd = nd;
-  return p;
+  p.q_prescaled = q_prescaled;
+  return attn_feature_p<P>(p);
 }
 // bodies of the attention operators with the Q convention as a PARAMETER (the entry points below pass 0 or 1): nothing
 // process-wide is written around a call, so concurrent callers (ctypes releases the GIL) cannot see each other's mode
 static int attention_fwd_impl(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo,
                               float* lse, int B, int H, int Sq, int Skv, float scale, int nd, int q_prescaled, void* stream) {
-  AttnP p = attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, nd);
-  p.q_prescaled = q_prescaled;
-  return launch_attention_fwd(p, (hipStream_t)stream);
+  return launch_attention_fwd(attn_operands(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Sq, Skv, scale, nd, q_prescaled), (hipStream_t)stream);
 }
 static int attention_bwd_impl(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O,
                               int ldo, const void* dO, int lddo, const float* lse, float* delta, void* dQ, int lddq,
@@ -307,29 +308,22 @@ int pea_op_attention_fwd_ipn(const void* Q, int ldq, const void* K, int ldk, con
 }
 int pea_op_attention_fwd_regions(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H,
                                  int Sq, int R, int Lr, const float* w, int Bw, float scale, int q_prescaled, void* stream) {
-  AttnRegionsP p = AttnRegionsP();
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.B = B; p.H = H; p.Sq = Sq; p.R = R; p.Lr = Lr; p.w = w; p.Bw = Bw; p.scale = scale; p.q_prescaled = q_prescaled; p.nd = 1;
+  AttnRegionsP p = attn_operands<AttnRegionsP>(Q, ldq, K, ldk, V, ldv, O, ldo, nullptr, B, H, Sq, 0, scale, 1, q_prescaled);
+  p.R = R; p.Lr = Lr; p.w = w; p.Bw = Bw;
   return launch_attention_fwd_regions(p, (hipStream_t)stream);
 }
 int pea_op_attention_maps(const void* Q, int ldq, const void* K, int ldk, float* maps, int B, int H, int Sq, int Skv, float scale,
                           int q_prescaled, const int* kv_len, int accumulate, void* stream) {
-  AttnMapsP p = AttnMapsP();
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.ldq = ldq; p.ldk = ldk; p.maps = maps;
-  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.q_prescaled = q_prescaled; p.kv_len = kv_len;
-  p.accumulate = accumulate; p.nd = 1;
+  AttnMapsP p = attn_operands<AttnMapsP>(Q, ldq, K, ldk, nullptr, 0, nullptr, 0, nullptr, B, H, Sq, Skv, scale, 1, q_prescaled);
+  p.maps = maps; p.kv_len = kv_len; p.accumulate = accumulate;
   return launch_attention_maps(p, (hipStream_t)stream);
 }
 int pea_op_attention_fwd_edit(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O, int ldo, int B, int H,
                               int Sq, int Skv, const int* src, const void* Mt, int ldm, const float* c, const float* d, float scale,
                               int q_prescaled, void* stream) {
   if (!src) { pea_set_error("pea_op_attention_fwd_edit: null src (a host int[B]; negative entries for unedited samples)"); return PEA_E_INVALID; }
-  AttnEditP p = AttnEditP();
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.Mt = (const bf16*)Mt; p.ldm = ldm; p.c = c; p.d = d;
-  p.scale = scale; p.q_prescaled = q_prescaled; p.nd = 1;
+  AttnEditP p = attn_operands<AttnEditP>(Q, ldq, K, ldk, V, ldv, O, ldo, nullptr, B, H, Sq, Skv, scale, 1, q_prescaled);
+  p.Mt = (const bf16*)Mt; p.ldm = ldm; p.c = c; p.d = d;
   for (int b = 0; b < 32; ++b) p.src[b] = b < B ? src[b] : -1;      // (B > 32 is refused by the launcher)
   return launch_attention_fwd_edit(p, (hipStream_t)stream);
 }
@@ -345,11 +339,8 @@ int pea_op_attention_fwd_shared(const void* Q, int ldq, const void* K, int ldk, 
                                 int Sq, int Skv, const int* ref, const float* coef, float scale, int q_prescaled,
                                 float shared_score_scale, float shared_score_shift, int nd, void* stream) {
   if (!ref) { pea_set_error("pea_op_attention_fwd_shared: null ref (a host int[B]; negative entries for plain samples)"); return PEA_E_INVALID; }
-  AttnSharedP p = AttnSharedP();
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.coef = coef; p.scale = scale; p.q_prescaled = q_prescaled;
-  p.share_scale = shared_score_scale; p.share_shift = shared_score_shift; p.nd = nd;
+  AttnSharedP p = attn_operands<AttnSharedP>(Q, ldq, K, ldk, V, ldv, O, ldo, nullptr, B, H, Sq, Skv, scale, nd, q_prescaled);
+  p.coef = coef; p.share_scale = shared_score_scale; p.share_shift = shared_score_shift;
   for (int b = 0; b < 32; ++b) p.ref[b] = b < B ? ref[b] : -1;      // (B > 32 is refused by the launcher)
   return launch_attention_fwd_shared(p, (hipStream_t)stream);
 }
@@ -474,9 +465,8 @@ int pea_op_euler_update(float* sample, const float* eps, const float* noise, flo
 int pea_op_attention_colsum_groups(int B, int H, int Sq, int Skv) { return attention_colsum_groups(B, H, Sq, Skv); }
 int pea_op_attention_colsum(const void* Q, int ldq, const void* K, int ldk, const float* lse, float* part, int B, int H, int Sq, int Skv,
                             float scale, int q_prescaled, void* stream) {
-  AttnColsumP p = AttnColsumP();
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.ldq = ldq; p.ldk = ldk; p.lse = lse; p.part = part;
-  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.scale = scale; p.q_prescaled = q_prescaled; p.nd = 1;
+  AttnColsumP p = attn_operands<AttnColsumP>(Q, ldq, K, ldk, nullptr, 0, nullptr, 0, nullptr, B, H, Sq, Skv, scale, 1, q_prescaled);
+  p.lse = lse; p.part = part;
   return launch_attention_colsum(p, (hipStream_t)stream);
 }
 int pea_op_sag_degrade(const float* latents, const float* eps, const float* part, int G, int map_h, int map_w, const int* iy,

@@ -3161,18 +3161,29 @@ static int attn_go(int dir, const AttnP& p0, hipStream_t s) {
 int launch_attention_fwd(const AttnP& p, hipStream_t s) { return attn_go(0, p, s); }
 int launch_attention_bwd(const AttnP& p, hipStream_t s) { return attn_go(1, p, s); }
 int launch_attention_fwd_fewq(const AttnP& p, hipStream_t s) { return attn_go(2, p, s); }
-// include/pea_hip.h.  Every operand of the problem is a non-null, aligned stand-in; nothing is launched
+// What the pea_debug_attn_*_dispatch exports plan over: struct F (AttnP or a feature's) with non-null, aligned stand-ins for the
+// common operands (nothing is launched, nothing is read), scale 1 / 8 and every leading dimension 64 H nd; ldk > 0: that of K.
+static float g_standin_page[64] __attribute__((aligned(16)));
+template <class F>
+static F attn_standin(int B, int H, int Sq, int Skv, int nd, int ldk = 0) {
+  AttnP a = AttnP();
+  a.Q = a.K = a.V = a.O = (bf16*)g_standin_page; a.scale = 0.125f;
+  a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.nd = nd;
+  a.ldq = a.ldk = a.ldv = a.ldo = 64 * H * (nd > 0 ? nd : 1);
+  if (ldk > 0) a.ldk = ldk;
+  return attn_feature_p<F>(a);
+}
+// include/pea_hip.h
 extern "C" int pea_debug_attn_dispatch(const int* q, int* out) {
   const int dir = q[0], feat = q[6];
   if (dir < 0 || dir > 2) return q[1] >= 0 && q[1] < AK_COUNT ? q[1] : -1;
   const AttnEnv e = {q[10] < 0 ? g_attn_env.xattn_ver : q[10], q[11] < 0 ? g_attn_env.use_tr : q[11],
                      q[12] < 0 ? g_attn_env.xattn : q[12], q[13] < 0 ? g_attn_env.fused_bwd : q[13]};
-  static float page[64];
+  float* const page = g_standin_page;
   bf16* const any = (bf16*)page;
-  AttnP p = AttnP();
-  p.Q = p.K = p.V = p.dO = any; p.O = any; p.lse = p.delta = page; p.scale = 0.125f;
-  p.B = q[1]; p.H = q[2]; p.Sq = q[3]; p.Skv = q[4]; p.nd = q[5];
-  p.ldq = p.ldk = p.ldv = p.ldo = p.lddo = p.lddq = p.lddk = p.lddv = p.ldk2 = p.ldv2 = 64 * p.H * (p.nd > 0 ? p.nd : 1);
+  AttnP p = attn_standin<AttnP>(q[1], q[2], q[3], q[4], q[5]);
+  p.dO = any; p.lse = p.delta = page;
+  p.lddo = p.lddq = p.lddk = p.lddv = p.ldk2 = p.ldv2 = p.ldq;
   p.causal = feat & 1; p.kv_len = feat & 2 ? (const int*)page : nullptr; p.bias = feat & 4 ? page : nullptr; p.q_prescaled = feat >> 3 & 1;
   if (feat & 16) { p.K2 = p.V2 = any; p.Skv2 = q[7]; p.scale2 = 1.f; p.nset = dir == 2 ? 0 : q[8]; }
   for (int j = 0; j < p.nset && j < 4; ++j) {                       // the sets share the Skv2 keys evenly; bit j of q[9]: set j has a mask
@@ -3214,13 +3225,21 @@ static int attn_check_operands(const char* who, const AttnOperands& a, int H, fl
            "%s: Q / K / V 16-byte, O %d-byte, fp32 operands 4-byte aligned", who, a.o_bytes);
   return PEA_OK;
 }
-// the plain attention over a feature's operands: what its unedited / plain samples compute, on the host and on the device
-template <class P>
-__host__ __device__ static inline AttnP attn_plain_p(const P& p) {
-  AttnP a = AttnP();
-  a.Q = p.Q; a.K = p.K; a.V = p.V; a.ldq = p.ldq; a.ldk = p.ldk; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
-  a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
-  return a;
+// The tail of a feature launcher behind its plan: the profiling tag (B * H, queries, keys, nd = 1), PROF_BEGIN with the launch's
+// flops and bytes, the launch itself (`launch`: the switch over the feature's instantiations), PROF_END, the launch error.
+template <class Launch>
+static int attn_feature_launch(int BH, int Sq, int keys, double flops, double bytes, hipStream_t s, Launch launch) {
+  if (g_prof_on) { g_prof_tag[0] = BH; g_prof_tag[1] = Sq; g_prof_tag[2] = keys; g_prof_tag[3] = 1; }
+  PROF_BEGIN(2, flops, bytes, s);
+  const int rc = launch();
+  PROF_END(s);
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+// what the feature dispatch exports write: out[0..5] = first, the grid, the LDS bytes, last
+static void attn_dispatch_out(int* out, int first, dim3 grid, int lds, int last) {
+  out[0] = first; out[1] = (int)grid.x; out[2] = (int)grid.y; out[3] = (int)grid.z; out[4] = lds; out[5] = last;
 }
 
 // ============================================================================= host: regional text prompts
@@ -3251,34 +3270,24 @@ int launch_attention_fwd_regions(const AttnRegionsP& p0, hipStream_t s) {
   const int rc = attn_plan_regions(p, plan);
   if (rc) return rc;
   const double keys = (double)p.R * p.Lr;
-  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.R * p.Lr; g_prof_tag[3] = 1; }
-  PROF_BEGIN(2, 4.0 * p.B * p.H * (double)p.Sq * keys * 64, 2.0 * p.B * p.H * 64 * (2.0 * p.Sq + 2.0 * keys), s);
-  int lrc = PEA_OK;
-  // an instantiation's LDS grows with R: its limit is raised to what four regions take
-  switch (plan.kb) {
-    case 1: lrc = launch_lds<xattn_regions_fwd_kernel<1>, 256, regions_lds(4, 1)>(plan.grid, plan.lds, s, p, plan.upw); break;
-    case 2: lrc = launch_lds<xattn_regions_fwd_kernel<2>, 256, regions_lds(4, 2)>(plan.grid, plan.lds, s, p, plan.upw); break;
-    default: lrc = launch_lds<xattn_regions_fwd_kernel<3>, 256, regions_lds(4, 3)>(plan.grid, plan.lds, s, p, plan.upw); break;
-  }
-  PROF_END(s);
-  if (lrc) return lrc;
-  HIPCHK(hipGetLastError());
-  return PEA_OK;
+  return attn_feature_launch(p.B * p.H, p.Sq, p.R * p.Lr, 4.0 * p.B * p.H * (double)p.Sq * keys * 64,
+                             2.0 * p.B * p.H * 64 * (2.0 * p.Sq + 2.0 * keys), s, [&] {
+    // an instantiation's LDS grows with R: its limit is raised to what four regions take
+    switch (plan.kb) {
+      case 1: return launch_lds<xattn_regions_fwd_kernel<1>, 256, regions_lds(4, 1)>(plan.grid, plan.lds, s, p, plan.upw);
+      case 2: return launch_lds<xattn_regions_fwd_kernel<2>, 256, regions_lds(4, 2)>(plan.grid, plan.lds, s, p, plan.upw);
+      default: return launch_lds<xattn_regions_fwd_kernel<3>, 256, regions_lds(4, 3)>(plan.grid, plan.lds, s, p, plan.upw);
+    }
+  });
 }
-// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+// include/pea_hip.h
 extern "C" int pea_debug_attn_regions_dispatch(const int* q, int* out) {
-  static float page[64];
-  bf16* const any = (bf16*)page;
-  AttnRegionsP p = AttnRegionsP();
-  p.Q = p.K = p.V = any; p.O = any; p.w = page; p.scale = 0.125f;
-  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.R = q[3]; p.Lr = q[4]; p.nd = q[5];
-  p.ldq = p.ldk = p.ldv = p.ldo = 64 * p.H;
-  if (q[6] > 0) p.ldk = q[6];
-  p.Bw = q[7] > 0 ? q[7] : 1;
+  AttnRegionsP p = attn_standin<AttnRegionsP>(q[0], q[1], q[2], 0, 1, q[6]);
+  p.w = g_standin_page; p.R = q[3]; p.Lr = q[4]; p.nd = q[5]; p.Bw = q[7] > 0 ? q[7] : 1;
   AttnRegionsPlan plan;
   const int rc = attn_plan_regions(p, plan);
   if (rc) return rc;
-  out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
+  attn_dispatch_out(out, plan.kb, plan.grid, plan.lds, plan.upw);
   return PEA_OK;
 }
 
@@ -3307,34 +3316,26 @@ int launch_attention_maps(const AttnMapsP& p0, hipStream_t s) {
   AttnMapsPlan plan;
   const int rc = attn_plan_maps(p, plan);
   if (rc) return rc;
-  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = 1; }
-  PROF_BEGIN(2, 2.0 * p.B * p.H * (double)p.Sq * p.Skv * 64,
-             2.0 * p.B * p.H * 64 * ((double)p.Sq + p.Skv) + (p.accumulate ? 8.0 : 4.0) * p.B * (double)p.Sq * p.Skv, s);
-  int lrc = PEA_OK;
-  switch (plan.kb) {                                               // (this kernel's workgroup is eight waves)
-    case 1: lrc = launch_lds<xattn_maps_kernel<1>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p); break;
-    case 2: lrc = launch_lds<xattn_maps_kernel<2>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p); break;
-    case 3: lrc = launch_lds<xattn_maps_kernel<3>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p); break;
-    default: lrc = launch_lds<xattn_maps_kernel<4>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p); break;
-  }
-  PROF_END(s);
-  if (lrc) return lrc;
-  HIPCHK(hipGetLastError());
-  return PEA_OK;
+  return attn_feature_launch(p.B * p.H, p.Sq, p.Skv, 2.0 * p.B * p.H * (double)p.Sq * p.Skv * 64,
+                             2.0 * p.B * p.H * 64 * ((double)p.Sq + p.Skv) + (p.accumulate ? 8.0 : 4.0) * p.B * (double)p.Sq * p.Skv, s, [&] {
+    switch (plan.kb) {                                             // (this kernel's workgroup is eight waves)
+      case 1: return launch_lds<xattn_maps_kernel<1>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p);
+      case 2: return launch_lds<xattn_maps_kernel<2>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p);
+      case 3: return launch_lds<xattn_maps_kernel<3>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p);
+      default: return launch_lds<xattn_maps_kernel<4>, 64 * MAPS_WAVES>(plan.grid, plan.lds, s, p);
+    }
+  });
 }
-// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+// include/pea_hip.h
 extern "C" int pea_debug_attn_maps_dispatch(const int* q, int* out) {
-  static float page[64];
-  AttnMapsP p = AttnMapsP();
-  p.Q = p.K = (const bf16*)page; p.maps = page; p.scale = 0.125f;
-  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.Skv = q[3]; p.nd = q[4];
-  p.ldq = q[5] > 0 ? q[5] : 64 * p.H;
-  p.ldk = q[6] > 0 ? q[6] : 64 * p.H;
-  p.kv_len = q[7] & 1 ? (const int*)page : nullptr; p.accumulate = q[7] >> 1 & 1; p.q_prescaled = q[7] >> 2 & 1;
+  AttnMapsP p = attn_standin<AttnMapsP>(q[0], q[1], q[2], q[3], 1, q[6]);
+  p.maps = g_standin_page; p.nd = q[4];
+  if (q[5] > 0) p.ldq = q[5];
+  p.kv_len = q[7] & 1 ? (const int*)g_standin_page : nullptr; p.accumulate = q[7] >> 1 & 1; p.q_prescaled = q[7] >> 2 & 1;
   AttnMapsPlan plan;
   const int rc = attn_plan_maps(p, plan);
   if (rc) return rc;
-  out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
+  attn_dispatch_out(out, plan.kb, plan.grid, plan.lds, plan.upw);
   return PEA_OK;
 }
 
@@ -3380,29 +3381,23 @@ int launch_attention_colsum(const AttnColsumP& p0, hipStream_t s) {
   AttnColsumPlan plan;
   const int rc = attn_plan_colsum(p, plan);
   if (rc) return rc;
-  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = 1; }
-  PROF_BEGIN(2, 2.0 * p.B * p.H * (double)p.Sq * p.Skv * 64,
-             2.0 * p.B * p.H * 64 * ((double)p.Sq * cdiv(p.Skv, 128) + p.Skv) + 4.0 * p.B * ((double)p.H * p.Sq + (double)plan.G * p.Skv), s);
-  const int lrc = p.q_prescaled ? launch_lds<attn_colsum_kernel<true>>(plan.grid, plan.lds, s, p)
-                                : launch_lds<attn_colsum_kernel<false>>(plan.grid, plan.lds, s, p);
-  PROF_END(s);
-  if (lrc) return lrc;
-  HIPCHK(hipGetLastError());
-  return PEA_OK;
+  return attn_feature_launch(p.B * p.H, p.Sq, p.Skv, 2.0 * p.B * p.H * (double)p.Sq * p.Skv * 64,
+                             2.0 * p.B * p.H * 64 * ((double)p.Sq * cdiv(p.Skv, 128) + p.Skv) +
+                                 4.0 * p.B * ((double)p.H * p.Sq + (double)plan.G * p.Skv), s, [&] {
+    return p.q_prescaled ? launch_lds<attn_colsum_kernel<true>>(plan.grid, plan.lds, s, p)
+                         : launch_lds<attn_colsum_kernel<false>>(plan.grid, plan.lds, s, p);
+  });
 }
-// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+// include/pea_hip.h
 extern "C" int pea_debug_attn_colsum_dispatch(const int* q, int* out) {
-  static float page[64];
-  AttnColsumP p = AttnColsumP();
-  p.Q = p.K = (const bf16*)page; p.part = page; p.lse = q[7] & 2 ? nullptr : page; p.scale = 0.125f;
-  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.Skv = q[3]; p.nd = q[4];
-  p.ldq = q[5] > 0 ? q[5] : 64 * p.H;
-  p.ldk = q[6] > 0 ? q[6] : 64 * p.H;
+  AttnColsumP p = attn_standin<AttnColsumP>(q[0], q[1], q[2], q[3], 1, q[6]);
+  p.part = g_standin_page; p.lse = q[7] & 2 ? nullptr : g_standin_page; p.nd = q[4];
+  if (q[5] > 0) p.ldq = q[5];
   p.q_prescaled = q[7] & 1;
   AttnColsumPlan plan;
   const int rc = attn_plan_colsum(p, plan);
   if (rc) return rc;
-  out[0] = plan.G; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.hpg;
+  attn_dispatch_out(out, plan.G, plan.grid, plan.lds, plan.hpg);
   return PEA_OK;
 }
 
@@ -3486,36 +3481,27 @@ int launch_attention_fwd_edit(const AttnEditP& p0, hipStream_t s) {
     rc = launch_attention_fwd(plan.plain, s);
     if (rc) return rc;
   }
-  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = 1; }
   const double pairs = (double)(p.B + plan.n_edited) * p.H * (double)p.Sq * p.Skv;     // a second score product per edited sample
-  PROF_BEGIN(2, 4.0 * pairs * 64 + 2.0 * plan.n_edited * p.H * (double)p.Sq * p.Skv * p.Skv,
-             2.0 * p.H * 64 * ((2.0 * p.B + plan.n_edited) * p.Sq + (2.0 * p.B + plan.n_edited) * p.Skv), s);
-  switch (plan.kb) {
-    case 1: rc = launch_lds<xattn_edit_fwd_kernel<1>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit); break;
-    case 2: rc = launch_lds<xattn_edit_fwd_kernel<2>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit); break;
-    default: rc = launch_lds<xattn_edit_fwd_kernel<3>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit); break;
-  }
-  PROF_END(s);
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  return PEA_OK;
+  return attn_feature_launch(p.B * p.H, p.Sq, p.Skv, 4.0 * pairs * 64 + 2.0 * plan.n_edited * p.H * (double)p.Sq * p.Skv * p.Skv,
+                             2.0 * p.H * 64 * ((2.0 * p.B + plan.n_edited) * p.Sq + (2.0 * p.B + plan.n_edited) * p.Skv), s, [&] {
+    switch (plan.kb) {
+      case 1: return launch_lds<xattn_edit_fwd_kernel<1>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit);
+      case 2: return launch_lds<xattn_edit_fwd_kernel<2>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit);
+      default: return launch_lds<xattn_edit_fwd_kernel<3>>(plan.grid, plan.lds, s, p, plan.upw, plan.upw_edit);
+    }
+  });
 }
-// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+// include/pea_hip.h
 extern "C" int pea_debug_attn_edit_dispatch(const int* q, int* out) {
-  static float page[64];
-  bf16* const any = (bf16*)page;
-  AttnEditP p = AttnEditP();
-  p.Q = p.K = p.V = any; p.O = any; p.scale = 0.125f;
-  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.Skv = q[3]; p.nd = q[4];
-  p.ldq = p.ldk = p.ldv = p.ldo = 64 * p.H;
-  if (q[5] > 0) p.ldk = q[5];
+  AttnEditP p = attn_standin<AttnEditP>(q[0], q[1], q[2], q[3], 1, q[5]);
+  p.nd = q[4];
   p.ldm = q[6] > 0 ? q[6] : (p.Skv + 7) / 8 * 8;
-  if (!(q[7] & 1)) { p.Mt = any; p.c = p.d = page; }
+  if (!(q[7] & 1)) { p.Mt = (const bf16*)g_standin_page; p.c = p.d = g_standin_page; }
   for (int b = 0; b < 32; ++b) p.src[b] = b < p.B ? q[8 + b] : -1;
   AttnEditPlan plan;
   const int rc = attn_plan_edit(p, plan);
   if (rc) return rc;
-  out[0] = plan.kb; out[1] = (int)plan.grid.x; out[2] = (int)plan.grid.y; out[3] = (int)plan.grid.z; out[4] = plan.lds; out[5] = plan.upw;
+  attn_dispatch_out(out, plan.kb, plan.grid, plan.lds, plan.upw);
   out[6] = plan.plain_first; out[7] = plan.upw_edit;
   return PEA_OK;
 }
@@ -3831,25 +3817,15 @@ int launch_attention_fwd_shared(const AttnSharedP& p0, hipStream_t s) {
     rc = launch_attention_fwd(plan.plain, s);
     if (rc) return rc;
   }
-  if (g_prof_on) { g_prof_tag[0] = p.B * p.H; g_prof_tag[1] = p.Sq; g_prof_tag[2] = p.Skv; g_prof_tag[3] = 1; }
   const double pairs = (double)(plan.n_tgt * 2 + (plan.plain_first ? 0 : p.B - plan.n_tgt)) * p.H * (double)p.Sq * p.Skv;
-  PROF_BEGIN(2, 4.0 * pairs * 64, 2.0 * p.H * 64 * 4.0 * (p.B + plan.n_tgt) * p.Sq, s);
-  rc = launch_lds<attn_shared_kernel>(plan.grid, plan.lds, s, p, plan.n_tgt_wg);
-  PROF_END(s);
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  return PEA_OK;
+  return attn_feature_launch(p.B * p.H, p.Sq, p.Skv, 4.0 * pairs * 64, 2.0 * p.H * 64 * 4.0 * (p.B + plan.n_tgt) * p.Sq, s,
+                             [&] { return launch_lds<attn_shared_kernel>(plan.grid, plan.lds, s, p, plan.n_tgt_wg); });
 }
-// include/pea_hip.h.  Operands are non-null, aligned stand-ins; nothing is launched
+// include/pea_hip.h (this one's out[] starts at the grid: it has no key-block count)
 extern "C" int pea_debug_attn_shared_dispatch(const int* q, int* out) {
-  static float page[64] __attribute__((aligned(16)));
-  bf16* const any = (bf16*)page;
-  AttnSharedP p = AttnSharedP();
-  p.Q = p.K = p.V = any; p.O = any; p.scale = 0.125f; p.share_scale = 1.f;
-  p.B = q[0]; p.H = q[1]; p.Sq = q[2]; p.Skv = q[3]; p.nd = q[4];
-  p.ldq = p.ldk = p.ldv = p.ldo = 64 * p.H;
-  if (q[5] > 0) p.ldk = q[5];
-  if (!(q[6] & 1)) p.coef = page;
+  AttnSharedP p = attn_standin<AttnSharedP>(q[0], q[1], q[2], q[3], 1, q[5]);
+  p.nd = q[4]; p.share_scale = 1.f;
+  if (!(q[6] & 1)) p.coef = g_standin_page;
   for (int b = 0; b < 32; ++b) p.ref[b] = b < p.B ? q[7 + b] : -1;
   AttnSharedPlan plan;
   const int rc = attn_plan_shared(p, plan);

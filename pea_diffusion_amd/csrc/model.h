@@ -1,8 +1,9 @@
 // Host runtime: the UNet as a static op tape (forward schedule + reverse data-gradient
 // schedule), the PEA adapter, and the fused KD training step.  No autograd, no tracing compiler:
 // the tape is built once per (config, batch, resolution, context length) and every launch is an
-// explicit kernel from pea_kernels.h.  graph.hip builds the tapes, tape.hip allocates, loads and runs them, adapter.hip and
-// trainer.hip hold the PEA adapter and the KD step; api_model.hip / vision.hip are the C ABI over them.
+// explicit kernel from pea_kernels.h.  graph.hip builds the tapes, tape.hip allocates, loads and runs them, attn_features.hip
+// holds the inference features of their attention ops (rules, launches, setters), adapter.hip and trainer.hip hold the PEA adapter
+// and the KD step; api_model.hip / vision.hip are the C ABI over them.
 #pragma once
 #include <string.h>
 
@@ -17,6 +18,14 @@
   do {                       \
     int rc__ = (x);          \
     if (rc__ != PEA_OK) return rc__; \
+  } while (0)
+
+#define NOTNULL(p, what)                         \
+  do {                                           \
+    if (!(p)) {                                  \
+      pea_set_error("%s: null handle", what);    \
+      return PEA_E_INVALID;                      \
+    }                                            \
   } while (0)
 
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -202,7 +211,7 @@ struct Tape {
   float* fu_buf = nullptr;
   size_t fu_coef_bytes = 0;
   int set_freeu(float s1, float s2, float b1, float b2, hipStream_t s);
-  // Image prompts (IP-Adapter, graph 0, inference only; api_model.hip: pea_unet_ip_*): up to four adapters ("sets"), each a
+  // Image prompts (IP-Adapter, graph 0, inference only; attn_features.hip: pea_unet_ip_*): up to four adapters ("sets"), each a
   // second K|V stack over its own n image tokens, columns laid out as the text stack's (t_kvall), so a cross-attention op finds
   // its image keys / values at its own bcol / ccol.  All sets share ONE packed image K|V buffer [B][total][cols], set j in rows
   // off .. off + n of every sample, so a layer hands the attention one K2 / V2 pair plus the table of sets (Tape::ip_attach: the
@@ -229,9 +238,10 @@ struct Tape {
       }
     }
   };
-  int ip_attach(const Op& o, AttnP& p);   // the image key sets of cross-attention op o, or none (tape.hip)
+  int ip_attach(const Op& o, AttnP& p);   // the image key sets of cross-attention op o, or none (attn_features.hip)
+  int ip_live_set() const;                // the first set whose tokens are set and not cleared, or -1
   IpState* ip = nullptr;
-  // Regional text prompts (graph 0, inference only; api_model.hip: pea_unet_set_prompt_regions): the context holds R prompts of
+  // Regional text prompts (graph 0, inference only; attn_features.hip: pea_unet_set_prompt_regions): the context holds R prompts of
   // L / R rows each, and while this is set every cross-attention on t_kvall is ONE launch_attention_fwd_regions with the weights
   // of its query count.  The tape, the plans, the arenas and the attention census do not change.  Outside the arenas.
   struct RegionState {
@@ -242,8 +252,7 @@ struct Tape {
     }
   };
   RegionState* regions = nullptr;
-  int regions_check(int R, bool need_weights) const;   // what a context must be to run R regions (tape.hip)
-  // Cross-attention heat maps (graph 0, inference only; api_model.hip: pea_unet_enable_attention_maps): while this is set, every
+  // Cross-attention heat maps (graph 0, inference only; attn_features.hip: pea_unet_enable_attention_maps): while this is set, every
   // selected cross-attention on t_kvall is followed by ONE launch_attention_maps over the same Q and K columns that adds the
   // layer's head-mean probabilities into the accumulator of its query count.  The ordinary launch, the tape, the plans, the arenas
   // and the attention census do not change.  Outside the arenas: release_acts keeps the accumulators.
@@ -257,7 +266,7 @@ struct Tape {
     }
   };
   MapState* maps = nullptr;
-  // Prompt-to-prompt editing (graph 0, inference only; api_model.hip: pea_unet_set_prompt_edit): the batch holds N prompts denoised
+  // Prompt-to-prompt editing (graph 0, inference only; attn_features.hip: pea_unet_set_prompt_edit): the batch holds N prompts denoised
   // from the same latents, src[b] >= 0 names the unedited source of sample b.  While this is set, a cross-attention on t_kvall is
   // ONE launch_attention_fwd_edit at a step whose tables do anything (cd_live), the plain launch otherwise; a self-attention with
   // at most self_max_tokens queries, while step < self_until, is its ordinary launch and one B = 1 launch per edited sample that
@@ -275,8 +284,7 @@ struct Tape {
     }
   };
   EditState* edit = nullptr;
-  int edit_check(bool forward) const;          // what a context must be to run an edit (tape.hip)
-  // StyleAligned generation (graph 0, inference only; api_model.hip: pea_unet_set_style_aligned): ref[b] >= 0 names the style
+  // StyleAligned generation (graph 0, inference only; attn_features.hip: pea_unet_set_style_aligned): ref[b] >= 0 names the style
   // reference of sample b.  While this is set, a self-attention op (is_self_attn) whose layer is switched on is ONE
   // launch_attn_adain_coef over its Q and K columns and ONE launch_attention_fwd_shared instead of launch_attention_fwd.  The
   // tape, the plans, the arenas and the attention census do not change.  Outside the arenas: release_acts keeps the buffers.
@@ -295,8 +303,7 @@ struct Tape {
   };
   StyleState* style = nullptr;
   bool is_self_attn(const Op& o) const { return graph == 0 && o.kind == OP_ATTN && o.b != t_kvall && !o.mask && o.p1 == o.p2; }
-  int style_check(bool forward) const;         // what a context must be to share self-attention (tape.hip)
-  // Self-attention guidance (graph 0, inference only; api_model.hip: pea_unet_enable_sag): while this is set, the ordinary launch
+  // Self-attention guidance (graph 0, inference only; attn_features.hip: pea_unet_enable_sag): while this is set, the ordinary launch
   // of ONE self-attention op (index `op` in `ops`) is handed the state's own lse buffer and is followed by ONE
   // launch_attention_colsum over samples first .. first + n of its Q, K and lse.  The ordinary launch's decision and its O do not
   // change (the forward kernels store lse beside O; the plan does not read the pointer).  The tape, the plans, the arenas and the
@@ -311,7 +318,11 @@ struct Tape {
     }
   };
   SagState* sag = nullptr;
-  int sag_check(bool forward) const;           // what a context must be to capture column sums (tape.hip)
+  // The features above on the host (attn_features.hip): what a context must be for each of them (AF_* bits of `which`), judged by
+  // its setter and again by forward() before the first launch; and the launches of attention op `oi` with them in place
+  enum { AF_IP = 1, AF_REGIONS = 2, AF_MAPS = 4, AF_EDIT = 8, AF_STYLE = 16, AF_SAG = 32 };
+  int attn_rules(unsigned which, bool forward, int arg = 0) const;
+  int attn_forward(size_t oi, hipStream_t s);
   std::deque<WSlot> slots;
   std::map<std::string, int> slot_by_name;
   std::deque<FusedMat> fused;

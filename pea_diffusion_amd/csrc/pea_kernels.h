@@ -227,6 +227,31 @@ struct AttnColsumP {
 };
 int attention_colsum_groups(int B, int H, int Sq, int Skv);      // G, or PEA_E_SHAPE for an empty problem
 int launch_attention_colsum(const AttnColsumP& p, hipStream_t s);
+// the plain attention over a feature's operands: what its unedited / plain samples compute, on the host and on the device
+template <class P>
+__host__ __device__ static inline AttnP attn_plain_p(const P& p) {
+  AttnP a = AttnP();
+  a.Q = p.Q; a.K = p.K; a.V = p.V; a.ldq = p.ldq; a.ldk = p.ldk; a.ldv = p.ldv; a.O = p.O; a.ldo = p.ldo;
+  a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Skv = p.Skv; a.scale = p.scale; a.nd = 1; a.q_prescaled = p.q_prescaled;
+  return a;
+}
+// The reverse, host only: feature struct F, zeroed, with every operand it shares with the plain attention `a` -- Q / K and their
+// leading dimensions, B, H, Sq, scale, q_prescaled, nd, and V / O (AttnMapsP and AttnColsumP have none) and Skv (AttnRegionsP has
+// none) where F has them.  A fill site then names only what its feature adds.  F = AttnP: `a` itself.
+template <class F> static inline auto attn_fill_vo(F& f, const AttnP& a, int) -> decltype((void)f.V) { f.V = a.V; f.ldv = a.ldv; f.O = a.O; f.ldo = a.ldo; }
+template <class F> static inline void attn_fill_vo(F&, const AttnP&, long) {}
+template <class F> static inline auto attn_fill_skv(F& f, const AttnP& a, int) -> decltype((void)f.Skv) { f.Skv = a.Skv; }
+template <class F> static inline void attn_fill_skv(F&, const AttnP&, long) {}
+template <class F>
+static inline F attn_feature_p(const AttnP& a) {
+  F f = F();
+  f.Q = a.Q; f.K = a.K; f.ldq = a.ldq; f.ldk = a.ldk; f.B = a.B; f.H = a.H; f.Sq = a.Sq;
+  f.scale = a.scale; f.q_prescaled = a.q_prescaled; f.nd = a.nd;
+  attn_fill_vo(f, a, 0);
+  attn_fill_skv(f, a, 0);
+  return f;
+}
+template <> inline AttnP attn_feature_p<AttnP>(const AttnP& a) { return a; }
 
 // ---------------------------------------------------------------- elementwise.hip
 int launch_geglu_fwd(const bf16* hg, bf16* y, long long rows, int inner, hipStream_t s);   // hg [rows][2*inner]

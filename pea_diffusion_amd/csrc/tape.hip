@@ -493,171 +493,6 @@ static int geglu_stash_form(const Op& o) {
   return (o.p3 == 3 && o.c >= 0 && o.p1 == 0) ? 1 : 0;
 }
 
-// Image prompts of cross-attention op o.  The weight of set j in this layer is scale_j * layer_scale_j[layer], read here, at
-// launch.  A set that is not live or weighs 0 here is dropped: the launch takes the run of rows from the first to the last
-// remaining set (AttnP::k2_brows keeps the packed buffer's batch stride), so one remaining set without a mask is the one-set
-// launch of a context that holds that adapter alone, bit for bit, and none is the plain attention.  A dropped set BETWEEN two
-// remaining ones stays in the run with weight 0 -- exact zeros in P; its rows are zero or an earlier image's, finite either way.
-int Tape::ip_attach(const Op& o, AttnP& p) {
-  IpState& st = *ip;
-  const auto lay = st.layer_of_col.find(o.bcol);
-  float w[4] = {0.f, 0.f, 0.f, 0.f};
-  int first = -1, last = -1;
-  for (int j = 0; j < st.nsets; ++j) {
-    const IpSet& e = st.set[j];
-    if (!e.live) continue;
-    w[j] = e.scale * (e.layer_scale.empty() || lay == st.layer_of_col.end() ? 1.f : e.layer_scale[lay->second]);
-    if (w[j] == 0.f) continue;
-    if (first < 0) first = j;
-    last = j;
-  }
-  if (first < 0) return PEA_OK;
-  const int row0 = st.set[first].off;
-  p.K2 = st.kv + (size_t)row0 * st.cols + o.bcol; p.V2 = st.kv + (size_t)row0 * st.cols + o.ccol; p.ldk2 = p.ldv2 = st.cols;
-  p.Skv2 = st.set[last].off + st.set[last].n - row0; p.k2_brows = st.total;
-  if (first == last && st.set[first].mask.empty()) {
-    p.scale2 = w[first];
-    return PEA_OK;
-  }
-  p.nset = last - first + 1;
-  for (int j = first; j <= last; ++j) {
-    const IpSet& e = st.set[j];
-    const int i = j - first;
-    p.set_end[i] = e.off + e.n - row0; p.set_w[i] = w[j];
-    if (w[j] == 0.f || e.mask.empty()) continue;
-    const auto m = e.mask.find(o.p1);
-    if (m == e.mask.end()) {                                       // ip_masks_complete has passed: not reached from forward()
-      pea_set_error("unet: image prompt %d has masks, but none for the %d queries of this layer (pea_unet_ip_set_mask)", j, o.p1);
-      return PEA_E_STATE;
-    }
-    p.set_mask[i] = m->second.first; p.set_mstride[i] = m->second.second == 1 ? 0 : o.p1;
-  }
-  return PEA_OK;
-}
-// a live set with a mask for some of the context's cross-attention query counts needs one for each: a layer without would
-// silently run with a mask of 1.  Checked before the first launch of a forward.
-static int ip_masks_complete(const Tape& u) {
-  if (!u.ip) return PEA_OK;
-  for (int j = 0; j < u.ip->nsets; ++j) {
-    const Tape::IpSet& e = u.ip->set[j];
-    if (!e.live || e.mask.empty()) continue;
-    for (const Op& o : u.ops)
-      if (o.kind == OP_ATTN && o.b == u.t_kvall && !e.mask.count(o.p1)) {
-        pea_set_error("pea_unet_forward: image prompt %d has a mask for %d queries but none for the layers with %d queries; "
-                      "pea_unet_ip_set_mask needs every count of pea_unet_ip_query_counts", j, e.mask.begin()->first, o.p1);
-        return PEA_E_STATE;
-      }
-  }
-  return PEA_OK;
-}
-
-// Regional text prompts: what the context must be.  Checked when weights are set and again (need_weights) before the first
-// launch of a forward: image prompts or per-sample context lengths may have arrived in between, and a query count without
-// weights would otherwise run on another layer's table.
-int Tape::regions_check(int R, bool need_weights) const {
-  const char* const who = need_weights ? "pea_unet_forward" : "pea_unet_set_prompt_regions";
-  if (needs_grad) {
-    pea_set_error("%s: regional prompts are an inference feature (no backward through them); this context was created with PEA_UNET_GRAD", who);
-    return PEA_E_STATE;
-  }
-  if (cross_kvlen) { pea_set_error("%s: regional prompts cannot be combined with per-sample context lengths", who); return PEA_E_STATE; }
-  if (ip)
-    for (int j = 0; j < ip->nsets; ++j)
-      if (ip->set[j].live) {
-        pea_set_error("%s: regional prompts cannot be combined with live image prompts (set %d; pea_unet_ip_clear)", who, j);
-        return PEA_E_STATE;
-      }
-  SHAPECHK(R >= 1 && R <= 4, "%s: 1..4 regions (R=%d)", who, R);
-  SHAPECHK(L % R == 0 && L / R <= 96, "%s: a context of %d rows is no %d prompts of at most 96 rows", who, L, R);
-  for (const Op& o : ops) {
-    if (o.kind != OP_ATTN || o.b != t_kvall) continue;
-    SHAPECHK(o.p3 == 1 && o.p2 == L, "%s: regional prompts need head_dim 64 cross-attention over the whole context (nd=%d, %d keys)", who, o.p3, o.p2);
-    if (need_weights && !regions->w.count(o.p1)) {
-      pea_set_error("%s: regional prompts have no weights for the layers with %d queries; pea_unet_set_prompt_regions needs every "
-                    "count of pea_unet_ip_query_counts", who, o.p1);
-      return PEA_E_STATE;
-    }
-  }
-  return PEA_OK;
-}
-
-// Prompt-to-prompt editing: what the context must be.  Checked when the tables are set and again (forward) before the first launch
-// of a forward: image prompts, regions, map capture or per-sample context lengths may have arrived in between.
-int Tape::edit_check(bool forward) const {
-  const char* const who = forward ? "pea_unet_forward" : "pea_unet_set_prompt_edit";
-  if (needs_grad) {
-    pea_set_error("%s: prompt editing is an inference feature (no backward through it); this context was created with PEA_UNET_GRAD", who);
-    return PEA_E_STATE;
-  }
-  if (cross_kvlen) { pea_set_error("%s: prompt editing cannot be combined with per-sample context lengths", who); return PEA_E_STATE; }
-  if (ip)
-    for (int j = 0; j < ip->nsets; ++j)
-      if (ip->set[j].live) {
-        pea_set_error("%s: prompt editing cannot be combined with live image prompts (set %d; pea_unet_ip_clear)", who, j);
-        return PEA_E_STATE;
-      }
-  if (regions) { pea_set_error("%s: prompt editing cannot be combined with prompt regions (pea_unet_clear_prompt_regions)", who); return PEA_E_STATE; }
-  if (maps) { pea_set_error("%s: prompt editing cannot be combined with attention-map capture (pea_unet_disable_attention_maps)", who); return PEA_E_STATE; }
-  SHAPECHK(L >= 1 && L <= 96, "%s: prompt editing takes a context of 1..96 rows (L=%d)", who, L);
-  SHAPECHK(B <= 32, "%s: prompt editing takes a batch of at most 32 (B=%d)", who, B);
-  for (const Op& o : ops) {
-    if (o.kind != OP_ATTN || o.b != t_kvall) continue;
-    SHAPECHK(o.p3 == 1 && o.p2 == L, "%s: prompt editing needs head_dim 64 cross-attention over the whole context (nd=%d, %d keys)", who, o.p3, o.p2);
-  }
-  if (forward && (edit->step < 0 || edit->step >= edit->T)) {
-    pea_set_error("%s: prompt-edit step %d is outside 0..%d (pea_unet_set_prompt_edit_step)", who, edit->step, edit->T - 1);
-    return PEA_E_STATE;
-  }
-  return PEA_OK;
-}
-
-// StyleAligned sharing: what the context must be.  Checked when the state is set and again (forward) before the first launch of a
-// forward: a prompt edit may have arrived in between.  Image prompts, regions, heat maps, FreeU and ControlNet residuals are
-// welcome: none of them sees a self-attention launch.
-int Tape::style_check(bool forward) const {
-  const char* const who = forward ? "pea_unet_forward" : "pea_unet_set_style_aligned";
-  if (needs_grad) {
-    pea_set_error("%s: StyleAligned sharing is an inference feature (no backward through it); this context was created with PEA_UNET_GRAD", who);
-    return PEA_E_STATE;
-  }
-  if (edit) {
-    pea_set_error("%s: StyleAligned sharing cannot be combined with prompt editing, whose self-attention rule rewrites the same outputs "
-                  "(pea_unet_clear_prompt_edit or pea_unet_clear_style_aligned)", who);
-    return PEA_E_STATE;
-  }
-  SHAPECHK(B <= 32, "%s: StyleAligned sharing takes a batch of at most 32 (B=%d)", who, B);
-  for (const Op& o : ops) {
-    if (!is_self_attn(o)) continue;
-    SHAPECHK(o.p3 == 1 && o.p1 >= 2, "%s: StyleAligned sharing needs head_dim 64 self-attention over at least 2 tokens (nd=%d, %d tokens)", who, o.p3, o.p1);
-  }
-  return PEA_OK;
-}
-
-// Self-attention guidance capture: what the context must be.  Checked when the state is set and again (forward) before the first
-// launch of a forward: a prompt edit or a StyleAligned state may have arrived in between.  Both rewrite or replace the chosen
-// launch.  Image prompts, regions, heat maps, FreeU and ControlNet residuals are welcome.
-int Tape::sag_check(bool forward) const {
-  const char* const who = forward ? "pea_unet_forward" : "pea_unet_enable_sag";
-  if (needs_grad) {
-    pea_set_error("%s: self-attention guidance is an inference feature; this context was created with PEA_UNET_GRAD", who);
-    return PEA_E_STATE;
-  }
-  if (edit) {
-    pea_set_error("%s: self-attention guidance cannot be combined with prompt editing, whose self-attention rule rewrites the captured "
-                  "launch (pea_unet_clear_prompt_edit or pea_unet_disable_sag)", who);
-    return PEA_E_STATE;
-  }
-  if (sag && style && style->n_targets) {
-    const auto it = style->layer_of_op.find(sag->op);
-    if (it != style->layer_of_op.end() && style->on[it->second]) {
-      pea_set_error("%s: self-attention layer %d is shared by StyleAligned, which replaces the launch self-attention guidance captures "
-                    "(switch that layer off in pea_unet_set_style_aligned, or pea_unet_disable_sag)", who, sag->layer);
-      return PEA_E_STATE;
-    }
-  }
-  return PEA_OK;
-}
-
 int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype, const void* text, int text_dtype,
                   const float* time_ids, float* eps, hipStream_t s) {
   std::string miss;
@@ -665,16 +500,8 @@ int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype
     pea_set_error("unet: weight '%s' was never loaded", miss.c_str());
     return PEA_E_STATE;
   }
-  RC(ip_masks_complete(*this));
-  if (regions) RC(regions_check(regions->R, true));
-  if (maps && regions) {
-    pea_set_error("pea_unet_forward: cross-attention heat maps cannot be combined with regional prompts (a context of several prompts has "
-                  "a softmax per region; pea_unet_disable_attention_maps or pea_unet_clear_prompt_regions)");
-    return PEA_E_STATE;
-  }
-  if (edit) RC(edit_check(true));
-  if (style) RC(style_check(true));
-  if (sag) RC(sag_check(true));
+  RC(attn_rules((ip ? AF_IP : 0) | (regions ? AF_REGIONS : 0) | (maps ? AF_MAPS : 0) | (edit ? AF_EDIT : 0) | (style ? AF_STYLE : 0) |
+                    (sag ? AF_SAG : 0), true));
   RC(ensure_acts());
   RC(ensure_folded(s));
   x_in = x; t_in = t; tid_in = time_ids; eps_out = eps;
@@ -881,84 +708,9 @@ int Tape::exec_ops(size_t begin, size_t end, bool skip_cached, hipStream_t s) {
                                 s));
         break;
       }
-      case OP_ATTN: {
-        AttnP p; memset(&p, 0, sizeof(p));
-        p.Q = tn[o.a].d + o.acol; p.ldq = tn[o.a].cols; p.K = tn[o.b].d + o.bcol; p.ldk = tn[o.b].cols;
-        p.V = tn[o.c].d + o.ccol; p.ldv = tn[o.c].cols; p.O = tn[o.out].d; p.ldo = tn[o.out].cols; p.lse = o.aux;
-        p.B = B; p.H = o.p0; p.Sq = o.p1; p.Skv = o.p2; p.scale = o.f0; p.nd = o.p3;
-        p.causal = o.mask & 1; p.kv_len = (o.mask & 2) ? kvlen : nullptr;
-        p.q_prescaled = o.pre;
-        if (o.mask & 4) p.bias = rel_bias;
-        if (cross_kvlen && o.b == t_kvall) p.kv_len = cross_kvlen;
-        if (regions && o.b == t_kvall) {                            // regional prompts: R softmaxes over the R runs of context rows
-          const auto& wt = regions->w.find(o.p1)->second;           // (regions_check has passed: the count is there)
-          AttnRegionsP r = AttnRegionsP();
-          r.Q = p.Q; r.ldq = p.ldq; r.K = p.K; r.ldk = p.ldk; r.V = p.V; r.ldv = p.ldv; r.O = p.O; r.ldo = p.ldo;
-          r.B = B; r.H = o.p0; r.Sq = o.p1; r.R = regions->R; r.Lr = o.p2 / regions->R; r.w = wt.first; r.Bw = wt.second;
-          r.scale = o.f0; r.q_prescaled = o.pre; r.nd = o.p3;
-          RC(launch_attention_fwd_regions(r, s));
-          break;
-        }
-        if (edit && o.b == t_kvall && edit->cd_live[edit->step]) {   // prompt editing: the source's softmax mixed into the edited samples'
-          AttnEditP e = AttnEditP();                                  // (edit_check has passed; a step whose tables do nothing runs the plain launch)
-          e.Q = p.Q; e.ldq = p.ldq; e.K = p.K; e.ldk = p.ldk; e.V = p.V; e.ldv = p.ldv; e.O = p.O; e.ldo = p.ldo;
-          e.B = B; e.H = o.p0; e.Sq = o.p1; e.Skv = o.p2; e.scale = o.f0; e.q_prescaled = o.pre; e.nd = o.p3;
-          e.Mt = edit->Mt; e.ldm = edit->ldm;
-          e.c = edit->cd + (size_t)edit->step * 2 * B * L; e.d = e.c + (size_t)B * L;
-          memcpy(e.src, edit->src, sizeof(e.src));
-          RC(launch_attention_fwd_edit(e, s));
-          break;
-        }
-        if (ip && o.b == t_kvall) RC(ip_attach(o, p));               // image prompts: the layer's own columns of the image K|V
-        if (style && style->n_targets && is_self_attn(o) && style->on[style->layer_of_op.find((int)oi)->second]) {
-          // StyleAligned: the targets' AdaIN coefficients from this layer's Q and K columns, then one launch in which they attend
-          // to their reference's keys and values as well (style_check has passed; plain samples keep their bits)
-          RC(launch_attn_adain_coef(p.Q, p.ldq, p.K, p.ldk, B, o.p0, o.p1, style->ref, o.f0, o.pre, style->adain_q, style->adain_k,
-                                    style->coef, style->scratch, s));
-          AttnSharedP e = AttnSharedP();
-          e.Q = p.Q; e.ldq = p.ldq; e.K = p.K; e.ldk = p.ldk; e.V = p.V; e.ldv = p.ldv; e.O = p.O; e.ldo = p.ldo;
-          e.B = B; e.H = o.p0; e.Sq = o.p1; e.Skv = o.p2; e.scale = o.f0; e.q_prescaled = o.pre; e.nd = o.p3;
-          e.coef = style->coef; e.share_scale = style->share_scale; e.share_shift = style->share_shift;
-          memcpy(e.ref, style->ref, sizeof(e.ref));
-          RC(launch_attention_fwd_shared(e, s));
-          break;
-        }
-        const bool sag_here = sag && sag->op == (int)oi;           // self-attention guidance: this launch also stores its lse
-        if (sag_here) p.lse = sag->lse;
-        RC(launch_attention_fwd(p, s));
-        if (sag_here) {                                             // ... and its column sums follow (sag_check has passed)
-          AttnColsumP c = AttnColsumP();
-          c.Q = p.Q + (size_t)sag->first * p.Sq * p.ldq; c.ldq = p.ldq; c.K = p.K + (size_t)sag->first * p.Skv * p.ldk; c.ldk = p.ldk;
-          c.lse = sag->lse + (size_t)sag->first * o.p0 * o.p1; c.part = sag->part;
-          c.B = sag->n; c.H = o.p0; c.Sq = o.p1; c.Skv = o.p2; c.scale = o.f0; c.q_prescaled = o.pre; c.nd = o.p3;
-          RC(launch_attention_colsum(c, s));
-        }
-        if (edit && graph == 0 && o.b != t_kvall && !o.mask && o.p1 == o.p2 && o.p1 <= edit->self_max_tokens && edit->step < edit->self_until) {
-          // prompt editing, self-attention: O[b] = softmax(Q[s] K[s]^T) V[b], one B = 1 launch per edited sample behind the
-          // ordinary one (unedited samples keep their bits by construction)
-          for (int b = 0; b < B; ++b) {
-            const int sb = edit->src[b];
-            if (sb < 0) continue;
-            AttnP e = p;
-            e.B = 1; e.lse = nullptr;
-            e.Q = p.Q + (size_t)sb * p.Sq * p.ldq; e.K = p.K + (size_t)sb * p.Skv * p.ldk;
-            e.V = p.V + (size_t)b * p.Skv * p.ldv; e.O = p.O + (size_t)b * p.Sq * p.ldo;
-            RC(launch_attention_fwd(e, s));
-          }
-        }
-        if (maps && o.b == t_kvall) {                               // heat maps: the text softmax's head mean, added to the level's sum
-          const auto lay = maps->layer_of_col.find(o.bcol);
-          if (lay != maps->layer_of_col.end() && maps->on[lay->second]) {
-            AttnMapsP m = AttnMapsP();
-            m.Q = p.Q; m.ldq = p.ldq; m.K = p.K; m.ldk = p.ldk; m.maps = maps->acc.find(o.p1)->second;
-            m.B = B; m.H = o.p0; m.Sq = o.p1; m.Skv = o.p2; m.scale = o.f0; m.q_prescaled = o.pre; m.nd = o.p3;
-            m.kv_len = cross_kvlen; m.accumulate = 1;
-            RC(launch_attention_maps(m, s));
-            ++maps->count[o.p1];
-          }
-        }
+      case OP_ATTN:                     // the plain launch, or what the inference features make of it (attn_features.hip)
+        RC(attn_forward(oi, s));
         break;
-      }
       case OP_ATTN_FEWQ: {             // the latents over the image rows' keys and their own, one softmax, both read in place
         AttnP p; memset(&p, 0, sizeof(p));
         const Tn &a = tn[o.a], &k = tn[o.b], &v = tn[o.c];
