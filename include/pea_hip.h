@@ -1031,6 +1031,46 @@ int pea_unet_enable_sag(void* unet, int layer, int first_sample, int n_samples);
 int pea_unet_disable_sag(void* unet);
 int pea_unet_sag_colsum(void* unet, float** part, int* G, int* S);
 
+/* ---- perturbed-attention guidance (Ahn et al. 2024, "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance") and
+ * smoothed-energy guidance (Hong 2024, "Smoothed Energy Guidance: Guiding Diffusion Models with Reduced Energy Curvature of
+ * Attention"): one more sample per prompt rides in the SAME UNet call, last in the batch, and in chosen self-attention layers its
+ * attention is perturbed; s (eps_text - eps_perturbed) is added to the guidance.  Restatements from the papers and the authors'
+ * public code (unpinned).
+ * pea_op_query_blur: Q bf16 rows [n][h * w] of pitch ld, the C columns from col0 (C % 64 == 0, col0 % 8 == 0) read as n grids of
+ * h x w tokens and blurred per channel IN PLACE: Q~ = Mh . Q . Mw^T with dense device fp32 Mh [h][h], Mw [w][w] (pag.blur_matrix
+ * folds taps, size clamp, reflect padding and the infinite-sigma mean into them).  One launch; a workgroup owns 8 channels of one
+ * sample and holds their whole grid in LDS as fp32, both passes accumulate in fp32 and only the store rounds.  Columns outside
+ * [col0, col0 + C) and rows outside the n samples are not touched.  h, w <= 64 (pea_op_query_blur_lds_bytes(h, w): the LDS the
+ * launch takes, 133120 of 163840 bytes at 64 x 64, or PEA_E_SHAPE for a grid it cannot hold): larger grids are refused, not
+ * served by another path.  PEA_E_SHAPE before any launch: a null operand, C % 64 != 0, a pitch or offset that is no multiple of 8
+ * or does not hold the columns, n > 65535.
+ * pea_op_attn_identity: the identity "attention" O = V: rows x C bf16 from V (pitch ldv, from column col0) to O (pitch ldo),
+ * 16 bytes per lane (the pitched copy the tape's concats use).
+ * pea_op_cfg_pag_combine: cfg != 0: eps fp32 [3B][per] = [u | t | p], out[B][per] = u + g (t - u) + s (t - p), then, when
+ * guidance_rescale > 0, rescale_noise_cfg against t as pea_op_cfg_combine does it (its reduction, its workspace:
+ * pea_op_cfg_combine_workspace_bytes(B)); s = 0 gives pea_op_cfg_combine's bits on the first 2B samples at any rescale.  cfg == 0:
+ * eps [2B][per] = [t | p], out = t + s (t - p); guidance_rescale is not applied. */
+int pea_op_query_blur(void* Q, int ld, int col0, int n, int h, int w, int C, const float* Mh, const float* Mw, void* stream);
+int pea_op_query_blur_lds_bytes(int h, int w);
+int pea_op_attn_identity(const void* V, int ldv, int col0, void* O, int ldo, long long rows, int C, void* stream);
+int pea_op_cfg_pag_combine(const float* eps, float* out, int B, long long per, int cfg, float guidance_scale, float pag_scale,
+                           float guidance_rescale, void* workspace, void* stream);
+/* The perturbation in a UNet context (graph 0, inference), a runtime state like the others: the tape, the plans and the arenas do
+ * not change.  The samples first_sample .. B - 1 are the perturbed ones (a non-empty suffix that leaves plain samples in front).
+ * layer_on: null = every self-attention layer, else n_layers switches in the order of pea_unet_num_self_attention_layers.  mode 1
+ * (identity, PAG): in a switched-on layer O[b] = V[b] for the perturbed samples -- the ordinary launch runs over the plain
+ * samples alone and ONE pitched copy follows.  mode 2 (query blur, SEG): ONE pea_op_query_blur over the perturbed samples' Q
+ * columns, in place, then the ordinary launch over all samples; the grids come as n_grids (<= 16) sides grid_h[i] x grid_w[i]
+ * and `tables`, HOST fp32: per grid Mh [h][h] then Mw [w][w], back to back; every switched-on layer's query count needs its grid
+ * (a forward without refuses).  The plain samples keep the bits they have without the feature.  Refused (PEA_E_STATE /
+ * PEA_E_SHAPE; by a forward too, before its first launch): a PEA_UNET_GRAD context, a switched-on layer whose head_dim is not
+ * 64, an empty or whole-batch suffix, live prompt editing (in both orders), StyleAligned switched on for a perturbed layer,
+ * self-attention guidance capturing one.  Image prompts, regions, heat maps, FreeU and ControlNet residuals combine freely.
+ * pea_unet_clear_attn_perturb frees the tables; after it a forward gives the bits it gave before. */
+int pea_unet_set_attn_perturb(void* unet, int mode, int first_sample, const float* layer_on, int n_layers, int n_grids,
+                              const int* grid_h, const int* grid_w, const float* tables, void* stream);
+int pea_unet_clear_attn_perturb(void* unet);
+
 #ifdef __cplusplus
 }
 #endif

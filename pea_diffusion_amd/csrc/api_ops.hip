@@ -477,6 +477,27 @@ int pea_op_cfg_sag_combine(const float* eps, const float* eps_deg, float* out, i
                            float sag_scale, void* stream) {
   return launch_cfg_sag_combine(eps, eps_deg, out, B, per, cfg, guidance_scale, sag_scale, (hipStream_t)stream);
 }
+// ---- perturbed-attention / smoothed-energy guidance (elementwise.hip: the query blur and the pitched copy; sampler.hip: the combine)
+int pea_op_query_blur(void* Q, int ld, int col0, int n, int h, int w, int C, const float* Mh, const float* Mw, void* stream) {
+  SHAPECHK(Q, "query_blur: null operand");
+  SHAPECHK(col0 >= 0 && col0 % 8 == 0 && C > 0 && col0 <= ld - C, "query_blur: columns %d .. %d of rows of %d (an offset that is a multiple of 8, inside the row)",
+           col0, col0 + C - 1, ld);
+  return launch_query_blur((bf16*)Q + col0, ld, n, h, w, C, Mh, Mw, (hipStream_t)stream);
+}
+int pea_op_query_blur_lds_bytes(int h, int w) {
+  return h > 0 && w > 0 && h <= QUERY_BLUR_MAX_SIDE && w <= QUERY_BLUR_MAX_SIDE ? (int)query_blur_lds_bytes(h, w) : PEA_E_SHAPE;
+}
+int pea_op_attn_identity(const void* V, int ldv, int col0, void* O, int ldo, long long rows, int C, void* stream) {
+  SHAPECHK(V && O, "attn_identity: null operand");
+  SHAPECHK(rows > 0 && C > 0 && C % 8 == 0 && col0 >= 0 && col0 % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && col0 <= ldv - C && ldo >= C,
+           "attn_identity: %lld rows, columns %d .. %d of %d -> %d of %d (multiples of 8, inside the rows)", rows, col0, col0 + C - 1, ldv, C, ldo);
+  SHAPECHK((((uintptr_t)V | (uintptr_t)O) & 15) == 0, "attn_identity: V and O are 16-byte aligned");
+  return launch_copy2d((const bf16*)V + col0, ldv, (bf16*)O, ldo, rows, C, 0, (hipStream_t)stream);
+}
+int pea_op_cfg_pag_combine(const float* eps, float* out, int B, long long per, int cfg, float guidance_scale, float pag_scale,
+                           float guidance_rescale, void* workspace, void* stream) {
+  return launch_cfg_pag_combine(eps, out, B, per, cfg, guidance_scale, pag_scale, guidance_rescale, workspace, (hipStream_t)stream);
+}
 // ---- LoRA weight composition (lora.hip)
 int pea_op_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank, float scale,
                         void* stream) {

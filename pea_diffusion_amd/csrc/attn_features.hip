@@ -1,5 +1,6 @@
 // The inference features that hang off the UNet's attention ops -- image prompts (IP-Adapter), regional prompts, cross-attention
-// heat maps, prompt-to-prompt editing, StyleAligned sharing, self-attention guidance -- on the host: a feature is its state struct
+// heat maps, prompt-to-prompt editing, StyleAligned sharing, self-attention guidance, perturbed-attention / smoothed-energy
+// guidance -- on the host: a feature is its state struct
 // (model.h), its rules (Tape::attn_rules, below), its setters (the C ABI at the end of this file; include/pea_hip.h) and its place
 // among the launches of an attention op (Tape::attn_forward).  No device code here: the kernels and their launchers are
 // attention.hip's.
@@ -38,7 +39,7 @@ int Tape::ip_live_set() const {
 // not exist yet.  forward true: before the first launch of a forward, every feature that is set, in this order -- features,
 // per-sample context lengths or image tokens may have arrived since the setter looked.  A rule fires where it always did: at
 // both times unless its line says otherwise.  Welcome everywhere, since none of them sees the launches in question: FreeU,
-// ControlNet residuals, and for the self-attention features (StyleAligned, guidance) image prompts, regions and heat maps.
+// ControlNet residuals, and for the self-attention features (StyleAligned, both guidances) image prompts, regions and heat maps.
 int Tape::attn_rules(unsigned which, bool forward, int arg) const {
   const int live = ip_live_set();
   // the text cross-attention the regions, edit and maps kernels are built for: head_dim 64 over the whole context
@@ -117,6 +118,9 @@ int Tape::attn_rules(unsigned which, bool forward, int arg) const {
     RC(xattn_whole_context("%s: prompt editing needs head_dim 64 cross-attention over the whole context (nd=%d, %d keys)", who));
     if (forward && (edit->step < 0 || edit->step >= edit->T))        // forward only
       REFUSE(PEA_E_STATE, "%s: prompt-edit step %d is outside 0..%d (pea_unet_set_prompt_edit_step)", who, edit->step, edit->T - 1);
+    if (perturb)
+      REFUSE(PEA_E_STATE, "%s: prompt editing cannot be combined with perturbed-attention guidance: its self-attention rule rewrites the "
+             "outputs of the perturbed samples (pea_unet_clear_attn_perturb)", who);
   }
   if (which & AF_STYLE) {
     const char* const who = forward ? "pea_unet_forward" : "pea_unet_set_style_aligned";
@@ -142,6 +146,36 @@ int Tape::attn_rules(unsigned which, bool forward, int arg) const {
       if (it != style->layer_of_op.end() && style->on[it->second])
         REFUSE(PEA_E_STATE, "%s: self-attention layer %d is shared by StyleAligned, which replaces the launch self-attention guidance captures "
                "(switch that layer off in pea_unet_set_style_aligned, or pea_unet_disable_sag)", who, sag->layer);
+    }
+  }
+  if (which & AF_PERTURB) {                                          // (at set time the setter has hung the state it wants judged)
+    const char* const who = forward ? "pea_unet_forward" : "pea_unet_set_attn_perturb";
+    const PerturbState& pt = *perturb;
+    if (needs_grad)
+      REFUSE(PEA_E_STATE, "%s: perturbed-attention guidance is an inference feature (the query blur overwrites Q, which a backward "
+             "would read); this context was created with PEA_UNET_GRAD", who);
+    SHAPECHK(pt.first >= 1 && pt.first < B, "%s: perturbed samples %d .. %d of a batch of %d (a non-empty suffix that leaves plain "
+             "samples in front)", who, pt.first, B - 1, B);
+    if (edit)
+      REFUSE(PEA_E_STATE, "%s: perturbed-attention guidance cannot be combined with prompt editing, whose self-attention rule rewrites "
+             "the same outputs (pea_unet_clear_prompt_edit or pea_unet_clear_attn_perturb)", who);
+    for (size_t i = 0; i < ops.size(); ++i) {
+      const Op& o = ops[i];
+      if (!is_self_attn(o)) continue;
+      const int layer = pt.layer_of_op.find((int)i)->second;
+      if (!pt.on[layer]) continue;
+      const int head_dim = (int)lroundf(1.f / (o.f0 * o.f0));       // (the softmax scale is head_dim^-1/2; padded heads keep their own)
+      SHAPECHK(o.p3 == 1 && head_dim == 64, "%s: self-attention layer %d has head_dim %d (stored as %d); the perturbed launches are "
+               "built for 64", who, layer, head_dim, 64 * o.p3);
+      if (style && style->n_targets && style->on[layer])            // both replace or rewrite that layer's launch
+        REFUSE(PEA_E_STATE, "%s: self-attention layer %d is shared by StyleAligned and perturbed at once (switch it off in "
+               "pea_unet_set_style_aligned or in pea_unet_set_attn_perturb)", who, layer);
+      if (sag && sag->op == (int)i)
+        REFUSE(PEA_E_STATE, "%s: self-attention layer %d is perturbed, and self-attention guidance captures its launch "
+               "(pea_unet_disable_sag, or switch the layer off in pea_unet_set_attn_perturb)", who, layer);
+      if (forward && pt.mode == PerturbState::BLUR && !pt.grid.count(o.p1))   // forward only, as the regions' weights
+        REFUSE(PEA_E_STATE, "%s: the query blur has no tables for the layers with %d queries; pea_unet_set_attn_perturb needs the "
+               "grid of every switched-on layer", who, o.p1);
     }
   }
   return PEA_OK;
@@ -225,7 +259,8 @@ static AttnMapsP maps_p(float* acc, const int* kv_len, const AttnP& p) {        
 
 // Forward of attention op oi (OP_ATTN).  Top to bottom, the precedence of the features: regions replace the launch; else a live
 // edit step replaces it; else image prompts attach to it; else StyleAligned replaces it; else the plain launch, with guidance's
-// lse pointer in it and the column sums behind it; then the edit's per-sample self-attention launches; then the heat maps'.
+// lse pointer in it and the column sums behind it -- on a perturbed layer behind the blur of the perturbed samples' queries, or over
+// the plain samples alone with the V -> O copy behind it; then the edit's per-sample self-attention launches; then the heat maps'.
 int Tape::attn_forward(size_t oi, hipStream_t s) {
   const Op& o = ops[oi];
   const bool text = o.b == t_kvall;                                  // cross-attention over the text context
@@ -247,9 +282,22 @@ int Tape::attn_forward(size_t oi, hipStream_t s) {
                               style->coef, style->scratch, s));
     return launch_attention_fwd_shared(shared_p(*style, p), s);
   }
+  // perturbed-attention guidance on this layer: the suffix's queries blurred in place in front of the one launch, or the launch
+  // over the plain samples alone and V copied to O for the suffix (attn_rules has passed: head_dim 64, the grid's tables are there)
+  const int perturbed = perturb && is_self_attn(o) && perturb->on[perturb->layer_of_op.find((int)oi)->second] ? perturb->mode : 0;
+  if (perturbed == PerturbState::BLUR) {
+    const PerturbState::Grid& g = perturb->grid.find(o.p1)->second;
+    RC(launch_query_blur((bf16*)p.Q + (size_t)perturb->first * p.Sq * p.ldq, p.ldq, B - perturb->first, g.h, g.w, 64 * p.H, g.Mh, g.Mw, s));
+  }
+  if (perturbed == PerturbState::IDENTITY) p.B = perturb->first;
   const bool sag_here = sag && sag->op == (int)oi;
   if (sag_here) p.lse = sag->lse;
   RC(launch_attention_fwd(p, s));
+  if (perturbed == PerturbState::IDENTITY) {
+    p.B = B;
+    RC(launch_copy2d(p.V + (size_t)perturb->first * p.Skv * p.ldv, p.ldv, p.O + (size_t)perturb->first * p.Sq * p.ldo, p.ldo,
+                     (long long)(B - perturb->first) * p.Sq, 64 * p.H, 0, s));
+  }
   if (sag_here) RC(launch_attention_colsum(colsum_p(*sag, p), s));
   if (edit && graph == 0 && !text && !o.mask && o.p1 == o.p2 && o.p1 <= edit->self_max_tokens && edit->step < edit->self_until) {
     // prompt editing, self-attention: O[b] = softmax(Q[s] K[s]^T) V[b], one B = 1 launch per edited sample behind the
@@ -708,6 +756,52 @@ int pea_unet_sag_colsum(void* h, float** part, int* G, int* S) {
   if (G) *G = u->sag->G;
   if (S) *S = u->sag->S;
   return PEA_OK;
+}
+// ------------------------------------------------------------------------------ perturbed-attention / smoothed-energy guidance
+int pea_unet_set_attn_perturb(void* h, int mode, int first_sample, const float* layer_on, int n_layers, int n_grids, const int* grid_h,
+                              const int* grid_w, const float* tables, void* stream) {
+  const char* const who = "pea_unet_set_attn_perturb";
+  Tape* u = nullptr;
+  RC(unet_handle(h, who, false, "graph %d", &u));
+  typedef Tape::PerturbState PS;
+  SHAPECHK(mode == PS::IDENTITY || mode == PS::BLUR, "%s: mode %d (1: identity, 2: query blur)", who, mode);
+  SHAPECHK(n_grids >= 0 && n_grids <= 16 && (n_grids == 0 || (grid_h && grid_w && tables)), "%s: %d grids with their sides and tables", who, n_grids);
+  std::unique_ptr<PS> st(new PS());
+  st->mode = mode; st->first = first_sample;
+  RC(parse_layer_on(who, layer_on, n_layers, self_attn_layers(*u, &st->layer_of_op), "self-attention", st->on));
+  // the tables of a grid, host fp32: Mh [h][h], then Mw [w][w]; a grid must be that of some self-attention layer (its query count)
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t err = hipSuccess;
+  for (int i = 0; i < n_grids && mode == PS::BLUR; ++i) {
+    const int gh = grid_h[i], gw = grid_w[i];
+    SHAPECHK(gh >= 1 && gw >= 1 && gh <= QUERY_BLUR_MAX_SIDE && gw <= QUERY_BLUR_MAX_SIDE,
+             "%s: a %d x %d token grid; the query blur holds a grid in LDS, at most %d x %d (%zu of 163840 bytes)", who, gh, gw,
+             QUERY_BLUR_MAX_SIDE, QUERY_BLUR_MAX_SIDE, query_blur_lds_bytes(QUERY_BLUR_MAX_SIDE, QUERY_BLUR_MAX_SIDE));
+    bool found = false;
+    for (const Op& o : u->ops) found = found || (u->is_self_attn(o) && o.p1 == gh * gw);
+    SHAPECHK(found && !st->grid.count(gh * gw), "%s: no self-attention layer of this context has %d queries, or the %d x %d grid is given twice",
+             who, gh * gw, gh, gw);
+    PS::Grid& g = st->grid[gh * gw];
+    g.h = gh; g.w = gw;
+    THEN(err, hipMalloc((void**)&g.Mh, sizeof(float) * gh * gh));
+    THEN(err, hipMalloc((void**)&g.Mw, sizeof(float) * gw * gw));
+    THEN(err, hipMemcpyAsync(g.Mh, tables, sizeof(float) * gh * gh, hipMemcpyHostToDevice, s));
+    THEN(err, hipMemcpyAsync(g.Mw, tables + gh * gh, sizeof(float) * gw * gw, hipMemcpyHostToDevice, s));
+    tables += gh * gh + gw * gw;
+  }
+  THEN(err, hipStreamSynchronize(s));                                 // the host tables are the caller's again
+  RC(dev_chain(who, err));
+  RC(pea_unet_clear_attn_perturb(h));
+  u->perturb = st.get();                                             // (the rules read the state they judge)
+  const int rc = u->attn_rules(Tape::AF_PERTURB, false);
+  u->perturb = nullptr;
+  if (rc) return rc;
+  u->perturb = st.release();
+  return PEA_OK;
+}
+int pea_unet_clear_attn_perturb(void* h) {                           // (the identity mode has no buffers)
+  return drop_state<Tape::PerturbState>(h, "pea_unet_clear_attn_perturb", &Tape::perturb,
+                                        [](const Tape::PerturbState& st) { return !st.grid.empty(); });
 }
 // ------------------------------------------------------------------------------ cross-attention heat maps
 int pea_unet_enable_attention_maps(void* h, const float* layer_on, int n_layers) {

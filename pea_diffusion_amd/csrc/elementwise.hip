@@ -863,6 +863,100 @@ int launch_copy2d(const bf16* x, int ldx, bf16* y, int ldy, long long rows, int 
   return PEA_OK;
 }
 
+// Smoothed-energy guidance (Hong 2024): the queries of the perturbed samples, as their h x w token grid, blurred per channel, IN
+// PLACE:  Q~[b][y][x][c] = sum_y' sum_x' Mh[y][y'] Mw[x][x'] Q[b][y'][x'][c].  Mh [h][h], Mw [w][w]: dense fp32 row-stochastic
+// matrices from the host (taps, size clamp, reflect padding and the infinite-sigma mean are all folded into them: one code path).
+// A workgroup owns QB_SLAB = 8 channels (one 16-byte access per token) of one sample and holds their whole grid in LDS as fp32
+// [h][w * 8 + 8] -- 133,120 bytes at 64 x 64, which is what fixes the slab: 16 channels would need 264 KB, and an fp32 image plus a
+// bf16 one does not fit either.  Pass 1 (along x): a thread takes one (row, channel), reads its w values into registers and writes
+// the w sums back over them; pass 2 (along y) the same per (column, channel); both products stay fp32 and only the store rounds.
+// A thread is the only reader and writer of its line in a pass, so in place needs no second buffer, and since the workgroup owns
+// every token of its channels the global rows can be overwritten too.  The row pad of 8 floats spreads pass 1's 32 lanes (4 rows
+// x 8 channels) over 32 banks; pass 2's lanes are consecutive dwords.  The matrix entries are uniform across a wave: scalar loads.  An output is
+// four interleaved fma chains added at the end (a fixed order: the same bits every run).  Measurements: EXPERIMENTS section 9 f14.
+#define QB_SLAB 8
+#define QB_THREADS(N) ((N) == 64 ? 512 : 256)                        // a 64-wide grid has 512 lines a pass: a thread each
+// (EXACT: the line has N entries -- SDXL's 32 and 64, the tiny UNet's 8 and 16 -- and nothing is predicated; otherwise m <= N)
+template <int N, bool EXACT>
+__device__ __forceinline__ void qblur_line(float* line, int stride, int m, const float* __restrict__ M) {
+  if constexpr (EXACT) m = N;
+  float r[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) r[j] = EXACT || j < m ? line[j * stride] : 0.f;
+#pragma unroll 1
+  for (int i = 0; i < m; ++i) {
+    const float* row = M + i * m;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};                             // four chains: one wave per SIMD hides no FMA latency
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (EXACT || j < m) acc[j & 3] = fmaf(row[j], r[j], acc[j & 3]);
+    line[i * stride] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  }
+}
+template <int N, bool EXACT>
+__global__ __launch_bounds__(QB_THREADS(N)) void query_blur_kernel(bf16* __restrict__ Q, int ld, int h, int w, const float* __restrict__ Mh,
+                                                         const float* __restrict__ Mw) {
+  extern __shared__ float qb_img[];
+  const int pitch = w * QB_SLAB + QB_SLAB;
+  bf16* const q = Q + (size_t)blockIdx.y * h * w * ld + blockIdx.x * QB_SLAB;
+  constexpr int NT = QB_THREADS(N);
+  for (int t = threadIdx.x; t < h * w; t += NT) {
+    const bf16x8 v = *(const bf16x8*)(q + (size_t)t * ld);
+    float* d = qb_img + (t / w) * pitch + (t % w) * QB_SLAB;
+    f32x4 lo, hi;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { lo[j] = (float)v[j]; hi[j] = (float)v[4 + j]; }
+    *(f32x4*)d = lo;
+    *(f32x4*)(d + 4) = hi;
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < h * QB_SLAB; t += NT)               // along x: line (row t / 8, channel t % 8)
+    qblur_line<N, EXACT>(qb_img + (t / QB_SLAB) * pitch + t % QB_SLAB, QB_SLAB, w, Mw);
+  __syncthreads();
+  for (int t = threadIdx.x; t < w * QB_SLAB; t += NT)               // along y: line (column t / 8, channel t % 8)
+    qblur_line<N, EXACT>(qb_img + t, pitch, h, Mh);
+  __syncthreads();
+  for (int t = threadIdx.x; t < h * w; t += NT) {
+    const float* d = qb_img + (t / w) * pitch + (t % w) * QB_SLAB;
+    const f32x4 lo = *(const f32x4*)d, hi = *(const f32x4*)(d + 4);
+    bf16x8 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v[j] = (bf16)lo[j]; v[4 + j] = (bf16)hi[j]; }
+    *(bf16x8*)(q + (size_t)t * ld) = v;
+  }
+}
+size_t query_blur_lds_bytes(int h, int w) { return (size_t)h * (w * QB_SLAB + QB_SLAB) * sizeof(float); }
+template <int N, bool EXACT>
+static int query_blur_launch(bf16* Q, int ld, int n, int h, int w, int C, const float* Mh, const float* Mw, size_t lds, hipStream_t s) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)query_blur_kernel<N, EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, QUERY_BLUR_MAX_SIDE *
+                               (QUERY_BLUR_MAX_SIDE * QB_SLAB + QB_SLAB) * (int)sizeof(float)));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((query_blur_kernel<N, EXACT>), dim3(C / QB_SLAB, n), dim3(QB_THREADS(N)), lds, s, Q, ld, h, w, Mh, Mw);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+int launch_query_blur(bf16* Q, int ld, int n, int h, int w, int C, const float* Mh, const float* Mw, hipStream_t s) {
+  SHAPECHK(Q && Mh && Mw, "query_blur: null operand");
+  SHAPECHK(n > 0 && n <= 65535 && h > 0 && w > 0 && C > 0, "query_blur: n=%d samples of a %d x %d grid, %d columns (n <= 65535)", n, h, w, C);
+  SHAPECHK(C % 64 == 0, "query_blur: %d columns (whole heads of 64)", C);
+  SHAPECHK(ld % 8 == 0 && ld >= C && ((uintptr_t)Q & 15) == 0, "query_blur: pitch %d for %d columns (a multiple of 8 holding them, rows 16-byte aligned)", ld, C);
+  SHAPECHK(h <= QUERY_BLUR_MAX_SIDE && w <= QUERY_BLUR_MAX_SIDE,
+           "query_blur: a %d x %d token grid; a workgroup holds the whole grid of its 8 channels in LDS as fp32, at most %d x %d (%zu of "
+           "163840 bytes)", h, w, QUERY_BLUR_MAX_SIDE, QUERY_BLUR_MAX_SIDE, query_blur_lds_bytes(QUERY_BLUR_MAX_SIDE, QUERY_BLUR_MAX_SIDE));
+  const size_t lds = query_blur_lds_bytes(h, w);
+  const int m = h > w ? h : w;
+  const bool exact = h == w && (m == 8 || m == 16 || m == 32 || m == 64);
+#define QB_GO(N) return exact ? query_blur_launch<N, true>(Q, ld, n, h, w, C, Mh, Mw, lds, s) : query_blur_launch<N, false>(Q, ld, n, h, w, C, Mh, Mw, lds, s)
+  if (m <= 8) QB_GO(8);
+  if (m <= 16) QB_GO(16);
+  if (m <= 32) QB_GO(32);
+  QB_GO(64);
+#undef QB_GO
+}
+
 __global__ void cast_i64_f32_kernel(const long long* __restrict__ x, float* __restrict__ y, long long n) {
   EW_LOOP(i, n) y[i] = (float)x[i];
 }

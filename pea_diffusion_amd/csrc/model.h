@@ -318,9 +318,30 @@ struct Tape {
     }
   };
   SagState* sag = nullptr;
+  // Perturbed-attention / smoothed-energy guidance (graph 0, inference only; attn_features.hip: pea_unet_set_attn_perturb): the last
+  // B - first samples of the batch are the perturbed ones.  While this is set, a self-attention op (is_self_attn) whose layer is
+  // switched on treats them differently -- mode 1 (identity): the ordinary launch over the first `first` samples and ONE pitched
+  // copy V -> O for the rest; mode 2 (blur): ONE launch_query_blur in place over the suffix's Q columns with the tables of the op's
+  // query count, then the ordinary launch over all B.  The other samples keep their bits (the forward's grid is (units, H, B) with
+  // no cross-sample state).  The tape, the plans, the arenas and the attention census do not change.  Outside the arenas.
+  struct PerturbState {
+    enum { IDENTITY = 1, BLUR = 2 };
+    int mode = 0, first = 0;
+    std::map<int, int> layer_of_op;            // as StyleState's
+    std::vector<char> on;
+    struct Grid { int h = 0, w = 0; float* Mh = nullptr; float* Mw = nullptr; };   // device fp32 [h][h] and [w][w]
+    std::map<int, Grid> grid;                  // query count -> its grid and blur matrices (mode 2)
+    ~PerturbState() {
+      for (auto& g : grid) {
+        if (g.second.Mh) (void)hipFree(g.second.Mh);
+        if (g.second.Mw) (void)hipFree(g.second.Mw);
+      }
+    }
+  };
+  PerturbState* perturb = nullptr;
   // The features above on the host (attn_features.hip): what a context must be for each of them (AF_* bits of `which`), judged by
   // its setter and again by forward() before the first launch; and the launches of attention op `oi` with them in place
-  enum { AF_IP = 1, AF_REGIONS = 2, AF_MAPS = 4, AF_EDIT = 8, AF_STYLE = 16, AF_SAG = 32 };
+  enum { AF_IP = 1, AF_REGIONS = 2, AF_MAPS = 4, AF_EDIT = 8, AF_STYLE = 16, AF_SAG = 32, AF_PERTURB = 64 };
   int attn_rules(unsigned which, bool forward, int arg = 0) const;
   int attn_forward(size_t oi, hipStream_t s);
   std::deque<WSlot> slots;

@@ -346,6 +346,11 @@ size_t kd_loss_workspace_bytes(int ntaps, const long long* per, long long per_ep
 int launch_accum(const bf16* x, bf16* y, long long n, int accum, hipStream_t s);
 int launch_copy2d(const bf16* x, int ldx, bf16* y, int ldy, long long rows, int C, int accum, hipStream_t s);
 int launch_cast_i64_f32(const long long* x, float* y, long long n, hipStream_t s);
+// smoothed-energy guidance: Q [n][h * w] rows of pitch ld, C columns (whole heads), blurred in place over the h x w grid per channel,
+// Q~ = Mh . Q . Mw^T with dense device fp32 Mh [h][h], Mw [w][w]; the grid sits in LDS: at most QUERY_BLUR_MAX_SIDE a side
+#define QUERY_BLUR_MAX_SIDE 64
+size_t query_blur_lds_bytes(int h, int w);
+int launch_query_blur(bf16* Q, int ld, int n, int h, int w, int C, const float* Mh, const float* Mw, hipStream_t s);
 
 // ---------------------------------------------------------------- prof.hip
 #define PEA_PROF_FAMILIES 8
@@ -363,6 +368,9 @@ int launch_permute_geglu_vec(const float* src, float* dst, int inner, hipStream_
 // sampler.hip: inference denoise-loop glue
 size_t cfg_combine_workspace_bytes(int B);
 int launch_cfg_combine(const float* eps2, float* out, int B, long long per, float g, float rescale, void* ws, hipStream_t s);
+// perturbed-attention / smoothed-energy guidance: eps [3B | 2B][per] with the perturbed samples last; cfg_combine's workspace
+int launch_cfg_pag_combine(const float* eps, float* out, int B, long long per, int cfg, float g, float sg, float rescale, void* ws,
+                           hipStream_t s);
 int launch_dpm_update(float* sample, const float* eps, float* x0_prev, long long n, float alpha_s, float sigma_s,
                       float c_s, float c_0, float c_1, hipStream_t s);
 // LCMScheduler.step: denoised = kx * sample + ke * eps; sample <- c_prev * denoised + c_noise * noise (noise / denoised may be null)

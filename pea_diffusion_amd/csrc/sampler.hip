@@ -15,16 +15,25 @@ __global__ void cfg_combine_kernel(const float* __restrict__ eps2, float* __rest
 }
 
 #define CFG_NBLK 64
+// The guided prediction of element i: u + g (t - u); PAG (perturbed-attention / smoothed-energy guidance): eps holds a third run of
+// samples p behind t, and sg (t - p) is added -- at sg = 0 the first form's bits.
+template <bool PAG>
+__device__ __forceinline__ float cfg_guided(const float* __restrict__ eps, long long n, long long i, float uv, float tv, float g, float sg) {
+  const float c = uv + g * (tv - uv);
+  if constexpr (PAG) return sg != 0.f ? c + sg * (tv - eps[2 * n + i]) : c;
+  return c;
+}
 // per (sample, block): sums of t, t^2, c, c^2 in double, fixed order inside the block
+template <bool PAG>
 __global__ __launch_bounds__(256) void cfg_stats_kernel(const float* __restrict__ eps2, long long n, long long per,
-                                                        float g, double* __restrict__ part) {
+                                                        float g, float sg, double* __restrict__ part) {
   const int b = blockIdx.y;
   const float* u = eps2 + (long long)b * per;
   const float* t = eps2 + n + (long long)b * per;
   double s[4] = {0, 0, 0, 0};
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long long)CFG_NBLK * 256) {
     const float uv = u[i], tv = t[i];
-    const float c = uv + g * (tv - uv);
+    const float c = cfg_guided<PAG>(eps2, n, (long long)b * per + i, uv, tv, g, sg);
     s[0] += tv; s[1] += (double)tv * tv; s[2] += c; s[3] += (double)c * c;
   }
   __shared__ double red[4][256];
@@ -51,11 +60,12 @@ __global__ void cfg_factor_kernel(const double* __restrict__ part, float* __rest
   const double vt = (s[1] - s[0] * s[0] / nn) / (nn - 1.0), vc = (s[3] - s[2] * s[2] / nn) / (nn - 1.0);
   factor[b] = (float)((double)phi * sqrt(vt / vc) + (1.0 - (double)phi));
 }
+template <bool PAG>
 __global__ void cfg_apply_kernel(const float* __restrict__ eps2, float* __restrict__ out, long long n, long long per,
-                                 float g, const float* __restrict__ factor) {
+                                 float g, float sg, const float* __restrict__ factor) {
   SM_LOOP(i, n) {
     const float u = eps2[i], t = eps2[n + i];
-    out[i] = (u + g * (t - u)) * factor[i / per];
+    out[i] = cfg_guided<PAG>(eps2, n, i, u, t, g, sg) * factor[i / per];
   }
 }
 
@@ -71,9 +81,38 @@ int launch_cfg_combine(const float* eps2, float* out, int B, long long per, floa
     SHAPECHK(ws != nullptr, "cfg_combine: guidance_rescale needs the workspace");
     double* part = (double*)ws;
     float* factor = (float*)(part + (size_t)B * CFG_NBLK * 4);
-    hipLaunchKernelGGL(cfg_stats_kernel, dim3(CFG_NBLK, B), dim3(256), 0, s, eps2, n, per, g, part);
+    hipLaunchKernelGGL(cfg_stats_kernel<false>, dim3(CFG_NBLK, B), dim3(256), 0, s, eps2, n, per, g, 0.f, part);
     hipLaunchKernelGGL(cfg_factor_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, part, factor, B, per, rescale);
-    hipLaunchKernelGGL(cfg_apply_kernel, dim3(sm_grid(n)), dim3(256), 0, s, eps2, out, n, per, g, factor);
+    hipLaunchKernelGGL(cfg_apply_kernel<false>, dim3(sm_grid(n)), dim3(256), 0, s, eps2, out, n, per, g, 0.f, factor);
+  }
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
+// Perturbed-attention / smoothed-energy guidance (Ahn et al. 2024; Hong 2024): the perturbed samples p ride in the same batch behind
+// the text samples.  cfg: eps = [u | t | p] (B samples each), out = u + g (t - u) + sg (t - p), then rescale_noise_cfg against t when
+// rescale > 0 -- cfg_combine's kernels with the third term, its reduction and its workspace; sg = 0 gives its bits on [u | t].
+// Otherwise eps = [t | p], out = t + sg (t - p), and no rescale (it is defined against the CFG result).
+__global__ void pag_combine_kernel(const float* __restrict__ eps, float* __restrict__ out, long long n, int cfg, float g, float sg) {
+  SM_LOOP(i, n) {
+    const float a = eps[i], b = eps[n + i];
+    out[i] = cfg ? cfg_guided<true>(eps, n, i, a, b, g, sg) : (sg != 0.f ? a + sg * (a - b) : a);
+  }
+}
+int launch_cfg_pag_combine(const float* eps, float* out, int B, long long per, int cfg, float g, float sg, float rescale, void* ws,
+                           hipStream_t s) {
+  SHAPECHK(eps && out, "cfg_pag_combine: null operand");
+  SHAPECHK(B > 0 && per > 1, "cfg_pag_combine: B=%d per=%lld", B, per);
+  const long long n = (long long)B * per;
+  if (!cfg || rescale <= 0.f) {
+    hipLaunchKernelGGL(pag_combine_kernel, dim3(sm_grid(n)), dim3(256), 0, s, eps, out, n, cfg != 0, g, sg);
+  } else {
+    SHAPECHK(ws != nullptr, "cfg_pag_combine: guidance_rescale needs the workspace (pea_op_cfg_combine_workspace_bytes)");
+    double* part = (double*)ws;
+    float* factor = (float*)(part + (size_t)B * CFG_NBLK * 4);
+    hipLaunchKernelGGL(cfg_stats_kernel<true>, dim3(CFG_NBLK, B), dim3(256), 0, s, eps, n, per, g, sg, part);
+    hipLaunchKernelGGL(cfg_factor_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, part, factor, B, per, rescale);
+    hipLaunchKernelGGL(cfg_apply_kernel<true>, dim3(sm_grid(n)), dim3(256), 0, s, eps, out, n, per, g, sg, factor);
   }
   HIPCHK(hipGetLastError());
   return PEA_OK;

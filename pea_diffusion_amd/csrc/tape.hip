@@ -273,6 +273,7 @@ Tape::~Tape() {
   delete edit;
   delete style;
   delete sag;
+  delete perturb;
 }
 
 int Tape::set_inpaint_cond(const float* mask, const float* masked, int cond_b, int lat_b, hipStream_t s) {
@@ -501,7 +502,7 @@ int Tape::forward(const float* x, const float* t, const void* ehs, int ehs_dtype
     return PEA_E_STATE;
   }
   RC(attn_rules((ip ? AF_IP : 0) | (regions ? AF_REGIONS : 0) | (maps ? AF_MAPS : 0) | (edit ? AF_EDIT : 0) | (style ? AF_STYLE : 0) |
-                    (sag ? AF_SAG : 0), true));
+                    (sag ? AF_SAG : 0) | (perturb ? AF_PERTURB : 0), true));
   RC(ensure_acts());
   RC(ensure_folded(s));
   x_in = x; t_in = t; tid_in = time_ids; eps_out = eps;

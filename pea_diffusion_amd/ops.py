@@ -703,6 +703,54 @@ def cfg_sag_combine(noise_pred, noise_pred_deg, guidance_scale, sag_scale, do_cf
     return out
 
 
+# ---- perturbed-attention / smoothed-energy guidance (Ahn et al. 2024; Hong 2024; pea_diffusion_amd/pag.py is the loop)
+def query_blur_(qkv, grid, Mh, Mw, cols=None, col0=0):
+    """In place (pea_op_query_blur): the columns [col0, col0 + cols) of the bf16 rows qkv [n, h*w, ld] read as n grids of
+    h x w tokens and blurred per channel, Q~ = Mh . Q . Mw^T.  Mh fp32 [h, h], Mw fp32 [w, w] on the device
+    (`pag.blur_matrix`).  cols: a multiple of 64 (default: all of ld); every other column keeps its bits.  -> qkv."""
+    n, S, ld = qkv.shape
+    h, w = int(grid[0]), int(grid[1])
+    cols = ld - col0 if cols is None else int(cols)
+    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous() or S != h * w:
+        raise PeaError(f"query_blur_: rows {tuple(qkv.shape)} {qkv.dtype}, expected contiguous bf16 [n, {h * w}, ld] for a {h} x {w} grid")
+    for m, side in ((Mh, h), (Mw, w)):
+        if m.dtype != torch.float32 or tuple(m.shape) != (side, side) or not m.is_contiguous() or m.device != qkv.device:
+            raise PeaError(f"query_blur_: blur matrix {tuple(m.shape)} {m.dtype}, expected contiguous fp32 [{side}, {side}] on the device")
+    check(lib().pea_op_query_blur(ptr(qkv), ld, int(col0), n, h, w, cols, ptr(Mh), ptr(Mw), stream_ptr()))
+    return qkv
+
+
+def attn_identity(v, out, cols, col0=0):
+    """The identity attention O = V (pea_op_attn_identity): `cols` bf16 columns from column col0 of v [..., ldv] into the
+    first `cols` columns of out [..., ldo], row by row; every other column of out keeps its bits.  -> out."""
+    if v.dtype != torch.bfloat16 or out.dtype != torch.bfloat16 or not v.is_contiguous() or not out.is_contiguous():
+        raise PeaError("attn_identity: v and out are contiguous bf16 tensors")
+    rows = v.numel() // v.shape[-1]
+    if out.numel() // out.shape[-1] != rows:
+        raise PeaError(f"attn_identity: {rows} rows of v, {out.numel() // out.shape[-1]} of out")
+    check(lib().pea_op_attn_identity(ptr(v), v.shape[-1], int(col0), ptr(out), out.shape[-1], rows, int(cols), stream_ptr()))
+    return out
+
+
+def cfg_pag_combine(noise_pred, guidance_scale, pag_scale, guidance_rescale=0.0, do_cfg=True):
+    """The guidance combine with a perturbed third (pea_op_cfg_pag_combine).  do_cfg: noise_pred fp32 [3B, ...] =
+    [uncond | text | perturbed] -> u + g (t - u) + s (t - p), then `rescale_noise_cfg` against t when guidance_rescale > 0;
+    at s = 0 the bits of `cfg_combine` on the first 2B samples.  Otherwise noise_pred [2B, ...] = [text | perturbed]
+    -> t + s (t - p)."""
+    x = noise_pred.contiguous()
+    k = 3 if do_cfg else 2
+    if x.dtype != torch.float32 or x.shape[0] % k:
+        raise PeaError(f"cfg_pag_combine: noise_pred {tuple(x.shape)} {x.dtype}, expected fp32 with a batch of {k} B (do_cfg={do_cfg})")
+    B = x.shape[0] // k
+    out = torch.empty((B,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
+    ws = None
+    if do_cfg and guidance_rescale > 0.0:
+        ws = torch.empty(lib().pea_op_cfg_combine_workspace_bytes(B), device=x.device, dtype=torch.uint8)
+    check(lib().pea_op_cfg_pag_combine(ptr(x), ptr(out), B, out[0].numel(), int(bool(do_cfg)), float(guidance_scale), float(pag_scale),
+                                       float(guidance_rescale), ptr(ws), stream_ptr()))
+    return out
+
+
 def dpm_update_(sample, eps, x0_prev, alpha_s, sigma_s, c_s, c_0, c_1):
     """In place: x0 = (sample - sigma_s*eps)/alpha_s; sample <- c_s*sample + c_0*x0 + c_1*x0_prev; x0_prev <- x0."""
     for t in (sample, eps, x0_prev):

@@ -523,6 +523,52 @@ class HipUNet(HipTape):
         """back to plain self-attention; a forward then gives the bits it gave before"""
         check(lib().pea_unet_clear_style_aligned(self._h))
 
+    def set_attention_perturbation(self, mode, layers=None, samples=None, blur_sigma=float("inf")):
+        """Perturbed-attention guidance (mode "pag"; Ahn et al. 2024) or smoothed-energy guidance (mode "seg"; Hong 2024) in one
+        UNet call (`pag.denoise_perturbed` is the loop): the last `samples` samples of the batch are the perturbed ones, and in
+        the chosen self-attention layers their attention is the identity, O = V ("pag"), or runs on queries blurred over the
+        token grid with a Gaussian of `blur_sigma` ("seg"; above 9999: the mean over the grid).  layers: as
+        `set_style_aligned`'s names / prefixes / fraction; None = the mid block.  samples: how many; None = the last third of a
+        batch that divides by 3.  Every other sample keeps its bits.  Holds until `clear_attention_perturbation()`."""
+        import numpy as np
+        from . import pag
+        from . import style_aligned as sa
+        modes = {"pag": 1, "seg": 2}
+        if mode not in modes:
+            raise PeaError(f"set_attention_perturbation: mode {mode!r} ('pag' or 'seg')")
+        if samples is None:
+            if self.B % 3:
+                raise PeaError(f"set_attention_perturbation: a batch of {self.B} is no [uncond | cond | perturbed]; say how many "
+                               "samples at its end are perturbed")
+            samples = self.B // 3
+        names = sa.layer_names(self)
+        if layers is None and not any(n.startswith("mid_block.") for n in names):
+            raise PeaError("set_attention_perturbation: this UNet has no mid-block attention; name the layers "
+                           "(style_aligned.layer_names)")
+        vec = sa.resolve_layers(self, ["mid_block"] if layers is None else layers)
+        arr = (ctypes.c_float * len(vec))(*vec)
+        grids, tables = [], []
+        if mode == "seg":
+            top = len(self.cfg.down_block_types) - 1
+            for name, on in zip(names, vec):
+                block, idx = name.split(".")[0], name.split(".")[1]
+                level = int(idx) if block == "down_blocks" else top if block == "mid_block" else top - int(idx)
+                h, w = self.H, self.W
+                for _ in range(level):
+                    h, w = (h + 1) // 2, (w + 1) // 2
+                if on and (h, w) not in grids:
+                    grids.append((h, w))
+                    tables += [pag.blur_matrix(h, blur_sigma).reshape(-1), pag.blur_matrix(w, blur_sigma).reshape(-1)]
+        gh = (ctypes.c_int * max(len(grids), 1))(*[g[0] for g in grids])
+        gw = (ctypes.c_int * max(len(grids), 1))(*[g[1] for g in grids])
+        flat = np.ascontiguousarray(np.concatenate(tables) if tables else np.zeros(1), dtype=np.float32)
+        check(lib().pea_unet_set_attn_perturb(self._h, modes[mode], self.B - int(samples), arr, len(vec), len(grids), gh, gw,
+                                              ctypes.c_void_p(flat.ctypes.data), stream_ptr()))
+
+    def clear_attention_perturbation(self):
+        """back to plain self-attention; a forward then gives the bits it gave before"""
+        check(lib().pea_unet_clear_attn_perturb(self._h))
+
     def enable_sag(self, layer=None, samples=None):
         """Self-attention guidance capture (Hong et al. 2023; `sag.denoise_sag` is the loop): while enabled, one self-attention
         layer's launch also stores its lse and is followed by one column-sum launch, `sag_colsum()`.  layer: an index or a name
