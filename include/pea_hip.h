@@ -1071,6 +1071,37 @@ int pea_unet_set_attn_perturb(void* unet, int mode, int first_sample, const floa
                               const int* grid_h, const int* grid_w, const float* tables, void* stream);
 int pea_unet_clear_attn_perturb(void* unet);
 
+/* ---- MultiDiffusion panoramas (Bar-Tal et al. 2023, "MultiDiffusion: Fusing Diffusion Paths for Controlled Image Generation"; the
+ * weights of Mixture of Diffusers, Jimenez 2023): a canvas fp32 [N][C][Hc][Wc] larger than the context's window h x w is denoised
+ * through overlapping window-sized VIEWS with the unchanged fixed-shape UNet, reconciled in the overlaps at every step.  A restatement
+ * from the paper (unpinned).  A view is (n, y0, x0): image n, rows y0 .. y0 + h - 1, columns (x0 + j) mod Wc for
+ * j < w; without wrap_x x0 + w <= Wc, with it 0 <= x0 < Wc and a view may straddle the seam; no wrap in y.  Both ops work on a CHUNK,
+ * the vb <= 16 view slots of one UNet call, n_valid of them real: `slots` is a HOST array int [n_valid][3] = (n, y0, x0), copied into
+ * the kernel arguments -- no device table, no host-to-device copy.  One launch each, every element read once, no atomics: the same
+ * bits every run.  16-byte accesses when w, Wc and every x0 are multiples of 4 and the pointers 16-byte aligned (a wrapped view
+ * included), one element per thread otherwise, with identical results.
+ * pea_op_views_gather: model_in fp32 [dup][vb][C][h][w], model_in[d][s] = crop of slot s * k_s for d < dup (dup 2: the CFG-doubled
+ *   batch); a slot past n_valid repeats the last valid slot (the UNet never reads uninitialised memory; its output there is ignored).
+ * pea_op_views_merge: eps fp32 [dup][vb][C][h][w] into the canvas, gather-style: a thread owns canvas elements and walks the valid
+ *   slots in ascending order.  Per covering slot e = u + g (t - u) for dup 2 (the expression of pea_op_cfg_combine, unconditional
+ *   half first), eps itself for dup 1; times factor[s] when `factor` (device fp32 [vb], pea_op_cfg_rescale_factors) is given;
+ *   acc += wy[i] wx[j] e with device fp32 tables wy [h], wx [w].  `first`: acc starts at 0 and every canvas element is stored (0 where
+ *   no slot of the chunk covers it); otherwise acc starts at what the canvas holds and elements outside the chunk's views are not
+ *   touched.  `last`: every element is then divided by total[n][Y][X] (device fp32 [N][Hc][Wc], the summed weights of ALL covering
+ *   views) in the same launch, in place.  C, h, w, Hc, Wc are free: the same entry merges decoded pixel tiles (C 3, dup 1).
+ * pea_op_cfg_rescale_factors: factor[b] = phi std(t_b) / std(cfg_b) + 1 - phi of rescale_noise_cfg for eps2 = [u | t] fp32 [2B][per]:
+ *   the reduction and factor launches of pea_op_cfg_combine without its apply pass (the same bits as its factors); workspace of
+ *   pea_op_cfg_combine_workspace_bytes(B), factor device fp32 [B].
+ * PEA_E_SHAPE before any HIP call: a null operand, vb outside 1..16, n_valid outside 1..vb, dup outside 1..2, a window larger than
+ * the canvas, a view outside the canvas without wrap_x, x0 >= Wc with it, n outside 0..N-1, factor given with dup 1. */
+int pea_op_views_gather(const float* canvas, float* model_in, const int* slots, int n_valid, int vb, int dup, int N, int C, int Hc,
+                        int Wc, int h, int w, int wrap_x, float k_s, void* stream);
+int pea_op_views_merge(const float* eps, float* canvas, const int* slots, int n_valid, int vb, int dup, int N, int C, int Hc, int Wc,
+                       int h, int w, int wrap_x, float guidance_scale, const float* factor, const float* wy, const float* wx,
+                       const float* total, int first, int last, void* stream);
+int pea_op_cfg_rescale_factors(const float* eps2, int B, long long per, float guidance_scale, float guidance_rescale, void* workspace,
+                               float* factor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -461,6 +461,21 @@ int pea_op_euler_update(float* sample, const float* eps, const float* noise, flo
                         float k_n, float k_s, void* stream) {
   return launch_euler_update(sample, eps, noise, model_in, n, dup, k_e, k_n, k_s, (hipStream_t)stream);
 }
+// ---- MultiDiffusion panoramas (sampler.hip: view gather, overlap merge, the per-view rescale factors)
+int pea_op_views_gather(const float* canvas, float* model_in, const int* slots, int n_valid, int vb, int dup, int N, int C, int Hc,
+                        int Wc, int h, int w, int wrap_x, float k_s, void* stream) {
+  return launch_views_gather(canvas, model_in, slots, n_valid, vb, dup, N, C, Hc, Wc, h, w, wrap_x, k_s, (hipStream_t)stream);
+}
+int pea_op_views_merge(const float* eps, float* canvas, const int* slots, int n_valid, int vb, int dup, int N, int C, int Hc, int Wc,
+                       int h, int w, int wrap_x, float guidance_scale, const float* factor, const float* wy, const float* wx,
+                       const float* total, int first, int last, void* stream) {
+  return launch_views_merge(eps, canvas, slots, n_valid, vb, dup, N, C, Hc, Wc, h, w, wrap_x, guidance_scale, factor, wy, wx, total,
+                            first, last, (hipStream_t)stream);
+}
+int pea_op_cfg_rescale_factors(const float* eps2, int B, long long per, float guidance_scale, float guidance_rescale, void* workspace,
+                               float* factor, void* stream) {
+  return launch_cfg_rescale_factors(eps2, B, per, guidance_scale, guidance_rescale, workspace, factor, (hipStream_t)stream);
+}
 // ---- self-attention guidance (attention.hip: the column sums; sampler.hip: degrade and combine)
 int pea_op_attention_colsum_groups(int B, int H, int Sq, int Skv) { return attention_colsum_groups(B, H, Sq, Skv); }
 int pea_op_attention_colsum(const void* Q, int ldq, const void* K, int ldk, const float* lse, float* part, int B, int H, int Sq, int Skv,

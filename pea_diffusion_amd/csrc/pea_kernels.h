@@ -384,6 +384,14 @@ int launch_sag_degrade(const float* latents, const float* eps, const float* part
                        float* out, int B, int C, int H, int W, float c_x, float c_e, float o_b, float o_e, hipStream_t s);
 int launch_cfg_sag_combine(const float* eps, const float* eps_deg, float* out, int B, long long per, int cfg, float g, float sag,
                            hipStream_t s);
+// MultiDiffusion panoramas: a chunk of vb view slots (host int [n_valid][3] = n, y0, x0) between the canvas and the UNet batch
+int launch_views_gather(const float* canvas, float* model_in, const int* slots, int n_valid, int vb, int dup, int N, int C, int Hc,
+                        int Wc, int h, int w, int wrap_x, float k_s, hipStream_t s);
+int launch_views_merge(const float* eps, float* canvas, const int* slots, int n_valid, int vb, int dup, int N, int C, int Hc, int Wc,
+                       int h, int w, int wrap_x, float g, const float* factor, const float* wy, const float* wx, const float* total,
+                       int first, int last, hipStream_t s);
+// cfg_combine's statistics and factor kernels alone: factor[B] of rescale_noise_cfg, workspace of cfg_combine_workspace_bytes(B)
+int launch_cfg_rescale_factors(const float* eps2, int B, long long per, float g, float rescale, void* ws, float* factor, hipStream_t s);
 // lora.hip: out[M][Kf] = acc + scale * up[M][rank] . down[rank][Kf], fp32 (acc may be out)
 int launch_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank,
                         float scale, hipStream_t s);

@@ -359,6 +359,168 @@ int launch_cfg_sag_combine(const float* eps, const float* eps_deg, float* out, i
   return PEA_OK;
 }
 
+// MultiDiffusion panoramas (Bar-Tal et al. 2023): the canvas [N][C][Hc][Wc] is denoised through window-sized views with the
+// fixed-shape UNet; these two kernels move a CHUNK -- the vb view slots of one UNet call -- between canvas and batch.  A slot is
+// (n, y0, x0): image n, rows y0 .. y0 + h - 1, columns (x0 + j) mod Wc.  The slot table travels by value in the kernel arguments.
+// Each kernel is instantiated for 4 consecutive columns per thread (16-byte accesses: w, Wc and every x0 multiples of 4, which also
+// keeps a group of 4 on one side of the wrap seam, and 16-byte aligned pointers) and for 1; the arithmetic per element is the same.
+#define VIEWS_MAX 16
+struct ViewSlots { int n[VIEWS_MAX], y0[VIEWS_MAX], x0[VIEWS_MAX]; };
+template <int V> struct ViewsVec { typedef float type; };
+template <> struct ViewsVec<4> { typedef f32x4 type; };
+
+// model_in[d][s][c][i][j] = canvas[n_s][c][y0_s + i][(x0_s + j) mod Wc] * k_s for d < dup; a slot past n_valid repeats the last valid one
+template <int V>
+__global__ __launch_bounds__(256) void views_gather_kernel(const float* __restrict__ canvas, float* __restrict__ model_in, ViewSlots sl,
+                                                           int n_valid, int dup, int C, int h, int w, int Hc, int Wc, float k_s,
+                                                           long long total, long long half) {
+  typedef typename ViewsVec<V>::type vec;
+  const int wv = w / V;
+  SM_LOOP(idx, total) {                                  // idx = (((s * C + c) * h + i) * w + j) / V
+    const int jq = (int)(idx % wv);
+    long long r = idx / wv;
+    const int i = (int)(r % h);
+    r /= h;
+    const int c = (int)(r % C), s = min((int)(r / C), n_valid - 1);
+    int X = sl.x0[s] + jq * V;
+    X = X >= Wc ? X - Wc : X;
+    const long long src = (((long long)sl.n[s] * C + c) * Hc + sl.y0[s] + i) * Wc + X;
+    vec m = *(const vec*)(canvas + src);
+    m = m * k_s;
+    *(vec*)(model_in + idx * V) = m;
+    if (dup == 2) *(vec*)(model_in + half + idx * V) = m;
+  }
+}
+
+static int views_check(const char* op, const void* a, const void* b, const int* slots, int n_valid, int vb, int dup, int N, int C,
+                       int Hc, int Wc, int h, int w, int wrap_x, ViewSlots* sl, bool* x0_by4) {
+  SHAPECHK(a && b && slots, "%s: null operand", op);
+  SHAPECHK(vb >= 1 && vb <= VIEWS_MAX, "%s: vb=%d view slots (1..%d)", op, vb, VIEWS_MAX);
+  SHAPECHK(n_valid >= 1 && n_valid <= vb, "%s: n_valid=%d of vb=%d slots (1..vb)", op, n_valid, vb);
+  SHAPECHK(dup == 1 || dup == 2, "%s: dup=%d (1 or 2)", op, dup);
+  SHAPECHK(N > 0 && C > 0 && h > 0 && w > 0, "%s: N=%d C=%d, a %d x %d window", op, N, C, h, w);
+  SHAPECHK(h <= Hc && w <= Wc, "%s: a %d x %d window on a %d x %d canvas (the window is larger)", op, h, w, Hc, Wc);
+  SHAPECHK((long long)vb * C * h * w < (1ll << 31) && (long long)Hc * Wc < (1ll << 31), "%s: chunk or canvas plane too large", op);
+  *x0_by4 = true;
+  for (int s = 0; s < n_valid; ++s) {
+    const int n = slots[3 * s], y0 = slots[3 * s + 1], x0 = slots[3 * s + 2];
+    SHAPECHK(n >= 0 && n < N, "%s: slot %d names image n=%d of %d", op, s, n, N);
+    SHAPECHK(y0 >= 0 && y0 <= Hc - h, "%s: slot %d: rows %d .. %d outside the %d rows of the canvas (no wrap in y)", op, s, y0, y0 + h - 1, Hc);
+    if (wrap_x) SHAPECHK(x0 >= 0 && x0 < Wc, "%s: slot %d: x0=%d outside 0 .. %d (wrap_x)", op, s, x0, Wc - 1);
+    else SHAPECHK(x0 >= 0 && x0 <= Wc - w, "%s: slot %d: columns %d .. %d outside the %d columns of the canvas (no wrap_x)", op, s, x0, x0 + w - 1, Wc);
+    sl->n[s] = n; sl->y0[s] = y0; sl->x0[s] = x0;
+    *x0_by4 = *x0_by4 && x0 % 4 == 0;
+  }
+  for (int s = n_valid; s < VIEWS_MAX; ++s) { sl->n[s] = sl->n[n_valid - 1]; sl->y0[s] = sl->y0[n_valid - 1]; sl->x0[s] = sl->x0[n_valid - 1]; }
+  return PEA_OK;
+}
+
+int launch_views_gather(const float* canvas, float* model_in, const int* slots, int n_valid, int vb, int dup, int N, int C, int Hc,
+                        int Wc, int h, int w, int wrap_x, float k_s, hipStream_t s) {
+  ViewSlots sl;
+  bool by4;
+  const int rc = views_check("views_gather", canvas, model_in, slots, n_valid, vb, dup, N, C, Hc, Wc, h, w, wrap_x, &sl, &by4);
+  if (rc != PEA_OK) return rc;
+  const long long half = (long long)vb * C * h * w;
+  const bool vec = by4 && w % 4 == 0 && Wc % 4 == 0 && (((uintptr_t)canvas | (uintptr_t)model_in) & 15) == 0;
+  if (vec) hipLaunchKernelGGL(views_gather_kernel<4>, dim3(sm_grid(half / 4)), dim3(256), 0, s, canvas, model_in, sl, n_valid, dup, C, h, w, Hc, Wc, k_s, half / 4, half);
+  else hipLaunchKernelGGL(views_gather_kernel<1>, dim3(sm_grid(half)), dim3(256), 0, s, canvas, model_in, sl, n_valid, dup, C, h, w, Hc, Wc, k_s, half, half);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
+// The overlap merge, gather-style: a thread owns V consecutive canvas elements of one row and walks the valid slots in ascending
+// order, so no two threads write one address and the sum has one order.  Per covering slot, at window position (i, j):
+//   e = dup == 2 ? u + g (t - u) (cfg_guided<false>, the expression of cfg_combine) : eps;   e *= factor[s] when factor is given
+//   acc = fmaf(wy[i] * wx[j], e, acc)
+// acc starts at 0 (first) or at what the canvas holds; `last` divides by T[n][Y][X] in the same launch.  An element that no slot of the
+// chunk covers is written only by `first` (0) or `last` (the division): in a middle chunk it keeps its partial sum untouched.
+template <int V>
+__global__ __launch_bounds__(256) void views_merge_kernel(const float* __restrict__ eps, float* __restrict__ canvas,
+                                                          const float* __restrict__ factor, const float* __restrict__ wy,
+                                                          const float* __restrict__ wx, const float* __restrict__ T, ViewSlots sl,
+                                                          int n_valid, int dup, int C, int h, int w, int Hc, int Wc, float g, int first,
+                                                          int last, long long total, long long half) {
+  typedef typename ViewsVec<V>::type vec;
+  const int wcv = Wc / V;
+  SM_LOOP(idx, total) {                                  // idx = (((n * C + c) * Hc + Y) * Wc + X) / V
+    const int X = (int)(idx % wcv) * V;
+    long long r = idx / wcv;
+    const int Y = (int)(r % Hc);
+    r /= Hc;
+    const int c = (int)(r % C), n = (int)(r / C);
+    float acc[V];
+    if (first) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] = 0.f;
+    } else {
+      const vec a = *(const vec*)(canvas + idx * V);
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] = ((const float*)&a)[k];
+    }
+    bool write = first || last;
+    for (int s = 0; s < n_valid; ++s) {
+      const int i = Y - sl.y0[s];
+      int j = X - sl.x0[s];
+      j = j < 0 ? j + Wc : j;                            // a wrapped view's columns behind the seam; without wrap x0 + w <= Wc and j stays >= w
+      if (sl.n[s] != n || (unsigned)i >= (unsigned)h || (unsigned)j >= (unsigned)w) continue;
+      const long long e = (((long long)s * C + c) * h + i) * w + j;
+      const vec uv = *(const vec*)(eps + e);
+      vec tv = uv;
+      if (dup == 2) tv = *(const vec*)(eps + half + e);
+      const float f = factor ? factor[s] : 1.f, wyi = wy[i];
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const float u = ((const float*)&uv)[k];
+        float v = dup == 2 ? cfg_guided<false>(eps, half, e + k, u, ((const float*)&tv)[k], g, 0.f) : u;
+        if (factor) v = v * f;
+        acc[k] = fmaf(wyi * wx[j + k], v, acc[k]);
+      }
+      write = true;
+    }
+    if (!write) continue;
+    vec o;
+    if (last) {
+      const vec t = *(const vec*)(T + ((long long)n * Hc + Y) * Wc + X);
+#pragma unroll
+      for (int k = 0; k < V; ++k) ((float*)&o)[k] = acc[k] / ((const float*)&t)[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < V; ++k) ((float*)&o)[k] = acc[k];
+    }
+    *(vec*)(canvas + idx * V) = o;
+  }
+}
+
+int launch_views_merge(const float* eps, float* canvas, const int* slots, int n_valid, int vb, int dup, int N, int C, int Hc, int Wc,
+                       int h, int w, int wrap_x, float g, const float* factor, const float* wy, const float* wx, const float* total,
+                       int first, int last, hipStream_t s) {
+  ViewSlots sl;
+  bool by4;
+  const int rc = views_check("views_merge", eps, canvas, slots, n_valid, vb, dup, N, C, Hc, Wc, h, w, wrap_x, &sl, &by4);
+  if (rc != PEA_OK) return rc;
+  SHAPECHK(wy && wx && total, "views_merge: null operand (wy, wx and the weight total)");
+  SHAPECHK(!(factor && dup == 1), "views_merge: per-slot rescale factors belong to the guided form (dup=2), not to dup=1");
+  const long long half = (long long)vb * C * h * w, n = (long long)N * C * Hc * Wc;
+  const bool vec = by4 && w % 4 == 0 && Wc % 4 == 0 && (((uintptr_t)eps | (uintptr_t)canvas | (uintptr_t)total) & 15) == 0;
+  if (vec) hipLaunchKernelGGL(views_merge_kernel<4>, dim3(sm_grid(n / 4)), dim3(256), 0, s, eps, canvas, factor, wy, wx, total, sl, n_valid, dup, C, h, w, Hc, Wc, g, first != 0, last != 0, n / 4, half);
+  else hipLaunchKernelGGL(views_merge_kernel<1>, dim3(sm_grid(n)), dim3(256), 0, s, eps, canvas, factor, wy, wx, total, sl, n_valid, dup, C, h, w, Hc, Wc, g, first != 0, last != 0, n, half);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
+// The per-view rescale_noise_cfg factors of a chunk laid out as [u | t] with B = vb: cfg_combine's reduction and factor kernels
+// without its apply pass (the merge multiplies).  ws: cfg_combine_workspace_bytes(B); factor: fp32 [B].
+int launch_cfg_rescale_factors(const float* eps2, int B, long long per, float g, float rescale, void* ws, float* factor, hipStream_t s) {
+  SHAPECHK(eps2 && ws && factor, "cfg_rescale_factors: null operand");
+  SHAPECHK(B > 0 && per > 1, "cfg_rescale_factors: B=%d per=%lld", B, per);
+  double* part = (double*)ws;
+  hipLaunchKernelGGL(cfg_stats_kernel<false>, dim3(CFG_NBLK, B), dim3(256), 0, s, eps2, (long long)B * per, per, g, 0.f, part);
+  hipLaunchKernelGGL(cfg_factor_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, part, factor, B, per, rescale);
+  HIPCHK(hipGetLastError());
+  return PEA_OK;
+}
+
 // Inpainting inputs (tests/test_sdxl_zh_inpaint.py: VaeImageProcessor.preprocess of image and mask, the masking of __call__ and
 // the nearest-mode resize of prepare_mask_latents): per pixel of image [N][3][H][W] and mask [N][1][H][W], both in [0, 1],
 //   init = 2 image - 1,  masked = init * (mask < 0.5),  latent_mask[n][0][y/8][x/8] = (mask >= 0.5) at y % 8 == x % 8 == 0.

@@ -783,6 +783,70 @@ def euler_update_(sample, eps, noise, model_in, k_e, k_n, k_s, dup=1):
     return sample
 
 
+# ---- MultiDiffusion panoramas (Bar-Tal et al. 2023; pea_diffusion_amd/panorama.py is the loop)
+def _view_slots(views, vb):
+    if not 1 <= len(views) <= vb:
+        raise PeaError(f"{len(views)} views for a chunk of {vb} slots (1..vb)")
+    return (ctypes.c_int * (3 * len(views)))(*[int(v) for view in views for v in view])
+
+
+def views_gather(canvas, views, vb, window, k_s=1.0, dup=1, wrap_x=False, out=None):
+    """Canvas to UNet batch in one launch (pea_op_views_gather).  canvas fp32 [N,C,Hc,Wc]; views: the (n, y0, x0) of the chunk's
+    real slots, at most vb; window = (h, w).  -> fp32 [dup * vb, C, h, w]: out[d * vb + s] = crop of slot s * k_s; the slots past
+    len(views) repeat the last view."""
+    N, C, Hc, Wc = canvas.shape
+    h, w = int(window[0]), int(window[1])
+    if canvas.dtype != torch.float32 or not canvas.is_contiguous():
+        raise PeaError("views_gather: the canvas is a contiguous fp32 tensor")
+    if out is None:
+        out = torch.empty(int(dup) * int(vb), C, h, w, device=canvas.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != int(dup) * int(vb) * C * h * w or out.device != canvas.device:
+        raise PeaError(f"views_gather: out {tuple(out.shape)} {out.dtype}, expected contiguous fp32 [{int(dup) * int(vb)}, {C}, {h}, {w}]")
+    check(lib().pea_op_views_gather(ptr(canvas), ptr(out), _view_slots(views, vb), len(views), int(vb), int(dup), N, C, Hc, Wc, h, w,
+                                    int(bool(wrap_x)), float(k_s), stream_ptr()))
+    return out
+
+
+def views_merge_(canvas, eps, views, wy, wx, total, dup=1, guidance_scale=0.0, factor=None, first=True, last=True, wrap_x=False):
+    """UNet batch into the canvas in one launch, in place (pea_op_views_merge).  eps fp32 [dup * vb, C, h, w] ([uncond | text] for
+    dup 2); views: the (n, y0, x0) of the chunk's real slots (the slots behind them are not read).  Each canvas element gets the
+    sum, in ascending slot order, of wy[i] wx[j] e over the views that cover it, e = u + g (t - u) (`cfg_combine`'s expression) for
+    dup 2 and eps for dup 1, times factor[s] (`cfg_rescale_factors`) when given.  first: the sum starts at 0 (and elements outside
+    the chunk's views are set to 0), else at what the canvas holds; last: divided by total [N,Hc,Wc] in the same launch.
+    wy [h], wx [w], total: fp32 on the device.  -> canvas."""
+    N, C, Hc, Wc = canvas.shape
+    h, w = eps.shape[-2:]
+    vb = eps.shape[0] // int(dup)
+    for t in (canvas, eps, wy, wx, total, factor):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != canvas.device):
+            raise PeaError("views_merge_: canvas, eps, wy, wx, total and factor are contiguous fp32 tensors on one device")
+    if eps.dim() != 4 or eps.shape[0] != vb * int(dup) or eps.shape[1] != C or wy.numel() != h or wx.numel() != w or total.numel() != N * Hc * Wc:
+        raise PeaError(f"views_merge_: eps {tuple(eps.shape)}, wy {tuple(wy.shape)}, wx {tuple(wx.shape)}, total {tuple(total.shape)} for a "
+                       f"canvas {tuple(canvas.shape)} and dup={dup}")
+    if factor is not None and factor.numel() != vb:
+        raise PeaError(f"views_merge_: factor {tuple(factor.shape)}, expected [{vb}]")
+    check(lib().pea_op_views_merge(ptr(eps), ptr(canvas), _view_slots(views, vb), len(views), vb, int(dup), N, C, Hc, Wc, h, w,
+                                   int(bool(wrap_x)), float(guidance_scale), ptr(factor), ptr(wy), ptr(wx), ptr(total), int(bool(first)),
+                                   int(bool(last)), stream_ptr()))
+    return canvas
+
+
+def cfg_rescale_factors(noise_pred2, guidance_scale, guidance_rescale, out=None, workspace=None):
+    """The per-sample factors of `rescale_noise_cfg` alone (pea_op_cfg_rescale_factors): noise_pred2 fp32 [2B, ...],
+    unconditional half first -> fp32 [B], what `cfg_combine(..., guidance_rescale)` multiplies its result by."""
+    x = noise_pred2
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.shape[0] % 2:
+        raise PeaError(f"cfg_rescale_factors: noise_pred {tuple(x.shape)} {x.dtype}, expected contiguous fp32 with a batch of 2 B")
+    B = x.shape[0] // 2
+    if out is None:
+        out = torch.empty(B, device=x.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = torch.empty(lib().pea_op_cfg_combine_workspace_bytes(B), device=x.device, dtype=torch.uint8)
+    check(lib().pea_op_cfg_rescale_factors(ptr(x), B, x[0].numel(), float(guidance_scale), float(guidance_rescale), ptr(workspace),
+                                           ptr(out), stream_ptr()))
+    return out
+
+
 def lora_compose(acc, down, up, scale, out=None):
     """out[M][Kf] = acc + scale * up[M][r] @ down[r][Kf], fp32 on the GPU (acc any shape with M leading; out may be acc)."""
     M, r = up.shape[0], down.shape[0]

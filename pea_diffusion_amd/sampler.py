@@ -73,6 +73,10 @@ class DPMSolverMultistep:
     def scale_model_input(self, sample, timestep=None):
         return sample
 
+    def model_input_scale(self) -> float:
+        """the factor `scale_model_input` applies at the current position: 1 (alpha-space)"""
+        return 1.0
+
     @staticmethod
     def _alpha_sigma(sigma):
         a = 1.0 / math.sqrt(sigma * sigma + 1.0)
@@ -152,6 +156,10 @@ class LCMScheduler:
 
     def scale_model_input(self, sample, timestep=None):
         return sample
+
+    def model_input_scale(self) -> float:
+        """the factor `scale_model_input` applies at the current position: 1 (alpha-space)"""
+        return 1.0
 
     def boundary_scalings(self, t):
         """(c_skip, c_out) of the consistency parameterisation at timestep t"""
@@ -264,6 +272,14 @@ class EulerDiscrete:
         if self._buf is None or tuple(self._buf.shape) != shape or self._buf.device != x.device:
             self._buf = torch.empty(shape, device=x.device, dtype=torch.float32)
         return self._buf
+
+    def model_input_scale(self) -> float:
+        """the factor `scale_model_input` applies at the current position, 1 / sqrt(sigma^2 + 1), as the fp32 value its kernel
+        multiplies by"""
+        if self.timesteps is None:
+            raise ValueError("model_input_scale: call set_timesteps first")
+        sigma = float(self.sigmas[min(self._i, len(self.sigmas) - 1)])
+        return float(np.float32(1.0 / math.sqrt(sigma * sigma + 1.0)))
 
     def scale_model_input(self, sample, timestep=None, dup: int = 1):
         """`sample / sqrt(sigma^2 + 1)`, [dup * B, ...] fp32: the buffer the previous `step` filled when `sample` is that
