@@ -321,6 +321,89 @@ int pea_op_prefetch(const void* p, long long bytes, void* stream);
 int pea_op_adamw(float* w, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int step, float grad_scale, void* stream);
 
+/* pea_op_kd_loss over COMPACTED teacher tensors: tmap = device int[B] (or NULL = pea_op_kd_loss), the row of student sample b
+ * inside taps_t[] / eps_t; entries of samples with zh != 0 are not read (use -1).  A sample with KD weight and tmap[b] < 0 has
+ * no teacher: its terms are NaN.  nan_guard inspects only samples with KD weight (masked samples are never read).           */
+int pea_op_kd_loss_tmap(int ntaps, const void* const* taps_s, const void* const* taps_t, void* const* dtaps,
+                        const long long* per, const float* eps_s, const float* eps, const float* eps_t, float* deps_s,
+                        long long per_eps, const long long* zh, const int* tmap, int B, float feat_weight, int nan_guard,
+                        float grad_scale, float* losses, void* workspace, void* stream);
+
+/* ---- Glue kernels between the families above: one entry per launcher, used by the kernel-level parity tests.  bf16 tensors
+ * are 16-byte aligned and move 8 elements per lane: flat sizes n, per-sample sizes and leading dimensions are multiples of 8
+ * (PEA_E_SHAPE otherwise) unless stated.  accum != 0: the output is read and added to (fp32 sum, one rounding).
+ *   add: y = a + b;  silu / gelu (erf): y = f(x), dx (+)= dy f'(x);  accum: y (+)= x
+ *   geglu_bwd_il: the GEGLU backward on the interleaved stash of pea_op_gemm_geglu(stash_grad = 1): hg[r][2i] = gelu(gate_i),
+ *     hg[r][2i+1] = h_i gelu'(gate_i); dhg[r][2i], [2i+1] = dy[r][i] * those; inner % 4 == 0
+ *   select_rows: y[b] = mask[b] ? u[b] : c[b] for B rows of `per` elements (mask: one byte per row); ystride (0 = per, else >=
+ *     per) = elements between consecutive rows of y, whose tails [per, ystride) are not written.  _bwd: dc[b] = mask[b] ? 0 :
+ *     dy[b], du[b] = mask[b] ? dy[b] : 0, with dystride the row pitch of dy
+ *   mean_tokens: y[b][c] = mean_l x[b][l][c] (any C);  _bwd: dx[b][l][c] (+)= dy[b][c] / L
+ *   colsum: db[c] (+)= sum_r x[r][c], fp32, any C;  colsum_batched: out[b * ldo + c] = sum_p x[b][p][c] (C % 8 == 0, C <= 8192),
+ *     scratch of pea_op_colsum_batched_scratch_bytes; fixed summation order, no atomics
+ *   copy2d: y[r][0:C] (+)= x[r][0:C] with row pitches ldx / ldy (ldx = 0: one row broadcast)
+ *   transpose_bf16 / _f32_bf16: y[c * ldy + r] = x[r * C + c], any R, C, ldy >= R
+ *   nhwc_to_nchw_f32 / nchw_f32_to_nhwc: bf16 [B][HW][C] <-> fp32 [B][C][HW], any sizes; dH, dW != 0: the bf16 side is stored
+ *     depth-to-space ([B][dH/2][dW/2][(y&1)*2+(x&1)][C], dH * dW == HW)
+ *   pad_gather: torch Linear weight src fp32 [N_t][K_t] -> bf16 w[st_n][ldw] (and wt[st_k][ldwt] = its transpose, or NULL) with
+ *     heads padded from d to dp: mode 0 plain, 1 rows (row = head * dp + j), 2 columns, 3 rows interleaved (h_i, gate_i)
+ *   pad_head_vec: dst[h * dp + j] = j < d ? src[h * d + j] : 0;  permute_geglu_vec: dst[2i] = src[i], dst[2i+1] = src[inner + i]
+ *   cast_i64_f32;  fill_random_*: uniform [-scale, scale) (+ offset), a function of (seed, index) alone
+ *   splitk_reduce: out[m * ldo + n] (+)= sum_s part[s * stride + m * N + n], bf16 out; N, ldo, stride multiples of 4
+ *   rmsnorm_fwd: y = x * rsqrt(mean(x^2) + eps) * gamma;  layernorm_stats: stats[r] = (mean, rstd); C % 8 == 0, C <= 4096
+ *   softmax_rows: s[r][0:cols] = softmax(scale * s[r][0:cols]) in place, row pitch ld
+ *   residual_import: src [B][C][HW] fp32 (dtype 0) / bf16 (1), or bf16 [B][HW][C] (2) -> dst bf16 [B][HW][C] * scale
+ *   vae_posterior: moments = quant_conv(h) (1x1, C2 even, <= 8; NCHW fp32), latents = (mean + exp(0.5 clamp(logvar, -30, 20)) *
+ *     noise) * scaling; noise NULL = the mean; moments or latents may be NULL
+ *   vae_post_quant: out = post_quant_conv(z * inv_scaling), 1 <= C <= 8
+ *   embed_tokens: out[b][l] = tok[clamp(ids[b][l], 0, vocab - 1)] (+ pos[l] (+ type0)); pos NULL: T5; type0 NULL: CLIP
+ *   t5_rel_bias: bias[h][q * pitch + k] = rel[bucket(k - q)][h] * log2(e), bucket(d) = (d > 0 ? half_buckets : 0) +
+ *     dist_bucket[|d|] (device int[L]); columns [L, pitch) are not written
+ *   gather_eos: out[b] = x[b][first l with ids[b][l] == eos_id, else L - 1]; eos_id < 0: the first argmax of ids[b]
+ *   kv_len: len[b] = (index of the last id != pad_id) + 1, at least 1                                                    */
+int pea_op_add(const void* a, const void* b, void* y, long long n, void* stream);
+int pea_op_silu_fwd(const void* x, void* y, long long n, void* stream);
+int pea_op_silu_bwd(const void* x, const void* dy, void* dx, long long n, int accum, void* stream);
+int pea_op_gelu_fwd(const void* x, void* y, long long n, void* stream);
+int pea_op_gelu_bwd(const void* x, const void* dy, void* dx, long long n, int accum, void* stream);
+int pea_op_accum(const void* x, void* y, long long n, int accum, void* stream);
+int pea_op_geglu_bwd_il(const void* hg, const void* dy, void* dhg, long long rows, int inner, void* stream);
+int pea_op_select_rows(const void* c, const void* u, const void* mask, void* y, int B, long long per, long long ystride,
+                       void* stream);
+int pea_op_select_rows_bwd(const void* dy, const void* mask, void* dc, void* du, int B, long long per, long long dystride,
+                           void* stream);
+int pea_op_mean_tokens(const void* x, void* y, int B, int L, int C, void* stream);
+int pea_op_mean_tokens_bwd(const void* dy, void* dx, int B, int L, int C, int accum, void* stream);
+int pea_op_colsum(const void* x, float* db, int R, int C, int accum, void* stream);
+long long pea_op_colsum_batched_scratch_bytes(int B, int HW, int C);
+int pea_op_colsum_batched(const void* x, float* out, int B, int HW, int C, int ldo, void* scratch, void* stream);
+int pea_op_copy2d(const void* x, int ldx, void* y, int ldy, long long rows, int C, int accum, void* stream);
+int pea_op_transpose_bf16(const void* x, void* y, int R, int C, int ldy, void* stream);
+int pea_op_transpose_f32_bf16(const float* x, void* y, int R, int C, int ldy, void* stream);
+int pea_op_nhwc_to_nchw_f32(const void* x, float* y, int B, int HW, int C, int dH, int dW, void* stream);
+int pea_op_nchw_f32_to_nhwc(const float* x, void* y, int B, int HW, int C, int dH, int dW, void* stream);
+int pea_op_pad_gather(const float* src, int N_t, int K_t, int mode, int d, int dp, void* w, int ldw, void* wt, int ldwt, int st_n,
+                      int st_k, void* stream);
+int pea_op_pad_head_vec(const float* src, float* dst, int heads, int d, int dp, void* stream);
+int pea_op_permute_geglu_vec(const float* src, float* dst, int inner, void* stream);
+int pea_op_cast_i64_f32(const long long* x, float* y, long long n, void* stream);
+int pea_op_fill_random_bf16(void* p, long long n, unsigned long long seed, float scale, void* stream);
+int pea_op_fill_random_f32(float* p, long long n, unsigned long long seed, float scale, float offset, void* stream);
+int pea_op_splitk_reduce(const float* part, int nsplit, long long stride, void* out, int ldo, int M, int N, int accum, void* stream);
+int pea_op_rmsnorm_fwd(const void* x, const float* gamma, void* y, int R, int C, float eps, void* stream);
+int pea_op_layernorm_stats(const void* x, float* stats, int R, int C, float eps, void* stream);
+int pea_op_softmax_rows(void* s, long long rows, int cols, int ld, float scale, void* stream);
+int pea_op_residual_import(const void* src, int dtype, void* dst, int B, int C, long long HW, float scale, void* stream);
+int pea_op_vae_posterior(const float* h, const float* wq, const float* bq, const float* noise, float* moments, float* latents, int B,
+                         int C2, long long HW, float scaling, void* stream);
+int pea_op_vae_post_quant(const float* z, const float* w, const float* b, float* out, int B, int C, long long HW, float inv_scaling,
+                          void* stream);
+int pea_op_embed_tokens(const long long* ids, const void* tok, const void* pos, const void* type0, void* out, int B, int L, int width,
+                        int vocab, void* stream);
+int pea_op_t5_rel_bias(const float* rel, const int* dist_bucket, float* bias, int H, int L, int pitch, int half_buckets, void* stream);
+int pea_op_gather_eos(const long long* ids, const void* x, void* out, int B, int L, int width, long long eos_id, void* stream);
+int pea_op_kv_len(const long long* ids, int* len, int B, int L, long long pad_id, void* stream);
+
 
 /* ========================================================================== model level ====
  * The three plug-in surfaces of the reference, as opaque handles.                               */

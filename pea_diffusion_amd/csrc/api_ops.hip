@@ -398,10 +398,11 @@ int pea_op_cast_bf16_f32(const void* x, float* y, long long n, void* stream) {
   return launch_cast_bf16_f32((const bf16*)x, y, n, (hipStream_t)stream);
 }
 
-int pea_op_kd_loss(int ntaps, const void* const* taps_s, const void* const* taps_t, void* const* dtaps,
-                   const long long* per, const float* eps_s, const float* eps, const float* eps_t, float* deps_s,
-                   long long per_eps, const long long* zh, int B, float feat_weight, int nan_guard,
-                   float grad_scale, float* losses, void* workspace, void* stream) {
+// tmap: optional device int[B], the row of student sample b inside COMPACTED teacher tensors (KdLossP::tmap), null = row b
+int pea_op_kd_loss_tmap(int ntaps, const void* const* taps_s, const void* const* taps_t, void* const* dtaps,
+                        const long long* per, const float* eps_s, const float* eps, const float* eps_t, float* deps_s,
+                        long long per_eps, const long long* zh, const int* tmap, int B, float feat_weight, int nan_guard,
+                        float grad_scale, float* losses, void* workspace, void* stream) {
   if (ntaps < 0 || ntaps > PEA_MAX_TAPS) {
     pea_set_error("kd_loss: ntaps=%d out of range", ntaps);
     return PEA_E_SHAPE;
@@ -418,8 +419,15 @@ int pea_op_kd_loss(int ntaps, const void* const* taps_s, const void* const* taps
   }
   p.eps_s = eps_s; p.eps = eps; p.eps_t = eps_t; p.deps_s = deps_s; p.per_eps = per_eps; p.zh = zh; p.B = B;
   p.feat_weight = feat_weight; p.nan_guard = nan_guard; p.grad_scale = grad_scale; p.losses = losses;
-  p.partial = (float*)workspace;
+  p.partial = (float*)workspace; p.tmap = tmap;
   return launch_kd_loss(p, (hipStream_t)stream);
+}
+int pea_op_kd_loss(int ntaps, const void* const* taps_s, const void* const* taps_t, void* const* dtaps,
+                   const long long* per, const float* eps_s, const float* eps, const float* eps_t, float* deps_s,
+                   long long per_eps, const long long* zh, int B, float feat_weight, int nan_guard,
+                   float grad_scale, float* losses, void* workspace, void* stream) {
+  return pea_op_kd_loss_tmap(ntaps, taps_s, taps_t, dtaps, per, eps_s, eps, eps_t, deps_s, per_eps, zh, nullptr, B, feat_weight,
+                             nan_guard, grad_scale, losses, workspace, stream);
 }
 
 long long pea_op_attention_bwd_scratch_bytes(int B, int H, int Sq, int Skv, int nd) {
@@ -525,6 +533,121 @@ int pea_op_inpaint_prepare(const float* image, const float* mask, int N, int H, 
     return PEA_E_INVALID;
   }
   return launch_inpaint_prepare(image, mask, N, H, W, init_image, masked_image, latent_mask, (hipStream_t)stream);
+}
+
+// ---- the glue kernels between the families above (elementwise.hip, norm.hip, sampler.hip, gemm.hip, kdloss.hip), one
+// entry per launcher: a cast and a forward each, for the kernel-level parity tests (tests/test_glue_ops_gpu.py)
+int pea_op_add(const void* a, const void* b, void* y, long long n, void* stream) {
+  return launch_add((const bf16*)a, (const bf16*)b, (bf16*)y, n, (hipStream_t)stream);
+}
+int pea_op_silu_fwd(const void* x, void* y, long long n, void* stream) {
+  return launch_silu_fwd((const bf16*)x, (bf16*)y, n, (hipStream_t)stream);
+}
+int pea_op_silu_bwd(const void* x, const void* dy, void* dx, long long n, int accum, void* stream) {
+  return launch_silu_bwd((const bf16*)x, (const bf16*)dy, (bf16*)dx, n, accum, (hipStream_t)stream);
+}
+int pea_op_gelu_fwd(const void* x, void* y, long long n, void* stream) {
+  return launch_gelu_fwd((const bf16*)x, (bf16*)y, n, (hipStream_t)stream);
+}
+int pea_op_gelu_bwd(const void* x, const void* dy, void* dx, long long n, int accum, void* stream) {
+  return launch_gelu_bwd((const bf16*)x, (const bf16*)dy, (bf16*)dx, n, accum, (hipStream_t)stream);
+}
+int pea_op_accum(const void* x, void* y, long long n, int accum, void* stream) {
+  return launch_accum((const bf16*)x, (bf16*)y, n, accum, (hipStream_t)stream);
+}
+int pea_op_geglu_bwd_il(const void* hg, const void* dy, void* dhg, long long rows, int inner, void* stream) {
+  return launch_geglu_bwd_il((const bf16*)hg, (const bf16*)dy, (bf16*)dhg, rows, inner, (hipStream_t)stream);
+}
+int pea_op_select_rows(const void* c, const void* u, const void* mask, void* y, int B, long long per, long long ystride,
+                       void* stream) {
+  return launch_select_rows((const bf16*)c, (const bf16*)u, (const unsigned char*)mask, (bf16*)y, B, per, (hipStream_t)stream, ystride);
+}
+int pea_op_select_rows_bwd(const void* dy, const void* mask, void* dc, void* du, int B, long long per, long long dystride,
+                           void* stream) {
+  return launch_select_rows_bwd((const bf16*)dy, (const unsigned char*)mask, (bf16*)dc, (bf16*)du, B, per, (hipStream_t)stream, dystride);
+}
+int pea_op_mean_tokens(const void* x, void* y, int B, int L, int C, void* stream) {
+  return launch_mean_tokens((const bf16*)x, (bf16*)y, B, L, C, (hipStream_t)stream);
+}
+int pea_op_mean_tokens_bwd(const void* dy, void* dx, int B, int L, int C, int accum, void* stream) {
+  return launch_mean_tokens_bwd((const bf16*)dy, (bf16*)dx, B, L, C, accum, (hipStream_t)stream);
+}
+int pea_op_colsum(const void* x, float* db, int R, int C, int accum, void* stream) {
+  return launch_colsum((const bf16*)x, db, R, C, accum, (hipStream_t)stream);
+}
+long long pea_op_colsum_batched_scratch_bytes(int B, int HW, int C) { return (long long)colsum_batched_scratch_bytes(B, HW, C); }
+int pea_op_colsum_batched(const void* x, float* out, int B, int HW, int C, int ldo, void* scratch, void* stream) {
+  return launch_colsum_batched((const bf16*)x, out, B, HW, C, ldo, (float*)scratch, (hipStream_t)stream);
+}
+int pea_op_copy2d(const void* x, int ldx, void* y, int ldy, long long rows, int C, int accum, void* stream) {
+  return launch_copy2d((const bf16*)x, ldx, (bf16*)y, ldy, rows, C, accum, (hipStream_t)stream);
+}
+int pea_op_transpose_bf16(const void* x, void* y, int R, int C, int ldy, void* stream) {
+  return launch_transpose_bf16((const bf16*)x, (bf16*)y, R, C, ldy, (hipStream_t)stream);
+}
+int pea_op_transpose_f32_bf16(const float* x, void* y, int R, int C, int ldy, void* stream) {
+  return launch_transpose_f32_bf16(x, (bf16*)y, R, C, ldy, (hipStream_t)stream);
+}
+int pea_op_nhwc_to_nchw_f32(const void* x, float* y, int B, int HW, int C, int dH, int dW, void* stream) {
+  return launch_nhwc_to_nchw_f32((const bf16*)x, y, B, HW, C, (hipStream_t)stream, dH, dW);
+}
+int pea_op_nchw_f32_to_nhwc(const float* x, void* y, int B, int HW, int C, int dH, int dW, void* stream) {
+  return launch_nchw_f32_to_nhwc(x, (bf16*)y, B, HW, C, (hipStream_t)stream, dH, dW);
+}
+int pea_op_pad_gather(const float* src, int N_t, int K_t, int mode, int d, int dp, void* w, int ldw, void* wt, int ldwt, int st_n,
+                      int st_k, void* stream) {
+  return launch_pad_gather(src, N_t, K_t, mode, d, dp, (bf16*)w, ldw, (bf16*)wt, ldwt, st_n, st_k, (hipStream_t)stream);
+}
+int pea_op_pad_head_vec(const float* src, float* dst, int heads, int d, int dp, void* stream) {
+  return launch_pad_head_vec(src, dst, heads, d, dp, (hipStream_t)stream);
+}
+int pea_op_permute_geglu_vec(const float* src, float* dst, int inner, void* stream) {
+  return launch_permute_geglu_vec(src, dst, inner, (hipStream_t)stream);
+}
+int pea_op_cast_i64_f32(const long long* x, float* y, long long n, void* stream) {
+  return launch_cast_i64_f32(x, y, n, (hipStream_t)stream);
+}
+int pea_op_fill_random_bf16(void* p, long long n, unsigned long long seed, float scale, void* stream) {
+  return launch_fill_random_bf16((bf16*)p, n, seed, scale, (hipStream_t)stream);
+}
+int pea_op_fill_random_f32(float* p, long long n, unsigned long long seed, float scale, float offset, void* stream) {
+  return launch_fill_random_f32(p, n, seed, scale, offset, (hipStream_t)stream);
+}
+int pea_op_splitk_reduce(const float* part, int nsplit, long long stride, void* out, int ldo, int M, int N, int accum, void* stream) {
+  return launch_splitk_reduce(part, nsplit, stride, (bf16*)out, ldo, M, N, accum, (hipStream_t)stream);
+}
+int pea_op_rmsnorm_fwd(const void* x, const float* gamma, void* y, int R, int C, float eps, void* stream) {
+  return launch_rmsnorm_fwd((const bf16*)x, gamma, (bf16*)y, R, C, eps, (hipStream_t)stream);
+}
+int pea_op_layernorm_stats(const void* x, float* stats, int R, int C, float eps, void* stream) {
+  return launch_layernorm_stats((const bf16*)x, stats, R, C, eps, (hipStream_t)stream);
+}
+int pea_op_softmax_rows(void* s, long long rows, int cols, int ld, float scale, void* stream) {
+  return launch_softmax_rows((bf16*)s, rows, cols, ld, scale, (hipStream_t)stream);
+}
+int pea_op_residual_import(const void* src, int dtype, void* dst, int B, int C, long long HW, float scale, void* stream) {
+  return launch_residual_import(src, dtype, (bf16*)dst, B, C, HW, scale, (hipStream_t)stream);
+}
+int pea_op_vae_posterior(const float* h, const float* wq, const float* bq, const float* noise, float* moments, float* latents, int B,
+                         int C2, long long HW, float scaling, void* stream) {
+  return launch_vae_posterior(h, wq, bq, noise, moments, latents, B, C2, HW, scaling, (hipStream_t)stream);
+}
+int pea_op_vae_post_quant(const float* z, const float* w, const float* b, float* out, int B, int C, long long HW, float inv_scaling,
+                          void* stream) {
+  return launch_vae_post_quant(z, w, b, out, B, C, HW, inv_scaling, (hipStream_t)stream);
+}
+int pea_op_embed_tokens(const long long* ids, const void* tok, const void* pos, const void* type0, void* out, int B, int L, int width,
+                        int vocab, void* stream) {
+  return launch_embed_tokens(ids, (const bf16*)tok, (const bf16*)pos, (const bf16*)type0, (bf16*)out, B, L, width, vocab, (hipStream_t)stream);
+}
+int pea_op_t5_rel_bias(const float* rel, const int* dist_bucket, float* bias, int H, int L, int pitch, int half_buckets, void* stream) {
+  return launch_t5_rel_bias(rel, dist_bucket, bias, H, L, pitch, half_buckets, (hipStream_t)stream);
+}
+int pea_op_gather_eos(const long long* ids, const void* x, void* out, int B, int L, int width, long long eos_id, void* stream) {
+  return launch_gather_eos(ids, (const bf16*)x, (bf16*)out, B, L, width, eos_id, (hipStream_t)stream);
+}
+int pea_op_kv_len(const long long* ids, int* len, int B, int L, long long pad_id, void* stream) {
+  return launch_kv_len(ids, len, B, L, pad_id, (hipStream_t)stream);
 }
 
 }  // extern "C"

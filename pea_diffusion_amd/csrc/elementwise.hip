@@ -691,7 +691,15 @@ __device__ __forceinline__ float rng_uniform(unsigned long long seed, unsigned l
   return (float)((z >> 40) & 0xFFFFFF) * (2.0f / 16777216.0f) - 1.0f;
 }
 __global__ void fill_random_bf16_kernel(bf16* p, long long n, unsigned long long seed, float scale) {
-  EW_LOOP(i, n) p[i] = (bf16)(rng_uniform(seed, (unsigned long long)i) * scale);
+  // the fp32 value lies in [-|scale|, |scale|); rounding to bf16 may land ON |scale| (about one value in 2^10) or, where the
+  // scale is no bf16 number, beyond either end: those move one bf16 towards zero, so the stored values keep the half-open range
+  const float lim = fabsf(scale);
+  EW_LOOP(i, n) {
+    bf16 b = (bf16)(rng_uniform(seed, (unsigned long long)i) * scale);
+    if (lim > 0.f && ((float)b >= lim || (float)b < -lim))
+      b = __builtin_bit_cast(bf16, (unsigned short)(__builtin_bit_cast(unsigned short, b) - 1));
+    p[i] = b;
+  }
 }
 __global__ void fill_random_f32_kernel(float* p, long long n, unsigned long long seed, float scale, float offset) {
   EW_LOOP(i, n) p[i] = rng_uniform(seed, (unsigned long long)i) * scale + offset;
@@ -1128,7 +1136,8 @@ int launch_gather_eos(const long long* ids, const bf16* x, bf16* out, int B, int
   HIPCHK(hipGetLastError());
   return PEA_OK;
 }
-// len[b] = number of leading tokens != pad_id  (BERT-style right padding -> key count for the attention mask)
+// len[b] = index of the LAST token != pad_id, plus 1 (a pad id in the middle of a prompt is counted as a key; with BERT-style
+// right padding this is the number of real tokens -> key count for the attention mask); a row of pad ids only gives 1
 __global__ void kv_len_kernel(const long long* __restrict__ ids, int* __restrict__ len, int B, int L, long long pad_id) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;

@@ -2330,6 +2330,9 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, int nsplit,
 }
 int launch_splitk_reduce(const float* part, int nsplit, long long stride, bf16* out, int ldo, int M, int N, int accum,
                          hipStream_t s) {
+  // the kernel moves 4 columns per thread (one 16-byte load, one 8-byte store): N % 4 columns would be dropped without a word
+  SHAPECHK(M > 0 && N > 0 && nsplit >= 1 && N % 4 == 0 && ldo % 4 == 0 && ldo >= N && stride % 4 == 0,
+           "splitk_reduce: M=%d N=%d ldo=%d nsplit=%d stride=%lld (N, ldo and stride multiples of 4, ldo >= N)", M, N, ldo, nsplit, stride);
   const long long total = (long long)M * (N / 4);
   const int grid = (int)(cdivl(total, 256) < 2048 ? cdivl(total, 256) : 2048);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, s, part, nsplit, stride, out, ldo, M, N, accum);

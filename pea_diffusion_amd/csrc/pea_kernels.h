@@ -329,8 +329,12 @@ struct KdLossP {
   float* partial;                  // [3 + ntaps] fp32 sums (zeroed by the launcher)
   float* losses;                   // [4]: total, noise, logits, features (written by a finishing kernel)
   const int* tap_finite_flags;     // unused (SD1.5 NaN guard handled through `nan_guard`)
-  int nan_guard;
-  float grad_scale;                // multiplies every seed (1/world for DP averaging, usually 1)
+  int nan_guard;                   // SD1.5 guard: a tap whose masked MSE sum is not finite is dropped (no loss term, zero seeds).  Only
+                                   // samples WITH KD weight (zh_or_not == 0) are inspected: masked samples are never read (with tmap their
+                                   // teacher rows do not exist).  train_sd_zh.py:246-268 and oracle.step_ref.kd_losses test mse * (1 - zh),
+                                   // where NaN * 0 = NaN, so there a non-finite value in a MASKED sample drops the tap too; here the tap
+                                   // is kept and the masked sample contributes nothing ("KD loss NaN guard")
+  float grad_scale;               // multiplies every seed (1/world for DP averaging, usually 1)
   const int* tmap;                 // optional device int[B]: teacher sample index of student sample b inside ft[] / eps_t (compacted
                                    // teacher rows, Trainer::live_teacher_mask); entries of samples with zh_or_not != 0 are not read
   int kd_samples_hint;             // profiling only: samples with zh_or_not == 0 (their taps are READ; the others' seeds are only

@@ -870,3 +870,264 @@ def clip_score(image_embeds, text_embeds, w=2.5, clamp=True):
     out = torch.empty(a.shape[0], device=a.device, dtype=torch.float32)
     check(lib().pea_op_clip_score(ptr(a), ptr(t), ptr(out), a.shape[0], a.shape[1], float(w), int(bool(clamp)), stream_ptr()))
     return out
+
+
+# ---- glue kernels (include/pea_hip.h, "Glue kernels between the families"): thin calls for the kernel-level parity tests.
+# Where a kernel writes a strided or partial output, or accumulates, the caller hands over the (pre-filled) output buffer.
+def _out(y, like=None, shape=None, dtype=BF):
+    if y is not None:
+        return y
+    return torch.empty_like(like) if shape is None else torch.empty(*shape, device=like.device, dtype=dtype)
+
+
+def add(a, b, y=None, n=None):
+    y = _out(y, a)
+    check(lib().pea_op_add(ptr(a), ptr(b), ptr(y), a.numel() if n is None else n, stream_ptr()))
+    return y
+
+
+def silu_fwd(x, y=None, n=None):
+    y = _out(y, x)
+    check(lib().pea_op_silu_fwd(ptr(x), ptr(y), x.numel() if n is None else n, stream_ptr()))
+    return y
+
+
+def gelu_fwd(x, y=None, n=None):
+    y = _out(y, x)
+    check(lib().pea_op_gelu_fwd(ptr(x), ptr(y), x.numel() if n is None else n, stream_ptr()))
+    return y
+
+
+def silu_bwd(x, dy, dx=None, accum=False, n=None):
+    dx = _out(dx, x)
+    check(lib().pea_op_silu_bwd(ptr(x), ptr(dy), ptr(dx), x.numel() if n is None else n, int(accum), stream_ptr()))
+    return dx
+
+
+def gelu_bwd(x, dy, dx=None, accum=False, n=None):
+    dx = _out(dx, x)
+    check(lib().pea_op_gelu_bwd(ptr(x), ptr(dy), ptr(dx), x.numel() if n is None else n, int(accum), stream_ptr()))
+    return dx
+
+
+def accum_(x, y, accum=True, n=None):
+    check(lib().pea_op_accum(ptr(x), ptr(y), x.numel() if n is None else n, int(accum), stream_ptr()))
+    return y
+
+
+def sumpool2_(x, y, accum=False):
+    """x [B,2H,2W,C] -> y [B,H,W,C] (+)= the 2 x 2 sums"""
+    B, H, W, C = y.shape
+    check(lib().pea_op_sumpool2(ptr(x), ptr(y), B, H, W, C, int(accum), stream_ptr()))
+    return y
+
+
+def geglu_bwd_il(hg, dy, dhg=None):
+    dhg = _out(dhg, hg)
+    check(lib().pea_op_geglu_bwd_il(ptr(hg), ptr(dy), ptr(dhg), dy.shape[0], dy.shape[1], stream_ptr()))
+    return dhg
+
+
+def select_rows_(c, u, mask, y, B, per, ystride=0):
+    """mask: uint8 / bool [>= B] on the device (a slice selects the first row's byte)"""
+    check(lib().pea_op_select_rows(ptr(c), ptr(u), ptr(mask), ptr(y), B, per, ystride, stream_ptr()))
+    return y
+
+
+def select_rows_bwd_(dy, mask, dc, du, B, per, dystride=0):
+    check(lib().pea_op_select_rows_bwd(ptr(dy), ptr(mask), ptr(dc), ptr(du), B, per, dystride, stream_ptr()))
+    return dc, du
+
+
+def mean_tokens(x, y=None):
+    B, L, C = x.shape
+    y = _out(y, x, (B, C))
+    check(lib().pea_op_mean_tokens(ptr(x), ptr(y), B, L, C, stream_ptr()))
+    return y
+
+
+def mean_tokens_bwd_(dy, dx, accum=False):
+    B, L, C = dx.shape
+    check(lib().pea_op_mean_tokens_bwd(ptr(dy), ptr(dx), B, L, C, int(accum), stream_ptr()))
+    return dx
+
+
+def colsum_(x, db, accum=False):
+    R, C = x.shape
+    check(lib().pea_op_colsum(ptr(x), ptr(db), R, C, int(accum), stream_ptr()))
+    return db
+
+
+def colsum_batched_(x, out, ldo=None):
+    """x bf16 [B,HW,C] -> out fp32 [B][ldo] (columns [C, ldo) are left alone)"""
+    B, HW, C = x.shape
+    ws = torch.empty(lib().pea_op_colsum_batched_scratch_bytes(B, HW, C), device=x.device, dtype=torch.uint8)
+    check(lib().pea_op_colsum_batched(ptr(x), ptr(out), B, HW, C, C if ldo is None else ldo, ptr(ws), stream_ptr()))
+    return out
+
+
+def copy2d_(x, ldx, y, ldy, rows, C, accum=False):
+    check(lib().pea_op_copy2d(ptr(x), ldx, ptr(y), ldy, rows, C, int(accum), stream_ptr()))
+    return y
+
+
+def transpose_(x, y, R, C, ldy):
+    """y[c * ldy + r] = x[r][c]; x bf16 or fp32, y bf16"""
+    fn = lib().pea_op_transpose_f32_bf16 if x.dtype == torch.float32 else lib().pea_op_transpose_bf16
+    check(fn(ptr(x), ptr(y), R, C, ldy, stream_ptr()))
+    return y
+
+
+def nhwc_to_nchw_f32(x, B, HW, C, d2s_hw=None, y=None):
+    y = _out(y, x, (B, C, HW), torch.float32)
+    dH, dW = d2s_hw or (0, 0)
+    check(lib().pea_op_nhwc_to_nchw_f32(ptr(x), ptr(y), B, HW, C, dH, dW, stream_ptr()))
+    return y
+
+
+def nchw_f32_to_nhwc(x, B, HW, C, d2s_hw=None, y=None):
+    y = _out(y, x, (B, HW, C), BF)
+    dH, dW = d2s_hw or (0, 0)
+    check(lib().pea_op_nchw_f32_to_nhwc(ptr(x), ptr(y), B, HW, C, dH, dW, stream_ptr()))
+    return y
+
+
+def pad_gather_(src, mode, d, dp, w, ldw, wt, ldwt, st_n, st_k):
+    N_t, K_t = src.shape
+    check(lib().pea_op_pad_gather(ptr(src), N_t, K_t, mode, d, dp, ptr(w), ldw, ptr(wt), ldwt, st_n, st_k, stream_ptr()))
+    return w, wt
+
+
+def pad_head_vec(src, heads, d, dp, dst=None):
+    dst = _out(dst, src, (heads * dp,), torch.float32)
+    check(lib().pea_op_pad_head_vec(ptr(src), ptr(dst), heads, d, dp, stream_ptr()))
+    return dst
+
+
+def permute_geglu_vec(src, dst=None):
+    dst = _out(dst, src)
+    check(lib().pea_op_permute_geglu_vec(ptr(src), ptr(dst), src.numel() // 2, stream_ptr()))
+    return dst
+
+
+def cast_i64_f32(x, y=None):
+    y = _out(y, x, tuple(x.shape), torch.float32)
+    check(lib().pea_op_cast_i64_f32(ptr(x), ptr(y), x.numel(), stream_ptr()))
+    return y
+
+
+def cast_f32_bf16(x, y=None):
+    y = _out(y, x, tuple(x.shape), BF)
+    check(lib().pea_op_cast_f32_bf16(ptr(x), ptr(y), x.numel(), stream_ptr()))
+    return y
+
+
+def cast_bf16_f32(x, y=None):
+    y = _out(y, x, tuple(x.shape), torch.float32)
+    check(lib().pea_op_cast_bf16_f32(ptr(x), ptr(y), x.numel(), stream_ptr()))
+    return y
+
+
+def fill_random_(p, seed, scale, offset=0.0, n=None):
+    n = p.numel() if n is None else n
+    if p.dtype == torch.float32:
+        check(lib().pea_op_fill_random_f32(ptr(p), n, seed, float(scale), float(offset), stream_ptr()))
+    else:
+        check(lib().pea_op_fill_random_bf16(ptr(p), n, seed, float(scale), stream_ptr()))
+    return p
+
+
+def splitk_reduce_(part, nsplit, stride, out, ldo, M, N, accum=False):
+    check(lib().pea_op_splitk_reduce(ptr(part), nsplit, stride, ptr(out), ldo, M, N, int(accum), stream_ptr()))
+    return out
+
+
+def rmsnorm_fwd_(x, gamma, y, R, C, eps=1e-6):
+    check(lib().pea_op_rmsnorm_fwd(ptr(x), ptr(gamma), ptr(y), R, C, eps, stream_ptr()))
+    return y
+
+
+def layernorm_stats_(x, stats, R, C, eps=1e-5):
+    check(lib().pea_op_layernorm_stats(ptr(x), ptr(stats), R, C, eps, stream_ptr()))
+    return stats
+
+
+def layernorm_fwd_(x, gamma, beta, y, stats, R, C, eps=1e-5):
+    check(lib().pea_op_layernorm_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(stats), R, C, eps, stream_ptr()))
+    return y, stats
+
+
+def layernorm_bwd_(x, dy, gamma, stats, dx, R, C, accum=False):
+    check(lib().pea_op_layernorm_bwd(ptr(x), ptr(dy), ptr(gamma), ptr(stats), ptr(dx), None, None, R, C, int(accum), stream_ptr()))
+    return dx
+
+
+def softmax_rows_(s, rows, cols, ld, scale=1.0):
+    check(lib().pea_op_softmax_rows(ptr(s), rows, cols, ld, float(scale), stream_ptr()))
+    return s
+
+
+def residual_import(src, dtype, B, C, HW, scale, dst=None):
+    dst = _out(dst, src, (B, HW, C), BF)
+    check(lib().pea_op_residual_import(ptr(src), dtype, ptr(dst), B, C, HW, float(scale), stream_ptr()))
+    return dst
+
+
+def vae_posterior(h, wq, bq, noise, scaling, want_moments=True, want_latents=True):
+    B, C2 = h.shape[:2]
+    HW = h[0, 0].numel()
+    mom = torch.empty_like(h) if want_moments else None
+    lat = torch.empty(B, C2 // 2, *h.shape[2:], device=h.device, dtype=torch.float32) if want_latents else None
+    check(lib().pea_op_vae_posterior(ptr(h), ptr(wq), ptr(bq), ptr(noise), ptr(mom), ptr(lat), B, C2, HW, float(scaling), stream_ptr()))
+    return mom, lat
+
+
+def vae_post_quant(z, w, b, inv_scaling):
+    out = torch.empty_like(z)
+    check(lib().pea_op_vae_post_quant(ptr(z), ptr(w), ptr(b), ptr(out), z.shape[0], z.shape[1], z[0, 0].numel(), float(inv_scaling),
+                                      stream_ptr()))
+    return out
+
+
+def embed_tokens(ids, tok, pos=None, type0=None):
+    B, L = ids.shape
+    vocab, width = tok.shape
+    out = torch.empty(B, L, width, device=tok.device, dtype=BF)
+    check(lib().pea_op_embed_tokens(ptr(ids), ptr(tok), ptr(pos), ptr(type0), ptr(out), B, L, width, vocab, stream_ptr()))
+    return out
+
+
+def t5_rel_bias_(rel, dist_bucket, bias, H, L, pitch):
+    """rel fp32 [num_buckets][H], dist_bucket int32 [L], bias fp32 [H][L][pitch] (columns [L, pitch) left alone)"""
+    check(lib().pea_op_t5_rel_bias(ptr(rel), ptr(dist_bucket), ptr(bias), H, L, pitch, rel.shape[0] // 2, stream_ptr()))
+    return bias
+
+
+def gather_eos(ids, x, eos_id):
+    B, L, width = x.shape
+    out = torch.empty(B, width, device=x.device, dtype=BF)
+    check(lib().pea_op_gather_eos(ptr(ids), ptr(x), ptr(out), B, L, width, eos_id, stream_ptr()))
+    return out
+
+
+def kv_len(ids, pad_id):
+    B, L = ids.shape
+    out = torch.empty(B, device=ids.device, dtype=torch.int32)
+    check(lib().pea_op_kv_len(ptr(ids), ptr(out), B, L, pad_id, stream_ptr()))
+    return out
+
+
+def kd_loss_tmap(taps_s, taps_t, eps_s, eps, eps_t, zh, tmap, feat_weight=0.1, nan_guard=False, grad_scale=1.0):
+    """kd_loss over compacted teacher tensors: tmap int32 [B] on the device (row of sample b in taps_t / eps_t), or None"""
+    n = len(taps_s)
+    B = eps_s.shape[0]
+    dt = [torch.empty_like(t) for t in taps_s]
+    de = torch.empty_like(eps_s)
+    arr = ctypes.c_void_p * max(n, 1)
+    a_s, a_t, a_d = arr(*[t.data_ptr() for t in taps_s]), arr(*[t.data_ptr() for t in taps_t]), arr(*[t.data_ptr() for t in dt])
+    per = (ctypes.c_longlong * max(n, 1))(*[t[0].numel() for t in taps_s])
+    losses = torch.empty(4, device=eps_s.device, dtype=torch.float32)
+    ws = torch.empty(lib().pea_op_kd_loss_workspace_bytes(n, per, eps_s[0].numel(), B), device=eps_s.device, dtype=torch.uint8)
+    check(lib().pea_op_kd_loss_tmap(n, a_s, a_t, a_d, per, ptr(eps_s), ptr(eps), ptr(eps_t), ptr(de), eps_s[0].numel(), ptr(zh),
+                                    ptr(tmap), B, feat_weight, int(nan_guard), grad_scale, ptr(losses), ptr(ws), stream_ptr()))
+    return losses, dt, de
