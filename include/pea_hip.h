@@ -38,7 +38,7 @@ int pea_device_count(void);
 
 /* ======================================================================== operator level ====
  * One entry point per hand-written kernel family; used by the parity tests and by callers that
- * want a single op.  act: 0 none, 1 GELU(erf), 2 SiLU.                                         */
+ * want a single op.  act: 0 none, 1 GELU(erf), 2 SiLU, 3 quick-GELU x * sigmoid(1.702 x).      */
 
 /* C[M][N] = act(alpha * A[M][K] . W[N][K]^T + bias[n] + rowvec[m / rows_per_batch][n]) + res[m][n]
  * (torch.nn.Linear / F.linear inside the UNet and the adapter, train_sdxl_zh.py:48-55,62-64).
@@ -90,6 +90,28 @@ int pea_op_conv3x3(const void* x, const void* w, void* y, int B, int Hs, int Ws,
 /* torch conv weight [Co][Ci][3][3] fp32 -> bf16 packed; dgrad=1 gives the flipped/transposed
  * weights w'[ci][(2-ky,2-kx,co)] whose forward conv is the data gradient.                        */
 int pea_op_pack_conv(const float* w, void* out, int Co, int Ci, int dgrad, void* stream);
+/* The GEMM / conv forms that only the model tape fills (GemmP fields no entry above can set), one thin entry each:
+ *   pea_op_gemm_geglu_tanh: pea_op_gemm_geglu with the gate's activation as an argument: geglu_tanh 0 = GELU(erf), 1 = gelu_new,
+ *       0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3))) (T5 v1.1 gated-gelu).  The gradient-form stash (stash_grad) exists for
+ *       the erf gate only and is refused with geglu_tanh.
+ *   pea_op_gemm_splitk: fp32 partial s (0 <= s < ksplit) = alpha * A[:, Ks] . W[:, Ks]^T over K-steps
+ *       Ks = [s * per, min((s + 1) * per, K / 64)), per = ceil(K / 64 / ksplit), written [M][N] with rows ldc apart at
+ *       part + s * split_stride (an empty range stores zeros); split_stride >= (M - 1) * ldc + N, split_stride % 4 == 0.
+ *       pea_op_splitk_reduce adds the partials (the backward of the stacked cross-attention K|V projection).
+ *   pea_op_conv3x3_ex: pea_op_conv3x3 on a plain source with ldw / ldc / ldres as arguments (Cout columns written into rows
+ *       ldc >= Cout wide, the other columns left alone), `act` in the epilogue (0 none, 1 GELU(erf), 2 SiLU, 3 quick-GELU
+ *       x * sigmoid(1.702 x)), Cin the STORED channel width of x (% 64; weights from pea_op_pack_conv_padded) and pad_off:
+ *       0 = padding 1 on every side (Ho = ceil(Hs / stride)); 1 = F.pad(x, (0,1,0,1)) then stride 2 without padding, the VAE
+ *       encoder's Downsample2D(padding=0): Ho = Hs / 2, Wo = Ws / 2, even sides only.
+ *   pea_op_pack_conv_padded: pea_op_pack_conv(dgrad = 0) for an input stored Cip >= Ci channels wide: out bf16 [Co][9 Cip],
+ *       zeros in the padding channels (ControlNet conditioning embedding).                                                  */
+int pea_op_gemm_geglu_tanh(const void* A, int lda, const void* W, int ldw, const float* bias, void* y, void* stash, int M, int N,
+                           int K, int stash_grad, int stash_rows, int geglu_tanh, void* stream);
+int pea_op_gemm_splitk(const void* A, int lda, const void* W, int ldw, float* part, int ldc, long long split_stride, int M, int N,
+                       int K, float alpha, int ksplit, void* stream);
+int pea_op_conv3x3_ex(const void* x, const void* w, int ldw, void* y, int ldc, int B, int Hs, int Ws, int Cin, int Cout,
+                      int stride, int pad_off, int act, const float* bias, const void* res, int ldres, void* stream);
+int pea_op_pack_conv_padded(const float* w, void* out, int Co, int Ci, int Cip, void* stream);
 /* conv3x3(interpolate(x, 2x nearest)) -- diffusers Upsample2D, the UNet's up_blocks[i].upsamplers[0] -- in its sub-pixel
  * form: per output parity (y&1, x&1) a 2 x 2 kernel of summed taps over the SOURCE (16 tap products per source pixel and
  * channel pair instead of the 36 of a 3 x 3 gather over the upsampled image).

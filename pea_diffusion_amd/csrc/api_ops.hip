@@ -108,6 +108,31 @@ int pea_op_gemm_geglu(const void* A, int lda, const void* W, int ldw, const floa
   return launch_gemm(p, (hipStream_t)stream);
 }
 
+// pea_op_gemm_geglu with the gate's activation as an argument (GemmP::geglu_tanh: the T5 v1.1 gated gelu_new)
+int pea_op_gemm_geglu_tanh(const void* A, int lda, const void* W, int ldw, const float* bias, void* y, void* stash, int M, int N,
+                           int K, int stash_grad, int stash_rows, int geglu_tanh, void* stream) {
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = ldw; p.bias = bias;
+  p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.rows_per_batch = 1;
+  p.geglu_y = (bf16*)y; p.ldy = N / 2; p.C = stash; p.ldc = N; p.stash_grad = stash_grad; p.stash_rows = stash_rows;
+  p.geglu_tanh = geglu_tanh ? 1 : 0;
+  return launch_gemm(p, (hipStream_t)stream);
+}
+
+// split-K (the tape's stacked K|V projection backward): fp32 partial s = alpha * A[:, K range s] . W[:, K range s]^T at
+// part + s * split_stride, rows ldc apart; pea_op_splitk_reduce adds them
+int pea_op_gemm_splitk(const void* A, int lda, const void* W, int ldw, float* part, int ldc, long long split_stride, int M, int N,
+                       int K, float alpha, int ksplit, void* stream) {
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = ldw; p.C = part; p.ldc = ldc;
+  SHAPECHK(ksplit >= 2, "gemm_splitk: ksplit=%d (at least two splits)", ksplit);
+  p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.rows_per_batch = 1; p.out_f32 = 1;
+  p.ksplit = ksplit; p.split_stride = split_stride;
+  return launch_gemm(p, (hipStream_t)stream);
+}
+
 int pea_op_ln_linear(const void* x, const float* gamma, const float* beta, const void* W, const float* bias, void* y,
                      void* geglu_y, int M, int N, int K, float eps, void* Wf, float* svec, float* tvec, float* stats,
                      void* stream) {
@@ -142,6 +167,32 @@ int pea_op_conv3x3(const void* x, const void* w, void* y, int B, int Hs, int Ws,
   p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = 9 * Cin; p.alpha = 1.f; p.bias = bias;
   p.rowvec = (const bf16*)rowvec; p.ldrv = ldrv; p.rows_per_batch = p.Ho * p.Wo;
   p.res = (const bf16*)res; p.ldres = Cout;
+  int rc = pea_zero_page(&p.zeros);
+  if (rc) return rc;
+  return launch_gemm(p, (hipStream_t)stream);
+}
+
+// The conv forms the tape's OP_CONV3 fills beyond pea_op_conv3x3: pad_off (the VAE encoder's Downsample2D(padding=0):
+// F.pad (0,1,0,1), then stride 2), an activation in the epilogue, Cin as the STORED width of x (zero-padded channels,
+// w = pea_op_pack_conv_padded), ldw / ldc / ldres as arguments (Cout columns written into rows ldc wide)
+int pea_op_conv3x3_ex(const void* x, const void* w, int ldw, void* y, int ldc, int B, int Hs, int Ws, int Cin, int Cout,
+                      int stride, int pad_off, int act, const float* bias, const void* res, int ldres, void* stream) {
+  SHAPECHK(B > 0 && Hs > 0 && Ws > 0 && (stride == 1 || stride == 2) && (pad_off == 0 || pad_off == 1) && act >= 0 && act <= 3,
+           "conv3x3_ex: B=%d Hs=%d Ws=%d stride=%d pad_off=%d act=%d", B, Hs, Ws, stride, pad_off, act);
+  SHAPECHK(!pad_off || (stride == 2 && Hs % 2 == 0 && Ws % 2 == 0),
+           "conv3x3_ex: pad_off is the stride-2 downsampler's (0,1,0,1) padding on even sides (stride=%d Hs=%d Ws=%d)", stride, Hs, Ws);
+  SHAPECHK(ldc >= Cout && ldw >= 9 * Cin && (!res || ldres >= Cout), "conv3x3_ex: ldc=%d ldres=%d vs Cout=%d, ldw=%d vs 9*Cin=%d",
+           ldc, ldres, Cout, ldw, 9 * Cin);
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.mode = 1;
+  p.A = (const bf16*)x; p.W = (const bf16*)w; p.ldw = ldw; p.C = y; p.ldc = ldc;
+  p.Hs = Hs; p.Ws = Ws; p.Cin = Cin; p.stride = stride; p.pad_off = pad_off;
+  p.Ho = stride == 2 ? (pad_off ? Hs / 2 : (Hs + 1) / 2) : Hs;
+  p.Wo = stride == 2 ? (pad_off ? Ws / 2 : (Ws + 1) / 2) : Ws;
+  p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = 9 * Cin; p.alpha = 1.f; p.bias = bias; p.act = act;
+  p.rows_per_batch = p.Ho * p.Wo;
+  p.res = (const bf16*)res; p.ldres = ldres;
   int rc = pea_zero_page(&p.zeros);
   if (rc) return rc;
   return launch_gemm(p, (hipStream_t)stream);
@@ -204,6 +255,11 @@ int pea_op_pack_conv_subpixel(const float* w, void* out, int Co, int Ci, int dgr
 int pea_op_pack_conv(const float* w, void* out, int Co, int Ci, int dgrad, void* stream) {
   return dgrad ? launch_pack_conv_dgrad(w, (bf16*)out, Co, Ci, (hipStream_t)stream)
                : launch_pack_conv_fwd(w, (bf16*)out, Co, Ci, (hipStream_t)stream);
+}
+// forward pack for an input stored Cip >= Ci channels wide: out [Co][9 Cip], the padding channels' weights zero
+int pea_op_pack_conv_padded(const float* w, void* out, int Co, int Ci, int Cip, void* stream) {
+  SHAPECHK(Co > 0 && Ci > 0 && Cip >= Ci, "pack_conv_padded: Co=%d Ci=%d stored as %d", Co, Ci, Cip);
+  return launch_pack_conv_fwd(w, (bf16*)out, Co, Ci, (hipStream_t)stream, Cip);
 }
 int pea_op_pack_conv_out(const float* w, float* out, int Co, int Ci, void* stream) {
   return launch_pack_conv_out(w, out, Co, Ci, (hipStream_t)stream);

@@ -1846,13 +1846,19 @@ int launch_gemm(const GemmP& p_in, hipStream_t stream) {
   if (p.pf_bytes > env.pf_max) p.pf_bytes = env.pf_max;
   SHAPECHK(p.qscale_cols % 16 == 0 && p.qscale_cols >= 0 && p.qscale_cols <= p.N && (!p.qscale_cols || (!p.act && !p.geglu_y && !p.gbwd_pre && p.ksplit <= 1)),
            "gemm: qscale_cols=%d must be a multiple of 16 within N, on a plain (no activation / GEGLU / split-K) epilogue", p.qscale_cols);
-  if (!g_num_cus) HIPCHK(gemm_query_cus());
-  const GemmDecision d = gemm_decide(p, g_num_cus, g_gemm_variant, env);
-  p.epi_fast = d.epi_fast;
+  // refusals that depend on the shape alone: ahead of the CU query, so they answer without a device
   if (p.ksplit > 1) {
     SHAPECHK(p.out_f32 && !p.accum_f32 && !p.bias && !p.res && !p.rowvec && !p.preact && p.act == 0 && p.mode == 0,
              "gemm: split-K writes plain fp32 partials");
+    // partial s is the [M][ldc] matrix at C + s * split_stride, stored as 16-byte quads
+    SHAPECHK(p.split_stride >= (long long)(p.M - 1) * p.ldc + p.N && p.split_stride % 4 == 0,
+             "gemm: split-K split_stride=%lld (M=%d N=%d ldc=%d): partials overlap or leave 16-byte alignment", p.split_stride, p.M, p.N, p.ldc);
   }
+  // the stash_grad branch of the GEGLU epilogues knows the erf form only (the tape's geglu_stash_form never asks for both)
+  SHAPECHK(!(p.stash_grad && p.geglu_tanh), "gemm: the gradient-form GEGLU stash exists for the erf gate only (geglu_tanh set)");
+  if (!g_num_cus) HIPCHK(gemm_query_cus());
+  const GemmDecision d = gemm_decide(p, g_num_cus, g_gemm_variant, env);
+  p.epi_fast = d.epi_fast;
   if (p.gbwd_pre) {
     // fused GEGLU backward: own instantiations of the persistent kernels
     SHAPECHK(p.epi_fast && p.mode == 0 && !p.res && !p.rowvec && !p.bias && !p.geglu_y && !p.ln_stats && p.ldgp % 8 == 0 &&

@@ -34,16 +34,34 @@ def gemm(a, w, bias=None, rowvec=None, rows_per_batch=1, act=0, res=None, want_p
     return (out, pre) if want_preact else out
 
 
-def gemm_geglu(a, w, bias=None, want_stash=True, stash_grad=True, stash_rows=0):
+def gemm_geglu(a, w, bias=None, want_stash=True, stash_grad=True, stash_rows=0, tanh=False, y=None, stash=None):
     """FF projection with GEGLU in its epilogue (pea_op_gemm_geglu): w [N,K] rows interleaved (h_i, gate_i);
-    returns (h * gelu(gate) [M,N/2], stash [M,N] or None).  stash_grad: the stash holds (gelu(gate), h * gelu'(gate))."""
+    returns (h * gelu(gate) [M,N/2], stash [M,N] or None).  stash_grad: the stash holds (gelu(gate), h * gelu'(gate)).
+    tanh: the gate goes through gelu_new, the tanh form (pea_op_gemm_geglu_tanh; no stash_grad with it).
+    y / stash: caller-provided [M,N/2] / [M,N] buffers."""
     M, K = a.shape
     N = w.shape[0]
-    y = torch.empty(M, N // 2, device=a.device, dtype=BF)
-    st = torch.zeros(M, N, device=a.device, dtype=BF) if want_stash else None
+    if y is None:
+        y = torch.empty(M, N // 2, device=a.device, dtype=BF)
+    st = stash if stash is not None else (torch.zeros(M, N, device=a.device, dtype=BF) if want_stash else None)
+    if tanh:
+        check(lib().pea_op_gemm_geglu_tanh(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(y), ptr(st), M, N, K,
+                                           int(stash_grad), stash_rows, 1, stream_ptr()))
+        return y, st
     check(lib().pea_op_gemm_geglu(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(y), ptr(st), M, N, K,
                                   int(stash_grad), stash_rows, stream_ptr()))
     return y, st
+
+
+def gemm_splitk(a, w, ksplit, part, ldc, split_stride, alpha=1.0):
+    """split-K GEMM (pea_op_gemm_splitk): fp32 partial s of alpha * a @ w.T over its own K-step range, [M,N] with rows ldc
+    apart at part[s * split_stride:]; `part` is a flat fp32 buffer the caller owns.  splitk_reduce_ adds the partials."""
+    M, K = a.shape
+    N = w.shape[0]
+    assert part.dtype == torch.float32 and part.numel() >= (ksplit - 1) * split_stride + (M - 1) * ldc + N
+    check(lib().pea_op_gemm_splitk(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(part), ldc, split_stride, M, N, K, alpha,
+                                   ksplit, stream_ptr()))
+    return part
 
 
 def gemm_geglu_bwd(a, w, pre, form=0):
@@ -74,8 +92,14 @@ def ln_linear(x, gamma, beta, w, bias=None, eps=1e-5, geglu=False):
     return (gy, y) if geglu else y
 
 
-def pack_conv(w_fp32, dgrad=False):
+def pack_conv(w_fp32, dgrad=False, cin_stored=None):
+    """cin_stored: the forward pack for an input stored that many channels wide (zero weights in the padding channels)"""
     Co, Ci = w_fp32.shape[:2]
+    if cin_stored is not None:
+        assert not dgrad, "the padded pack is a forward pack"
+        out = torch.empty(Co, 9 * cin_stored, device=w_fp32.device, dtype=BF)
+        check(lib().pea_op_pack_conv_padded(ptr(w_fp32.contiguous()), ptr(out), Co, Ci, cin_stored, stream_ptr()))
+        return out
     out = torch.empty((Ci, 9 * Co) if dgrad else (Co, 9 * Ci), device=w_fp32.device, dtype=BF)
     check(lib().pea_op_pack_conv(ptr(w_fp32.contiguous()), ptr(out), Co, Ci, int(dgrad), stream_ptr()))
     return out
@@ -93,6 +117,25 @@ def conv3x3(x, w_packed, bias=None, stride=1, upsample2x=False, transposed2=Fals
                                int(transposed2), ptr(bias), ptr(rowvec),
                                rowvec.stride(0) if rowvec is not None else 0, ptr(res), stream_ptr()))
     return y
+
+
+def conv3x3_ex(x, w_packed, bias=None, stride=1, pad_off=0, act=0, res=None, out=None, ldc=None):
+    """pea_op_conv3x3_ex: x [B,H,W,Cs] bf16 NHWC with Cs the stored channel width; w_packed [Cout, 9*Cs].  pad_off=1 (stride 2):
+    F.pad(x, (0,1,0,1)) then stride 2 without padding.  act: 0 none, 1 GELU, 2 SiLU, 3 quick-GELU.  out / ldc: a caller's
+    buffer whose rows are ldc >= Cout wide (only the first Cout columns of a row are written); res [rows, ldres] likewise.
+    Returns [B,Ho,Wo,Cout], or `out` as given."""
+    B, H, W, Cs = x.shape
+    Cout = w_packed.shape[0]
+    Ho, Wo = ((H // 2, W // 2) if pad_off else ((H + 1) // 2, (W + 1) // 2)) if stride == 2 else (H, W)
+    ldc = Cout if ldc is None else ldc
+    if out is None:
+        assert ldc == Cout
+        out = torch.empty(B, Ho, Wo, Cout, device=x.device, dtype=BF)
+    else:
+        assert out.numel() >= (B * Ho * Wo - 1) * ldc + Cout
+    check(lib().pea_op_conv3x3_ex(ptr(x), ptr(w_packed), w_packed.stride(0), ptr(out), ldc, B, H, W, Cs, Cout, stride, pad_off,
+                                  act, ptr(bias), ptr(res), res.shape[-1] if res is not None else 0, stream_ptr()))
+    return out
 
 
 def pack_conv_subpixel(w_fp32, dgrad=False):
