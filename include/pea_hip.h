@@ -1207,6 +1207,35 @@ int pea_op_views_merge(const float* eps, float* canvas, const int* slots, int n_
 int pea_op_cfg_rescale_factors(const float* eps2, int B, long long per, float guidance_scale, float guidance_rescale, void* workspace,
                                float* factor, void* stream);
 
+/* ---- semantic guidance (Brack et al. 2023, "SEGA: Instructing Text-to-Image Models using Semantic Guidance"): K <= 8 edit concepts
+ * ride in the SAME UNet call behind the CFG pair, eps fp32 [(2 + K) B][C][hw] = [u | t | e_1 .. e_K]; each concept's scaled
+ * difference d_c = s_c (e_c - u) (s_c signed: a reversed edit is a negative scale) is kept only in its upper tail, per GROUP = one
+ * (concept, sample, channel) of hw positions: m_c = d_c where |d_c| >= thr_c else 0, thr_c = torch.quantile(|d_c|, q_c) with linear
+ * interpolation: r = q (hw - 1) in fp32, k = floor(r), thr = lerp(v[k], v[min(k + 1, hw - 1)], r - k) over the ascending values v.
+ * A restatement from the paper and diffusers' semantic pipeline (unpinned).  edit_scale, quantile, weight and
+ * warm are HOST arrays of K entries, read at call time and copied into the kernel arguments.  A concept of weight 0 (cooled down) is
+ * not computed and its samples are not read.
+ * pea_op_abs_diff_quantile: thr fp32 [K][B][C]; bounds (may be null) fp32 [K][B][C][2] = the two order statistics.  One launch, one
+ *   workgroup of 1024 threads per group: the group is read once into registers (16 values a thread, so hw <= 16384) and v[k] found by
+ *   an exact radix select over the 32-bit pattern of |d| (four 256-bin histograms in LDS; no sort, no global atomics, no scratch);
+ *   ties are exact: v[k + 1] is v[k] again when more than k + 1 values are <= v[k], else the smallest value above.  thr and bounds
+ *   of a cooled concept are +inf.  hw is free (no multiple of 4 or 64 needed).
+ * pea_op_cfg_sega_combine: the whole step in two launches (the select into `workspace`, pea_op_sega_workspace_bytes(B, C, K), then one
+ *   elementwise pass; the select is skipped when every concept is cooled):
+ *     E_all = sum_c w_c m_c (ascending c), E_warm = sum_c warm_c w_c m_c, used = E_all + mu mom,
+ *     out [B][C][hw] = u + g (t - u) + (any warm_c ? E_warm + mu mom : 0),   mom <- beta mom + (1 - beta) used   (fp32 [B][C][hw], in place).
+ *   The pass recomputes d_c with the select's two operations, so the cut sees the ranked values; u + g (t - u) is
+ *   pea_op_cfg_combine's expression: with every concept cooled and a zero momentum, its bits on [u | t].  The same bits every run.
+ *   Non-finite eps: unspecified.
+ * PEA_E_SHAPE before any device work: a null operand, B < 1, C < 1, hw outside 2..16384, K outside 1..8, a quantile outside [0, 1),
+ * a negative weight, momentum_beta outside [0, 1], a missing workspace. */
+long long pea_op_sega_workspace_bytes(int B, int C, int K);
+int pea_op_abs_diff_quantile(const float* eps, float* thr, float* bounds, int B, int C, int hw, int K, const float* edit_scale,
+                             const float* quantile, const float* weight, void* stream);
+int pea_op_cfg_sega_combine(const float* eps, float* momentum, float* out, int B, int C, int hw, int K, float guidance_scale,
+                            const float* edit_scale, const float* quantile, const float* weight, const int* warm, float momentum_scale,
+                            float momentum_beta, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

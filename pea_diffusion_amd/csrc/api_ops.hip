@@ -577,6 +577,18 @@ int pea_op_cfg_pag_combine(const float* eps, float* out, int B, long long per, i
                            float guidance_rescale, void* workspace, void* stream) {
   return launch_cfg_pag_combine(eps, out, B, per, cfg, guidance_scale, pag_scale, guidance_rescale, workspace, (hipStream_t)stream);
 }
+// ---- semantic guidance (sega.hip: the per-group quantile select and the masked combine)
+long long pea_op_sega_workspace_bytes(int B, int C, int K) { return (long long)sega_workspace_bytes(B, C, K); }
+int pea_op_abs_diff_quantile(const float* eps, float* thr, float* bounds, int B, int C, int hw, int K, const float* edit_scale,
+                             const float* quantile, const float* weight, void* stream) {
+  return launch_abs_diff_quantile(eps, thr, bounds, B, C, hw, K, edit_scale, quantile, weight, (hipStream_t)stream);
+}
+int pea_op_cfg_sega_combine(const float* eps, float* momentum, float* out, int B, int C, int hw, int K, float guidance_scale,
+                            const float* edit_scale, const float* quantile, const float* weight, const int* warm, float momentum_scale,
+                            float momentum_beta, void* workspace, void* stream) {
+  return launch_cfg_sega_combine(eps, momentum, out, B, C, hw, K, guidance_scale, edit_scale, quantile, weight, warm, momentum_scale,
+                                 momentum_beta, workspace, (hipStream_t)stream);
+}
 // ---- LoRA weight composition (lora.hip)
 int pea_op_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank, float scale,
                         void* stream) {

@@ -396,6 +396,13 @@ int launch_views_merge(const float* eps, float* canvas, const int* slots, int n_
                        int first, int last, hipStream_t s);
 // cfg_combine's statistics and factor kernels alone: factor[B] of rescale_noise_cfg, workspace of cfg_combine_workspace_bytes(B)
 int launch_cfg_rescale_factors(const float* eps2, int B, long long per, float g, float rescale, void* ws, float* factor, hipStream_t s);
+// sega.hip: semantic guidance.  eps [(2 + K) B][C][hw] with the K edit concepts last; the K-arrays are host memory, read at call time
+size_t sega_workspace_bytes(int B, int C, int K);
+int launch_abs_diff_quantile(const float* eps, float* thr, float* bounds, int B, int C, int hw, int K, const float* edit_scale,
+                             const float* quantile, const float* weight, hipStream_t s);
+int launch_cfg_sega_combine(const float* eps, float* momentum, float* out, int B, int C, int hw, int K, float g, const float* edit_scale,
+                            const float* quantile, const float* weight, const int* warm, float mu, float beta, void* ws,
+                            hipStream_t s);
 // lora.hip: out[M][Kf] = acc + scale * up[M][rank] . down[rank][Kf], fp32 (acc may be out)
 int launch_lora_compose(const float* acc, const float* down, const float* up, float* out, int M, int Kf, int rank,
                         float scale, hipStream_t s);

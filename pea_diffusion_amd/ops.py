@@ -794,6 +794,63 @@ def cfg_pag_combine(noise_pred, guidance_scale, pag_scale, guidance_rescale=0.0,
     return out
 
 
+# ---- semantic guidance (Brack et al. 2023; pea_diffusion_amd/sega.py is the loop)
+def _sega_operands(op, eps, edit_scale, quantile, weight):
+    """B, C, hw, K and the three host arrays of the SEGA entries, for eps fp32 [(2 + K) B, C, ...]"""
+    K = len(edit_scale)
+    if not (K >= 1 and len(quantile) == K and len(weight) == K):
+        raise PeaError(f"{op}: {K} edit scales, {len(quantile)} quantiles, {len(weight)} weights (one each per concept, at least one)")
+    if eps.dtype != torch.float32 or not eps.is_contiguous() or eps.dim() < 3 or eps.shape[0] % (2 + K):
+        raise PeaError(f"{op}: noise_pred {tuple(eps.shape)} {eps.dtype}, expected contiguous fp32 [(2 + {K}) B, C, ...] "
+                       "([uncond | text | edit_1 .. edit_K])")
+    B, C = eps.shape[0] // (2 + K), eps.shape[1]
+    arr = lambda v: (ctypes.c_float * K)(*[float(a) for a in v])
+    return B, C, eps[0, 0].numel(), K, arr(edit_scale), arr(quantile), arr(weight)
+
+
+def abs_diff_quantile(noise_pred, edit_scale, quantile, weight, want_bounds=False):
+    """The per-group cut of semantic guidance in one launch (pea_op_abs_diff_quantile).  noise_pred fp32 [(2 + K) B, C, h, w] =
+    [uncond | text | edit_1 .. edit_K]; edit_scale, quantile, weight: K numbers each.  -> thr fp32 [K, B, C] =
+    `torch.quantile((s_c (e_c - u)).abs().flatten(2), q_c, dim=2)` (+inf for a concept of weight 0), and with want_bounds the
+    two order statistics it interpolates, fp32 [K, B, C, 2]."""
+    B, C, hw, K, s, q, w = _sega_operands("abs_diff_quantile", noise_pred, edit_scale, quantile, weight)
+    thr = torch.empty(K, B, C, device=noise_pred.device, dtype=torch.float32)
+    bounds = torch.empty(K, B, C, 2, device=noise_pred.device, dtype=torch.float32) if want_bounds else None
+    check(lib().pea_op_abs_diff_quantile(ptr(noise_pred), ptr(thr), ptr(bounds), B, C, hw, K, s, q, w, stream_ptr()))
+    return (thr, bounds) if want_bounds else thr
+
+
+def sega_workspace(B, C, K, device):
+    """the workspace `cfg_sega_combine` takes (pea_op_sega_workspace_bytes): allocate once before a loop"""
+    return torch.empty(lib().pea_op_sega_workspace_bytes(int(B), int(C), int(K)), device=device, dtype=torch.uint8)
+
+
+def cfg_sega_combine(noise_pred, momentum, guidance_scale, edit_scale, quantile, weight, warm, momentum_scale=0.1, momentum_beta=0.4,
+                     workspace=None, out=None):
+    """One step of semantic guidance in two launches (pea_op_cfg_sega_combine).  noise_pred fp32 [(2 + K) B, C, h, w] =
+    [uncond | text | edit_1 .. edit_K]; momentum fp32 [B, C, h, w], updated IN PLACE; edit_scale (signed), quantile, weight,
+    warm: K numbers each.  m_c = d_c where |d_c| >= its group's quantile else 0 with d_c = s_c (e_c - u);
+    -> u + g (t - u) + (any warm ? sum_c warm_c w_c m_c + mu mom : 0), fp32 [B, C, h, w], and
+    mom <- beta mom + (1 - beta) (sum_c w_c m_c + mu mom).  Every weight 0 and a zero momentum: the bits of `cfg_combine`."""
+    B, C, hw, K, s, q, w = _sega_operands("cfg_sega_combine", noise_pred, edit_scale, quantile, weight)
+    if len(warm) != K:
+        raise PeaError(f"cfg_sega_combine: {len(warm)} warm flags for {K} concepts")
+    shape = (B,) + tuple(noise_pred.shape[1:])
+    for name, t in (("momentum", momentum), ("out", out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != noise_pred.device):
+            raise PeaError(f"cfg_sega_combine: {name} {tuple(t.shape)} {t.dtype}, expected contiguous fp32 {shape} on the device")
+    if momentum is None:
+        raise PeaError("cfg_sega_combine: the momentum buffer is missing")
+    if out is None:
+        out = torch.empty(shape, device=noise_pred.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = sega_workspace(B, C, K, noise_pred.device)
+    flags = (ctypes.c_int * K)(*[int(bool(a)) for a in warm])
+    check(lib().pea_op_cfg_sega_combine(ptr(noise_pred), ptr(momentum), ptr(out), B, C, hw, K, float(guidance_scale), s, q, w, flags,
+                                        float(momentum_scale), float(momentum_beta), ptr(workspace), stream_ptr()))
+    return out
+
+
 def dpm_update_(sample, eps, x0_prev, alpha_s, sigma_s, c_s, c_0, c_1):
     """In place: x0 = (sample - sigma_s*eps)/alpha_s; sample <- c_s*sample + c_0*x0 + c_1*x0_prev; x0_prev <- x0."""
     for t in (sample, eps, x0_prev):
